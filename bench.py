@@ -5,11 +5,16 @@ Metric (BASELINE.json): "MNT4-753 G1 MSM scalar-muls/sec + 2^n NTT ms at 1/2/4/8
   value  = whole-job MSM throughput: every rank runs one complete MNT4-753 G1 MSM of 2^log_n
            (base, scalar) pairs per step on its own GPU (bases and scalars already resident in
            HBM), then the partial sums are all-gathered and folded (weak scaling, one exchange).
-  ntt    = (extra object) 2^ntt_log_n-point MNT4-753 Fr NTT, device resident, ms per transform.
+  ntt    = (extra object, --full) 2^ntt_log_n-point MNT4-753 Fr NTT, device resident, ms per transform.
 One "step" = one pass of the MSM hot path over one batch of synthetic input.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the figures taken from
+those steps.  --full adds everything else: the closed-form checks, the per-window path, single-MSM latency, the product
+peak and kernel resources, the drop-in path, the 2^24-pair, G2, NTT and prover objects and the CPU baseline.
+--dump-outputs DIR writes the result of the last timed step as DIR/*.npy (float64, see dump_outputs).
 """
 import argparse
 import json
@@ -36,6 +41,18 @@ def kernels_sha():
     return h.hexdigest()
 
 
+def dump_outputs(d, gl, curve, xyz):
+    """--dump-outputs: the MSM result of the last timed step (rank 0: the sum over all ranks), normalised to affine as
+    into_affine does (gh_proj_to_affine), since the projective triple a caller receives is one of many for the same point.
+    msm_affine_xy.npy: x, y as (2, deg, 24) 32-bit words of their Montgomery limbs, low word first; msm_affine_infinity.npy:
+    (1,) 1 for the point at infinity.  float64 holds every 32-bit word exactly."""
+    os.makedirs(d, exist_ok=True)
+    xy, inf = gl.proj_to_affine(curve, xyz)
+    words = np.ascontiguousarray(xy, dtype=np.uint64).view(np.uint32).astype(np.float64)
+    np.save(os.path.join(d, "msm_affine_xy.npy"), words.reshape(2, -1, 24))
+    np.save(os.path.join(d, "msm_affine_infinity.npy"), np.array([1.0 if inf else 0.0]))
+
+
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 measured)
 FPMUL_PEAK_PER_S = 23.4e9       # measured 753-bit Montgomery products/s, profiles/r01_microbench_valu_rates.txt
 
@@ -60,7 +77,14 @@ def main():
     ap.add_argument("--curve", default="mnt4753_g1", choices=["mnt4753_g1", "mnt4753_g2", "mnt6753_g1", "mnt6753_g2"])
     ap.add_argument("--total-log-n", type=int, default=0,
                     help="strong scaling (BASELINE config 4): 2^total-log-n pairs in all, 2^total-log-n / N per GPU; overrides --log-n")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every check and extra object beyond the headline (closed forms, per-window path, drop-in path, "
+                         "2^24, G2, NTT, prover, CPU baseline; the --no-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the MSM result of the last timed step to DIR/*.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Started as a plain `python bench.py --gpus N`: become the launcher.  One rank per GPU is started as a child
@@ -198,11 +222,11 @@ def main():
     ds = gl.DeviceBuffer(n * 96).upload(scalars)
     # The bases are a proving key: uploaded once, outside the timed region, and -- like the
     # layout conversion at upload -- expanded once into the shift table 2^(c w) P_i (gh_bases_precompute).
-    # The per-window path (no table) is timed as well and reported under "per_window_path".
+    # With --full the per-window path (no table) is timed as well and reported under "per_window_path".
     plain = None
     table_info = None
     phases_alone = None
-    if not args.no_precompute and not args.window:
+    if args.full and not args.no_precompute and not args.window:
         for _ in range(max(1, args.warmup)):
             rb.msm_dev(ds, n)
         gl.load_library().gh_dev_sync()
@@ -219,6 +243,7 @@ def main():
                  "num_windows": ptm["num_windows"], "accumulate_ms": ptm["accumulate_ms"], "steps": PW_STEPS,
                  "pipelined_batch": {"value": n / dtb, "ms_per_step": dtb * 1e3, "steps": PW_STEPS},
                  "closed_form_ok": closed_form_ok(curve, key_p0, key_step, scalars, plain_out)}
+    if not args.no_precompute and not args.window:
         t0 = time.perf_counter()
         c_tab = rb.precompute(0)
         rows = 752 // c_tab + 1
@@ -227,6 +252,7 @@ def main():
                       "note": "one-time per resident key, outside the timed region (like the base upload); key_load_s = key_generate_s "
                               "(synthetic chain on the device; a real key pays its upload instead) + build_s"}
         table_info["key_load_s"] = key_generate_s + table_info["build_s"]
+    if plain is not None:
         a1 = gl.proj_to_affine(curve, rb.msm_dev(ds, n))
         t0 = time.perf_counter()
         solo_tm = []
@@ -276,6 +302,9 @@ def main():
     AFF_MODE = "affine rounds (asmgen/g2_rounds.py) + projective finish" if os.environ.get("GH_AFF_ASM", "1") != "0" else "affine rounds (aff_kernels.h) + projective finish"
     bucket_mode = AFF_MODE if (C.deg > 1 and os.environ.get("GH_AFFINE", "2") != "0") or os.environ.get("GH_AFFINE") == "1" \
         else ("XYZZ mixed additions (madd-2008-s, 8 M + 2 S, Y3 as one dual product)" if xyzz else "projective mixed additions")
+    # set-up, untimed: a batch allocates its buffers on first use (two pipeline slots, pinned staging per job index mod 4);
+    # one batch of four allocates them all, so that the timed steps pay for none of them whatever --warmup is
+    gl.msm_batch_dev([(rb, ds, n)] * 4)
     if args.warmup:
         run_steps(args.warmup)
     sync()
@@ -295,6 +324,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = world * n * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gl, curve, result)
     tm_last = tm
     acc_avg_ms = float(np.mean(acc_ms))
     # bytes per pair = affine base + 96-byte scalar, read once: G1 288 B, MNT4 G2 480 B, MNT6 G2 672 B
@@ -304,17 +335,19 @@ def main():
     # base-field products per addition: projective mixed addition 11 (madd-1998-cmo); affine rounds 5 M + 1 S (+ the shared
     # inversion, not counted); tower fields: Fq2 product = 4 Fp products in the lane-pair form, Fq3 = 9
     per_add = (6 if bucket_mode.startswith("affine") else (10 if xyzz else 11)) * {1: 1, 2: 4, 3: 9}[C.deg]
-    # every rank checks ITS partial sum (own key, own scalars) against the closed form; the line reports the AND over ranks
-    cf_ok = closed_form_ok(curve, key_p0, key_step, scalars, own_partial[0])
-    if world > 1:
-        import torch
-        f = torch.tensor([1 if cf_ok else 0])
-        dist.all_reduce(f, op=dist.ReduceOp.MIN)
-        cf_ok = bool(int(f.item()))
+    # --full: every rank checks ITS partial sum (own key, own scalars) against the closed form; the line reports the AND over ranks
+    cf_ok = None
+    if args.full:
+        cf_ok = closed_form_ok(curve, key_p0, key_step, scalars, own_partial[0])
+        if world > 1:
+            import torch
+            f = torch.tensor([1 if cf_ok else 0])
+            dist.all_reduce(f, op=dist.ReduceOp.MIN)
+            cf_ok = bool(int(f.item()))
     fpmul_rate = madds * per_add / (acc_avg_ms * 1e-3)
-    # measured on this box, in this run: the product peak and what the code object says about the three hot kernels
+    # --full, measured on this card, in this run: the product peak and what the code object says about the hot kernels
     peak_now, hot_kernels = None, None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             peak_now = gl.measure_fpmul_peak()
             hot_kernels = {k: gl.kernel_resources(k) for k in ("g1_acc_p4", "g2_f2_bwd_r0", "g2_f3_bwd_r0", "ntt_p6_k8")}
@@ -370,9 +403,6 @@ def main():
                                         "lean (lane-level) form for every MSM of the batch but the last, from 2^25 list entries; segment form otherwise")
                                        if (C.deg == 1 and not args.no_pipeline) else "segment form",
                    "parallelism": "pairs sharded by rank, 1 all-gather of partial sums" if world > 1 else "single GPU"},
-        "closed_form_ok": cf_ok,
-        "closed_form_note": "each rank's partial sum of the last timed step == (sum s_i) P_0 + (sum i s_i) H on its chain key, evaluated with "
-                            "Python integers (tests/support.py chain_msm_closed_form): an answer no MSM code path produced",
         "roofline": {"kernel": "%s (bucket accumulation of the %s MSM)" % (("gh_asm_acc_g1 (generated assembly of msm_accumulate_xyzz_kernel)" if os.environ.get("GH_ACC_ASM", "1") != "0" else "msm_accumulate_xyzz_kernel") if xyzz else "msm_accumulate_kernel / aff_round_kernel", curve), "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_acc,
                      "traffic_note": "FETCH_SIZE + WRITE_SIZE bytes of the accumulation launches of one MSM from %s (separate rocprofv3 --pmc passes), null when that file was measured on other kernel sources (sha256 of ginger-lib_amd/csrc and asmgen) or another workload; measured by the builder: %s" % (traffic_src, traffic_when or "box and date unknown"),
@@ -400,8 +430,12 @@ def main():
                            "bytes_per_rank_and_msm": 288 * C.deg, "exchanges_per_timed_region": 1,
                            "avg_us": float(np.mean(exch_us[-1:])) if exch_us else None,
                            "note": "the partial sums of all timed steps travel in ONE all-gather after the batch; avg_us = that exchange"}
-    if not cf_ok:
-        out["error"] = "MSM result differs from the closed form on the chain key"
+    if cf_ok is not None:
+        out["closed_form_ok"] = cf_ok
+        out["closed_form_note"] = ("each rank's partial sum of the last timed step == (sum s_i) P_0 + (sum i s_i) H on its chain key, evaluated with "
+                                   "Python integers (tests/support.py chain_msm_closed_form): an answer no MSM code path produced")
+        if not cf_ok:
+            out["error"] = "MSM result differs from the closed form on the chain key"
     if plain is not None:
         out["per_window_path"] = plain
         if not plain["same_affine_result_as_table_path"]:
@@ -413,7 +447,7 @@ def main():
     #      hashed on every call (identity = content), found resident, and only the scalars cross PCIe; nothing is pipelined.
     #      Pageable host arrays, as a Vec is.  `handle_path` = the same four calls for a caller that holds the handle
     #      (gh_msm_resident: no hash).
-    if rank == 0 and world == 1 and not args.window and not args.no_precompute:
+    if args.full and rank == 0 and world == 1 and not args.window and not args.no_precompute:
         host_s = [scalars, scalars[::-1].copy(), scalars.copy(), scalars[::-1].copy()]
         host_bases = rb.download(0, n)
         gl.key_cache_clear()
@@ -448,7 +482,7 @@ def main():
         del host_bases
 
     # ---- BASELINE config 3's second size: 2^24 pairs (per-window path and shift table c = 23, 115 GB), same line
-    if not args.no_2p24 and rank == 0 and world == 1 and curve == "mnt4753_g1" and not args.window and args.log_n < 24:
+    if args.full and not args.no_2p24 and rank == 0 and world == 1 and curve == "mnt4753_g1" and not args.window and args.log_n < 24:
         try:
             n24 = 1 << 24
             rb24, p0_24, st_24 = chain_key(curve, n24, 77)
@@ -521,7 +555,7 @@ def main():
             out["msm_2p24"] = {"error": str(e)}
 
     # ---- G2 (the prover's b_g2 MSM: BASELINE configs 4 / 5 shapes), one MSM at a time and as a pipelined batch of ten
-    if not args.no_g2 and rank == 0 and world == 1 and curve == "mnt4753_g1" and not args.window:
+    if args.full and not args.no_g2 and rank == 0 and world == 1 and curve == "mnt4753_g1" and not args.window:
         out["g2"] = {}
         for crv, lg in (("mnt4753_g2", 20), ("mnt6753_g2", 19)):
             try:
@@ -570,7 +604,7 @@ def main():
                 out["g2"][crv] = {"error": str(e)}
 
     # ---- NTT (single GPU per rank; reported from rank 0)
-    if not args.no_ntt and rank == 0:
+    if args.full and not args.no_ntt and rank == 0:
         N = 1 << args.ntt_log_n
         a = S.random_scalars_np(N, seed=7, below=pyref.P6.p)
         buf = gl.DeviceBuffer(N * 96).upload(a)
@@ -607,7 +641,7 @@ def main():
                                    "algorithmic_bytes_per_transform": nb}}
 
     # ---- CPU baseline: the oracle (restated reference algorithm, C++) on the host cores, bounded sample
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         cores = os.cpu_count() or 1
         m = n                      # the headline's own size (2^20 pairs: ~11 s on the box's host cores)
         import math
@@ -662,7 +696,7 @@ def main():
     #      and made resident (gh_bases_upload_wire + shift tables); the timed part is prover.rs:201-346 from the host's limb arrays
     #      on: rows over PCIe, witness map, into_repr, four G1 MSMs as one batch and one G2 MSM, host fold.  A, B, C are checked
     #      against the Groth16 equations evaluated in the exponent from the toxic waste (no MSM / FFT code path involved).
-    if not args.no_prover and rank == 0 and world == 1 and curve == "mnt4753_g1" and not args.window:
+    if args.full and not args.no_prover and rank == 0 and world == 1 and curve == "mnt4753_g1" and not args.window:
         try:
             gl.dev_trim()
             import importlib

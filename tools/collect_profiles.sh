@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 # chain keys (distinct bases, as bench.py's): a tiled key is a key of equal bases, which the library now adds up front
 P="python3 $R/tools/g2_probe.py"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/stats" -o run -- python3 "$R/bench.py" --no-cpu-baseline --no-2p24 > "$R/$OUT/stats.log" 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/stats" -o run -- python3 "$R/bench.py" --full --no-cpu-baseline --no-2p24 > "$R/$OUT/stats.log" 2>&1 || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$R/$OUT/g1_$c" -o run -- $P mnt4753_g1 20 2 > "$R/$OUT/g1_$c.log" 2>&1 || exit 1
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$R/$OUT/g2_$c" -o run -- $P mnt4753_g2 20 2 > "$R/$OUT/g2_$c.log" 2>&1 || exit 1
