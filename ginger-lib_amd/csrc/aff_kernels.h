@@ -20,8 +20,8 @@
 //   x1 == x2 otherwise       -> the point at infinity, stored as a marker (x.l[0] = 0xFFFFFFFF, not a limb value)
 //   marker + Q -> Q
 // Both rare paths sit behind a wave-uniform `any` so the common case pays nothing for them.
-// After the last round a bucket holds a few points at most; msm_accumulate_kernel<.., AFFIN = true> adds them
-// projectively (identity list, markers skipped) and leaves the buckets in the form the reduction expects.
+// After the last round a bucket holds a few points at most; msm_accumulate_xyzz_kernel / msm_accumulate_split_kernel
+// <.., AFFIN = true> add them projectively (identity list, markers skipped) and leave the buckets in the form the reduction expects.
 //
 // Memory layout ("T64"): the intermediate lists and the running products are stored wave-tiled and 16-byte-chunk
 // major -- a tile holds the 64 lane slots of one wave iteration, chunk c of slot s at ((tile * NCH + c) * 64 + s) * 16
@@ -228,19 +228,17 @@ template <class C, class FS, bool R0> struct AffRoundLane {
     // touches 64 different pages; the L1 translation cache holds fewer, and with the 14 loads of a row issued wave-wide
     // each of them missed all 64 translations again (measured: 4.9e8 UTCL1 misses for 18.4 M additions -- 13 per row --
     // against 1.6e3 in a later round; 3.7 wave cycles per VALU instruction against 2.0).  The row is therefore fetched a
-    // part of the wave at a time: the pages of 64 / GH_AFF_GATHER_SPLIT lanes stay resident across the row's loads
+    // part of the wave at a time: the pages of 64 / GATHER_SPLIT lanes stay resident across the row's loads
     // (4.9e8 -> 2.6e7 misses, round 0 13.8 -> 12.0 ms).
-#ifndef GH_AFF_GATHER_SPLIT
-#define GH_AFF_GATHER_SPLIT 4
-#endif
+    static constexpr int GATHER_SPLIT = 4;
     GH_HD static void gather_row(const AffRoundArgs<C>& a, uint32_t idx, int comp, T& x, T& y) {
         const Fp* px = coef(a.rows + idx, 0, comp);
         const Fp* py = coef(a.rows + idx, 1, comp);
         const bool hx = LANES == 1 ? false : (comp & 1) != 0, hy = LANES == 1 ? true : ((LANES + comp) & 1) != 0;
 #if defined(__HIP_DEVICE_COMPILE__)
-        const int part = (int)((threadIdx.x & 63u) / (64 / GH_AFF_GATHER_SPLIT));
+        const int part = (int)((threadIdx.x & 63u) / (64 / GATHER_SPLIT));
 #pragma unroll
-        for (int q = 0; q < GH_AFF_GATHER_SPLIT; q++) {
+        for (int q = 0; q < GATHER_SPLIT; q++) {
             if (part == q) { x = ld_fp_wide(px, hx); y = ld_fp_wide(py, hy); }
             __builtin_amdgcn_sched_barrier(0);
         }

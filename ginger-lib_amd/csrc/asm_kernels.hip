@@ -18,6 +18,7 @@ namespace gh_asm {
 
 using gh_rt::g;
 using gh_rt::g_err;
+using gh_rt::env_int;
 
 namespace {
 constexpr int NTT_ASM_KMIN = 6, NTT_ASM_KMAX = 8;
@@ -108,7 +109,7 @@ int load_locked() {
 }  // namespace
 
 bool enabled() {
-    static const bool on = !(getenv("GH_ACC_ASM") && atoi(getenv("GH_ACC_ASM")) == 0);
+    static const bool on = env_int("GH_ACC_ASM", 1) != 0;
     return on;
 }
 
@@ -131,12 +132,12 @@ int acc_g1_launch(int prime, const void* bases, const uint32_t* sorted, const Ac
 }
 
 bool aff_enabled() {
-    static const bool on = !(getenv("GH_AFF_ASM") && atoi(getenv("GH_AFF_ASM")) == 0);
+    static const bool on = env_int("GH_AFF_ASM", 1) != 0;
     return on;
 }
 
 bool aff_g1_enabled() {
-    static const bool on = !(getenv("GH_AFF_ASM_G1") && atoi(getenv("GH_AFF_ASM_G1")) == 0);
+    static const bool on = env_int("GH_AFF_ASM_G1", 1) != 0;
     return on && aff_enabled();
 }
 
@@ -157,7 +158,7 @@ int aff_launch(int tower, bool fwd, bool r0, const AffArgs& a, uint32_t waves, h
 }
 
 bool ntt_enabled() {
-    static const bool on = !(getenv("GH_NTT_ASM") && atoi(getenv("GH_NTT_ASM")) == 0);
+    static const bool on = env_int("GH_NTT_ASM", 1) != 0;
     return on;
 }
 

@@ -284,7 +284,7 @@ template <> const MsmOps* fixed_ops<Mnt6G2>() { return msm_ops_mnt6753_g2(); }
 
 // d_out[i] = sum over rows of table[outer][digit_outer(scalar i)] on g.stream (scalars already on the device)
 template <class C> int launch_fixed_sums(const FixedTable* t, const void* d_s, size_t n, void* d_o) {
-    static const bool naive = getenv("GH_FIXED_NAIVE") && atoi(getenv("GH_FIXED_NAIVE")) != 0;
+    static const bool naive = env_int("GH_FIXED_NAIVE", 0) != 0;
     if (naive || t->has_marks || n * (size_t)t->outerc >= ((size_t)1 << 31)) {
         GH_LAUNCH((fixed_msm_kernel<C>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, g.stream, (const Aff<C>*)t->d_table,
                            t->window, t->outerc, t->scalar_size, (const uint32_t*)d_s, n, (Proj<C>*)d_o);

@@ -231,10 +231,7 @@ int gh_shutdown(void) try {
     std::lock_guard<std::mutex> lk(g_mu);
     dist_teardown_locked();              // a communicator must not outlive the streams and the device binding it was made on
     if (!g.ready) return GH_OK;
-    hipStreamSynchronize(g.stream);
-    hipStreamSynchronize(g.stream_acc);
-    hipStreamSynchronize(g.stream_acc2);
-    hipStreamSynchronize(g.stream_red);
+    (void)sync_msm_streams();
     for (auto& kv : g.pool) if (kv.second.p) hipFree(kv.second.p);
     g.pool.clear();
     for (auto& f : g.at_shutdown) f();   // function-local device / pinned allocations (msm_impl.h)
@@ -408,7 +405,7 @@ int gh_msm_resident_dev_batch(const gh_bases_t* handles, const void* const* d_sc
     if (rc) return rc;
     rc = ops->batch(hs.data(), d_scalars, n_scalars, count, out_xyz);
     if (rc) {   // leave no stage of a failed pipeline in flight
-        hipStreamSynchronize(g.stream); hipStreamSynchronize(g.stream_acc); hipStreamSynchronize(g.stream_red);
+        (void)sync_msm_streams();
     }
     return rc;
 } catch (...) { return gh_rt::api_exception(); }
@@ -617,7 +614,7 @@ void cache_fit(const BasesBase* keep) {
         for (size_t i = 0; i < kc.e.size(); i++)
             if (kc.e[i].key != keep && (victim == kc.e.size() || kc.e[i].stamp < kc.e[victim].stamp)) victim = i;
         if (victim == kc.e.size()) return;           // only `keep` is left: a key larger than the budget stays for this call
-        hipStreamSynchronize(g.stream); hipStreamSynchronize(g.stream_acc); hipStreamSynchronize(g.stream_red);
+        (void)sync_msm_streams();
         free_key(kc.e[victim].key);
         kc.e.erase(kc.e.begin() + (long)victim);
         kc.st.evictions++;
@@ -656,7 +653,7 @@ int gh_key_cache_config(size_t max_bytes, int table_after) try {
 } catch (...) { return gh_rt::api_exception(); }
 int gh_key_cache_clear(void) try {
     std::lock_guard<std::mutex> lk(g_mu);
-    if (g.ready) { hipStreamSynchronize(g.stream); hipStreamSynchronize(g.stream_acc); hipStreamSynchronize(g.stream_red); }
+    if (g.ready) (void)sync_msm_streams();
     cache_drop_all();
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
@@ -736,7 +733,7 @@ int gh_msm_cached(gh_curve_t curve, const uint64_t* bases, const uint8_t* infini
         rc = ops->upload(bases, infinity, n, 0, &h);
         if (rc == GH_E_NOMEM && !kc.e.empty()) {      // the cache is only a cache: make room and try once more
             (void)hipGetLastError();
-            hipStreamSynchronize(g.stream); hipStreamSynchronize(g.stream_acc); hipStreamSynchronize(g.stream_red);
+            (void)sync_msm_streams();
             cache_drop_all();
             rc = ops->upload(bases, infinity, n, 0, &h);
         }
@@ -1030,9 +1027,7 @@ int gh_dev_download(void* h_dst, const void* d_src, size_t bytes) try {
 int gh_dev_trim(void) try {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g.ready) return GH_OK;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream_acc));
-    HIPCHK(hipStreamSynchronize(g.stream_red));
+    HIPCHK(sync_msm_streams());
     pool_release("");
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }

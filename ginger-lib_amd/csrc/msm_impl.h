@@ -12,28 +12,6 @@
 #include "asm_kernels.h"
 #include "host_math.h"
 
-#ifndef GH_F3S_TRIPLE
-#define GH_F3S_TRIPLE 2   // Fq3 tower product in the projective accumulation / reduction kernels (F3S in msm_kernels.h):
-                          //   0 = three plain products in a rolled loop (three reductions, 4056 mads), 2 waves/SIMD
-                          //   1 = triple product with ONE reduction (fp_mul3, 2704 mads) inlined at every site: hipcc did not finish
-                          //       that kernel in 25 minutes (eleven sites) -- kept for the record
-                          //   2 = the same triple product as ONE out-of-line device function (f3s_mul_outlined): compiles in seconds;
-                          //       2^19 pairs: projective accumulation 222 -> 167 ms, bucket reduction 17.4 -> 13.6 ms
-#endif
-#ifndef GH_AFF_F3S_TRIPLE
-#define GH_AFF_F3S_TRIPLE 2   // the same choice for the Fq3 affine rounds: 0 = rolled (2^19 pairs: rounds + finish 133 ms), 1 = inlined
-                              // triple product (not compiled after 70 CPU-minutes), 2 = out-of-line triple product at one wave per
-                              // SIMD (98 ms; at two waves per SIMD, GH_F3S_CALL_WAVES=2, the caller spills 1.4 KB: 140 ms)
-#endif
-#ifndef GH_AFF_F2S_DUAL
-#define GH_AFF_F2S_DUAL 1   // Fq2 affine rounds: 1 = dual product, one wave per SIMD (2^20 pairs: 68 ms); 0 = two plain products, two waves
-                            // per SIMD (784 B of spills: 91 ms)
-#endif
-#ifndef GH_F2S_DUAL
-#define GH_F2S_DUAL 1   // Fq2 accumulation: 1 = dual product at 1 wave/SIMD (119 ms at 2^20 pairs); 0 = two plain products per
-                        // lane at 2 waves/SIMD, measured 166 ms (1.8 KB of spills: both shuffled operand sets stay live)
-#endif
-
 namespace gh_rt {
 using namespace gh;
 
@@ -173,7 +151,7 @@ int dedup_bases(BasesBase* h) {
     if (h->d_dup_members) { (void)hipFree(h->d_dup_members); h->d_dup_members = nullptr; }
     if (h->d_dup_chunks) { (void)hipFree(h->d_dup_chunks); h->d_dup_chunks = nullptr; }
     h->n_dup_groups = h->n_dup_members = h->n_dup_chunks = 0;
-    static const bool off = getenv("GH_DEDUP") && atoi(getenv("GH_DEDUP")) == 0;
+    static const bool off = env_int("GH_DEDUP", 1) == 0;
     const size_t n = h->n;
     if (off || !g.dedup_mode || n < 2 || n >= ((size_t)1 << 31)) return GH_OK;
     hipStream_t st = g.stream;
@@ -280,7 +258,7 @@ int precompute_bases(BasesBase* h, int c_req, int max_rows) {
     // folded with c doublings each (finish()).  For keys whose full table does not fit next to the others (four 2^24-base
     // G1 queries: 4 x 126 GB at c = 21): 8 rows are 28 GB.  A capped table keeps its sets at 2^20 buckets (c = 21) where the
     // full table of a large key would take c = 23: the sets multiply the bucket reduction.
-    const int env_rows = getenv("GH_TABLE_ROWS") ? atoi(getenv("GH_TABLE_ROWS")) : 0;
+    const int env_rows = env_int("GH_TABLE_ROWS", 0);
     const int cap = max_rows > 0 ? max_rows : env_rows;
     int c = c_req > 0 ? c_req : precompute_window(n, C::F::DEG);
     if (c_req <= 0 && cap > 0 && cap < 752 / c + 1 && c > 21) c = 21;
@@ -295,20 +273,16 @@ int precompute_bases(BasesBase* h, int c_req, int max_rows) {
     const size_t slab = n < ((size_t)1 << 20) ? n : ((size_t)1 << 20);
     const size_t need = (size_t)W * n * sizeof(Aff<C>) + 2 * (size_t)(W - 1) * slab * sizeof(FT) + ((size_t)1 << 30);
     if (need > free_b) {   // the scratch caches of earlier calls (bucket lists, affine-round lists) are only caches: drop them
-        HIPCHK(hipStreamSynchronize(g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream_acc));
-        HIPCHK(hipStreamSynchronize(g.stream_red));
+        HIPCHK(sync_msm_streams());
         pool_release("");
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
     }
     if (need > free_b) { g_err = "not enough device memory for the precomputed table"; return GH_E_NOMEM; }
-    if (const char* t = getenv("GH_TEST_TABLE_NOMEM"); t && atoi(t) != 0) {
+    if (env_int("GH_TEST_TABLE_NOMEM", 0) != 0) {
         // fault injection (include/ginger_hip.h gh_test_hooks): the path a table build takes when the card is full -- every pooled
         // scratch buffer is dropped, the key stays on the per-window path.  tests/test_gpu_parity.py runs gh_msm_cached through it
         // on every GPU run (the round-3 fault: a pooled scalar buffer freed here under a running copy).
-        HIPCHK(hipStreamSynchronize(g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream_acc));
-        HIPCHK(hipStreamSynchronize(g.stream_red));
+        HIPCHK(sync_msm_streams());
         pool_release("");
         g_err = "not enough device memory for the precomputed table (GH_TEST_TABLE_NOMEM)";
         return GH_E_NOMEM;
@@ -326,24 +300,17 @@ int precompute_bases(BasesBase* h, int c_req, int max_rows) {
     if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 4, st);
     for (size_t i0 = 0; i0 < n && e == hipSuccess; i0 += slab) {
         const size_t cnt = n - i0 < slab ? n - i0 : slab;
-        static const bool pre_jac = !(getenv("GH_PRE_JAC") && atoi(getenv("GH_PRE_JAC")) == 0);
         {   // the table builders carry 2-9 KB of stack per lane: no dispatch the card cannot back with scratch (runtime.h scratch_guard)
-            const void* kfn = !pre_jac ? (const void*)(msm_precompute_kernel<C>)
-                              : (C::F::DEG == 1 ? (const void*)(msm_precompute_jac_kernel<C, typename C::F>)
-                                                : (const void*)(msm_precompute_jac_kernel<C, typename C::FC>));
+            const void* kfn = C::F::DEG == 1 ? (const void*)(msm_precompute_jac_kernel<C, typename C::F>)
+                                             : (const void*)(msm_precompute_jac_kernel<C, typename C::FC>);
             if (int grc = scratch_guard(kfn, (cnt + 255) / 256 * 256)) { hipFree(table); return grc; }
         }
-        if (pre_jac) {
-            if constexpr (C::F::DEG == 1)
-                hipLaunchKernelGGL((msm_precompute_jac_kernel<C, typename C::F>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st,
-                                   table, (const uint8_t*)h->d_inf, n, i0, cnt, slab, c_row, W, zs, zp, bad);
-            else
-                hipLaunchKernelGGL((msm_precompute_jac_kernel<C, typename C::FC>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, st,
-                                   table, (const uint8_t*)h->d_inf, n, i0, cnt, slab, c_row, W, zs, zp, bad);
-        } else {
-            hipLaunchKernelGGL((msm_precompute_kernel<C>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, st,
+        if constexpr (C::F::DEG == 1)
+            hipLaunchKernelGGL((msm_precompute_jac_kernel<C, typename C::F>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st,
                                table, (const uint8_t*)h->d_inf, n, i0, cnt, slab, c_row, W, zs, zp, bad);
-        }
+        else
+            hipLaunchKernelGGL((msm_precompute_jac_kernel<C, typename C::FC>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, st,
+                               table, (const uint8_t*)h->d_inf, n, i0, cnt, slab, c_row, W, zs, zp, bad);
         e = hipGetLastError();
     }
     uint32_t hbad = 0;
@@ -560,7 +527,7 @@ struct MsmJob {
         total = (size_t)sets * nb;                             // buckets that exist
         slots = (size_t)RW * Q;                                // bucket array incl. padding
         win_stride = nb;
-        static const int env_L1 = getenv("GH_REDUCE_L") ? atoi(getenv("GH_REDUCE_L")) : 0;
+        static const int env_L1 = env_int("GH_REDUCE_L", 0);
         // items per lane, level 1 (power of two).  The wave programs are latency chains (2 L1 + 17 steps,
         // then 2 L2 + 17): as long as the launch stays within one wave per SIMD (1024 on MI355X) a shorter
         // L1 only shortens the chain; beyond that the steps of co-resident waves add up again
@@ -585,7 +552,7 @@ struct MsmJob {
         // leaving the reduction out).  The chain is longer (level 2 then folds 64 x as many items per window: 6.5 + 8.3 ms inside
         // a batch at 2^20 against 8.8 + 3.0), so an MSM that runs alone and the last one of a batch keep the segment form, and
         // so do short accumulations the longer chain would not fit behind (2^18 pairs: 12.8 instead of 8.0 ms per MSM).
-        static const int env_lean = getenv("GH_REDUCE_LEAN") ? atoi(getenv("GH_REDUCE_LEAN")) : -1;
+        static const int env_lean = env_int("GH_REDUCE_LEAN", -1);
         lean = C::F::DEG == 1 && tpw == 64 && (env_lean >= 0 ? env_lean != 0 : (!solo && !last && (size_t)W * n >= ((size_t)1 << 25)));
         const uint32_t seg_slots = (uint32_t)tpw * (uint32_t)L1;
         segs_per_window = (Q + seg_slots - 1) / seg_slots;
@@ -601,7 +568,7 @@ struct MsmJob {
         // bound by its table gathers and every round pays an inversion per lane) and lose inside a pipelined batch
         // (30.4 vs 28.0 ms per MSM), so G1 stays projective unless asked.
         {
-            static const int env_aff = getenv("GH_AFFINE") ? atoi(getenv("GH_AFFINE")) : -1;
+            static const int env_aff = env_int("GH_AFFINE", -1);
             const int mode = env_aff >= 0 ? env_aff : g.affine_mode;
             tree = mode == 1 || (mode == 2 && C::F::DEG >= 2 && (size_t)W * n >= ((size_t)1 << 21));
         }
@@ -621,29 +588,25 @@ struct MsmJob {
         heavy_chunk = heavy_thr;                                    // chunk = a bucket of threshold size
         max_chunks = ((size_t)W * n) / heavy_chunk + max_heavy + 1;
         int rc;
-        char nm[48];
-#define POOL(name, ptr, bytes)                                      \
-    snprintf(nm, sizeof nm, "%s#%d", name, slot);                   \
-    if ((rc = pool_get(nm, bytes, (void**)&ptr))) return rc;
-        POOL("digits", digits, (size_t)W * n * 4)
-        POOL("counts", counts, total * 4)
-        POOL("starts", starts, total * 4)
-        POOL("cursor", cursor, total * 4)
-        POOL("sorted", sorted, (size_t)W * n * 4)
-        POOL("order", order, total * 4)
-        POOL("size_hist", size_hist, MSM_SIZE_BINS * 4)
-        POOL("size_cursor", size_cursor, MSM_SIZE_BINS * 4)
-        POOL("chunk_start", chunk_start, (max_heavy + 2) * 4)
-        POOL("plan", plan, 64)
-        POOL("buckets", buckets, slots * sizeof(Proj<C>))
-        POOL("seg_out", seg_out, (size_t)RW * segs_per_window * 3 * sizeof(Proj<C>))
-        POOL("win_out", win_out, (size_t)3 * RW * 3 * sizeof(Proj<C>))
+        if ((rc = slot_buf("digits", slot, (size_t)W * n * 4, &digits)) ||
+            (rc = slot_buf("counts", slot, total * 4, &counts)) ||
+            (rc = slot_buf("starts", slot, total * 4, &starts)) ||
+            (rc = slot_buf("cursor", slot, total * 4, &cursor)) ||
+            (rc = slot_buf("sorted", slot, (size_t)W * n * 4, &sorted)) ||
+            (rc = slot_buf("order", slot, total * 4, &order)) ||
+            (rc = slot_buf("size_hist", slot, MSM_SIZE_BINS * 4, &size_hist)) ||
+            (rc = slot_buf("size_cursor", slot, MSM_SIZE_BINS * 4, &size_cursor)) ||
+            (rc = slot_buf("chunk_start", slot, (max_heavy + 2) * 4, &chunk_start)) ||
+            (rc = slot_buf("plan", slot, 64, &plan)) ||
+            (rc = slot_buf("buckets", slot, slots * sizeof(Proj<C>), &buckets)) ||
+            (rc = slot_buf("seg_out", slot, (size_t)RW * segs_per_window * 3 * sizeof(Proj<C>), &seg_out)) ||
+            (rc = slot_buf("win_out", slot, (size_t)3 * RW * 3 * sizeof(Proj<C>), &win_out)))
+            return rc;
         // (also for the last MSM of a batch, which does not use it: a buffer that is first allocated in the middle of a later batch
         //  costs that batch a device-wide wait -- 9 ms at 2^20)
         if (lean || (C::F::DEG == 1 && tpw == 64 && !solo && (size_t)W * n >= ((size_t)1 << 25))) {
-            POOL("lane_out", lane_out, (size_t)RW * segs_per_window * 64 * 2 * sizeof(Proj<C>))
+            if ((rc = slot_buf("lane_out", slot, (size_t)RW * segs_per_window * 64 * 2 * sizeof(Proj<C>), &lane_out))) return rc;
         }
-#undef POOL
         if ((rc = pinned(es, 0, 512, (void**)&hplan))) return rc;
         if ((rc = pinned(es, 1, (size_t)9 * RW * sizeof(Proj<C>), (void**)&hw))) return rc;
         return GH_OK;
@@ -654,20 +617,17 @@ struct MsmJob {
         if (n == 0) return GH_OK;
         int rc;
         // keys a wave combines into one atomic each before falling back to per-lane atomics (wave_agg_inc)
-        static const int env_agg = getenv("GH_AGG_ITERS") ? atoi(getenv("GH_AGG_ITERS")) : -1;
+        static const int env_agg = env_int("GH_AGG_ITERS", -1);
         const int agg_iters = env_agg >= 0 ? env_agg : 12;
         HIPCHK(hipEventRecord(g.pev[es][0], st));
         HIPCHK(hipMemsetAsync(size_hist, 0, MSM_SIZE_BINS * 4, st));
         HIPCHK(hipMemsetAsync(plan, 0, 64, st));
         if (h->n_dup_groups) {     // the scalars of equal bases, added up (msm_kernels.h "equal bases"): the MSM sees the distinct bases only
-            char nm[48];
             uint32_t* merged_s = nullptr;
-            snprintf(nm, sizeof nm, "merged_scalars#%d", slot);
-            if ((rc = pool_get(nm, n * 96, (void**)&merged_s))) return rc;
+            if ((rc = slot_buf("merged_scalars", slot, n * 96, &merged_s))) return rc;
             HIPCHK(hipMemcpyAsync(merged_s, d_scalars, n * 96, hipMemcpyDeviceToDevice, st));
             uint32_t* partial = nullptr;
-            snprintf(nm, sizeof nm, "merged_partial#%d", slot);
-            if ((rc = pool_get(nm, (size_t)h->n_dup_chunks * 96 + 96, (void**)&partial))) return rc;
+            if ((rc = slot_buf("merged_partial", slot, (size_t)h->n_dup_chunks * 96 + 96, &partial))) return rc;
             GH_LAUNCH(msm_merge_scalars_kernel, dim3(h->n_dup_chunks), dim3(256), 0, st, (const uint32_t*)d_scalars, merged_s, n,
                       (const uint32_t*)h->d_dup_starts, (const uint32_t*)h->d_dup_members, (const uint32_t*)h->d_dup_chunks, h->n_dup_chunks,
                       partial, scalar_modulus<C>());
@@ -680,7 +640,6 @@ struct MsmJob {
         // scatter with device-scope atomics (fewer launches).  GH_SORT=atomic / part forces one of them where it applies.
         const size_t entries = (size_t)W * n;
         static const char* env_sort = getenv("GH_SORT");
-        static const bool sort_ordered = !(getenv("GH_SORT_ORDERED") && atoi(getenv("GH_SORT_ORDERED")) == 0);
         const uint32_t tile = entries > ((size_t)1 << 27) ? 65536u : 16384u;
         uint32_t bin_shift = 8;
         auto bins_at = [&](uint32_t sh) { return (total + ((size_t)1 << sh) - 1) >> sh; };
@@ -702,24 +661,19 @@ struct MsmJob {
             const size_t cells = (size_t)a.n_bins * a.n_blocks + 1;
             uint32_t *block_hist = nullptr, *block_off = nullptr;
             uint2* part = nullptr;
-            char nm[48];
-            snprintf(nm, sizeof nm, "part_hist#%d", slot);
-            if ((rc = pool_get(nm, cells * 4, (void**)&block_hist))) return rc;
-            snprintf(nm, sizeof nm, "part_off#%d", slot);
-            if ((rc = pool_get(nm, cells * 4, (void**)&block_off))) return rc;
-            snprintf(nm, sizeof nm, "part_pairs#%d", slot);
-            if ((rc = pool_get(nm, entries * 8, (void**)&part))) return rc;
+            if ((rc = slot_buf("part_hist", slot, cells * 4, &block_hist)) ||
+                (rc = slot_buf("part_off", slot, cells * 4, &block_off)) ||
+                (rc = slot_buf("part_pairs", slot, entries * 8, &part))) return rc;
             GH_LAUNCH(msm_digits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                                (const uint32_t*)d_scalars, (const uint8_t*)h->d_inf, n, c, W, win_stride, top_unsigned, scalar_modulus<C>(), digits,
                                (uint32_t*)nullptr, agg_iters, merged ? 1u : 0u, (uint32_t)sets);
             HIPCHK(hipMemsetAsync(block_hist + (cells - 1), 0, 4, st));
             GH_LAUNCH(msm_part_hist_kernel, dim3(a.n_blocks), dim3(MSM_PART_THREADS), 0, st, a, block_hist);
             HIPCHK(hipGetLastError());
-            snprintf(nm, sizeof nm, "scan_tmp3#%d", slot);
-            if ((rc = device_scan(block_hist, block_off, cells, nm, st))) return rc;
+            if ((rc = device_scan(block_hist, block_off, cells, slot_name("scan_tmp3", slot).c_str(), st))) return rc;
             GH_LAUNCH(msm_part_scatter_kernel, dim3(a.n_blocks), dim3(MSM_PART_THREADS), 0, st, a, (const uint32_t*)block_off, part);
             GH_LAUNCH(msm_bin_sort_kernel, dim3(a.n_bins), dim3(MSM_BIN_THREADS), (size_t)4 << bin_shift, st, (const uint2*)part,
-                               (const uint32_t*)block_off, a.n_blocks, bin_shift, (uint32_t)total, counts, starts, sorted, sort_ordered ? 1u : 0u);
+                               (const uint32_t*)block_off, a.n_blocks, bin_shift, (uint32_t)total, counts, starts, sorted);
             HIPCHK(hipGetLastError());
         } else {
             HIPCHK(hipMemsetAsync(counts, 0, total * 4, st));
@@ -755,11 +709,7 @@ struct MsmJob {
         if (n_heavy > max_heavy || n_chunks > max_chunks) { g_err = "internal: heavy-bucket plan out of range"; return GH_E_HIP; }
         const size_t lds_wave = 64 * sizeof(Proj<C>);
         partials = nullptr;
-        char nm[48];
-        snprintf(nm, sizeof nm, "partials#%d", slot);
-        if (n_heavy > 0 && (rc = pool_get(nm, (size_t)n_chunks * sizeof(Proj<C>), (void**)&partials))) return rc;
-        // 2 waves / SIMD (256 VGPRs, 184 B scratch) measured 29.3 ms vs 34.6 ms for 1 wave (297 registers) at 2^20
-        static const int acc_waves = getenv("GH_ACC_WAVES") ? atoi(getenv("GH_ACC_WAVES")) : 2;
+        if (n_heavy > 0 && (rc = slot_buf("partials", slot, (size_t)n_chunks * sizeof(Proj<C>), &partials))) return rc;
         const void* src_points = merged ? h->d_table : h->d_points;
         if (slots > total)   // padding slots of the last pseudo-window: infinity (Z = 0)
             HIPCHK(hipMemsetAsync((void*)(buckets + total), 0, (slots - total) * sizeof(Proj<C>), st));
@@ -768,61 +718,35 @@ struct MsmJob {
             if ((rc = launch_tree(st))) return rc;
         }
         if (!tree) {
-        {
             // one launch: the chunks of the heavy buckets first, then every other bucket, longest first
             const size_t tasks = (size_t)n_chunks + (total - n_heavy);
-            // G2: one coefficient per lane, 2 (Fq2) / 3 (Fq3) lanes per task (msm_kernels.h 4b)
-            constexpr bool is_g2 = std::is_same<C, Mnt4G2>::value || std::is_same<C, Mnt6G2>::value;
-            if constexpr (is_g2) {
-                {
-                    typedef typename std::conditional<std::is_same<C, Mnt4G2>::value, F2S<P4, 13, GH_F2S_DUAL != 0>, F3S<P6, 11, GH_F3S_TRIPLE>>::type FS;
-                    constexpr int LANES = FS::LANES;
-                    const size_t waves = (tasks + (64 / LANES) - 1) / (64 / LANES);
-                    GH_LAUNCH((msm_accumulate_split_kernel<C, FS, LANES>), dim3((unsigned)((waves * 64 + 255) / 256)), dim3(256), 0, st,
-                                       (const Aff<C>*)src_points, (const uint32_t*)sorted, (const uint32_t*)starts,
-                                       (const uint32_t*)counts, (const uint32_t*)order, (uint32_t)total, (const Aff<C>*)salts, buckets,
-                                       (const uint32_t*)chunk_start, n_heavy, n_chunks, heavy_chunk, partials);
-                }
-            }
-            // G1: XYZZ accumulators (msm_kernels.h 4a: 10 multiplications / 9 reductions per update); GH_ACC_XYZZ=0 selects the
-            // homogeneous-projective kernel (madd-1998-cmo, 11 / 11) for A/B measurements
-            static const bool acc_xyzz = !(getenv("GH_ACC_XYZZ") && atoi(getenv("GH_ACC_XYZZ")) == 0);
-            bool done_xyzz = false;
             if constexpr (C::F::DEG == 1) {
-                if (acc_xyzz && acc_waves >= 2 && gh_asm::enabled()) {
+                // G1: XYZZ accumulators (msm_kernels.h 4a: 10 multiplications / 9 reductions per update)
+                if (gh_asm::enabled()) {
                     // the assembly kernel (asmgen/g1_xyzz.py): the same updates on a fixed register plan, 0 B of scratch
                     gh_asm::AccTask* tk = nullptr;
-                    snprintf(nm, sizeof nm, "acc_tasks#%d", slot);
-                    if ((rc = pool_get(nm, tasks * sizeof(gh_asm::AccTask), (void**)&tk))) return rc;
+                    if ((rc = slot_buf("acc_tasks", slot, tasks * sizeof(gh_asm::AccTask), &tk))) return rc;
                     GH_LAUNCH((msm_acc_tasks_kernel<C>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st,
                                        (const uint32_t*)starts, (const uint32_t*)counts, (const uint32_t*)order, (uint32_t)total, buckets,
                                        (const uint32_t*)chunk_start, n_heavy, n_chunks, heavy_chunk, partials, (AccTaskRec*)tk);
                     if ((rc = gh_asm::acc_g1_launch(std::is_same<typename C::PF, P6>::value ? 6 : 4, src_points, (const uint32_t*)sorted, tk,
                                                     salts, (uint32_t)tasks, st))) return rc;
-                    done_xyzz = true;
-                } else if (acc_xyzz && acc_waves >= 2) {
+                } else {
                     GH_LAUNCH((msm_accumulate_xyzz_kernel<C>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st,
                                        (const Aff<C>*)src_points, (const uint32_t*)sorted, (const uint32_t*)starts,
                                        (const uint32_t*)counts, (const uint32_t*)order, (uint32_t)total, (const Aff<C>*)salts, buckets,
                                        (const uint32_t*)chunk_start, n_heavy, n_chunks, heavy_chunk, partials, 0u, 0u);
-                    done_xyzz = true;
                 }
+            } else {
+                // G2: one coefficient per lane, 2 (Fq2) / 3 (Fq3) lanes per task (msm_kernels.h 4b)
+                typedef typename std::conditional<C::F::DEG == 2, F2S<P4, 13>, F3S<P6, 11>>::type FS;
+                constexpr int LANES = FS::LANES;
+                const size_t waves = (tasks + (64 / LANES) - 1) / (64 / LANES);
+                GH_LAUNCH((msm_accumulate_split_kernel<C, FS, LANES>), dim3((unsigned)((waves * 64 + 255) / 256)), dim3(256), 0, st,
+                                   (const Aff<C>*)src_points, (const uint32_t*)sorted, (const uint32_t*)starts,
+                                   (const uint32_t*)counts, (const uint32_t*)order, (uint32_t)total, (const Aff<C>*)salts, buckets,
+                                   (const uint32_t*)chunk_start, n_heavy, n_chunks, heavy_chunk, partials);
             }
-            if constexpr (!is_g2) {      // (the one-lane G2 instances, 4-8 KB of stack per lane, are no longer built: G2 is always split)
-            if (!done_xyzz) {
-                if (acc_waves >= 2)
-                    GH_LAUNCH((msm_accumulate_kernel<C, 2>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st,
-                                       (const Aff<C>*)src_points, (const uint32_t*)sorted, (const uint32_t*)starts,
-                                       (const uint32_t*)counts, (const uint32_t*)order, (uint32_t)total, (const Aff<C>*)salts, buckets,
-                                       (const uint32_t*)chunk_start, n_heavy, n_chunks, heavy_chunk, partials);
-                else
-                    GH_LAUNCH((msm_accumulate_kernel<C, 1>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st,
-                                       (const Aff<C>*)src_points, (const uint32_t*)sorted, (const uint32_t*)starts,
-                                       (const uint32_t*)counts, (const uint32_t*)order, (uint32_t)total, (const Aff<C>*)salts, buckets,
-                                       (const uint32_t*)chunk_start, n_heavy, n_chunks, heavy_chunk, partials);
-            }
-            }
-        }
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(g.pev[es][3], st));
@@ -841,7 +765,7 @@ struct MsmJob {
     // the single-reduction triple product (Fq3: six product sites per addition, where the projective kernel's eleven did
     // not get through hipcc unrolled)
     typedef typename std::conditional<C::F::DEG == 1, F1S<typename C::PF>,
-            typename std::conditional<C::F::DEG == 2, F2S<P4, 13, GH_AFF_F2S_DUAL != 0>, F3S<P6, 11, GH_AFF_F3S_TRIPLE>>::type>::type TreeFS;
+            typename std::conditional<C::F::DEG == 2, F2S<P4, 13>, F3S<P6, 11>>::type>::type TreeFS;
 
     int launch_tree(hipStream_t st) {
         typedef TreeFS FS;
@@ -849,14 +773,14 @@ struct MsmJob {
         constexpr uint32_t TPW = 64 / LANES;
         int rc;
         const uint32_t n0 = hplan[2], maxc = hplan[4];
-        static const int env_R = getenv("GH_AFF_ROUNDS") ? atoi(getenv("GH_AFF_ROUNDS")) : 0;
-        static const int env_bmin = getenv("GH_AFF_BMIN") ? atoi(getenv("GH_AFF_BMIN")) : 8;
-        static const int env_fin = getenv("GH_AFF_FINISH_MAX") ? atoi(getenv("GH_AFF_FINISH_MAX")) : 64;
+        static const int env_R = env_int("GH_AFF_ROUNDS", 0);
+        static const int env_bmin = env_int("GH_AFF_BMIN", 8);
+        static const int env_fin = env_int("GH_AFF_FINISH_MAX", 64);
         // rounds: down to ~env_left points per bucket on average (the late rounds are short batches -- one inversion per
         // lane and round -- while the projective finish is dense work), and no bucket left with more than env_fin points
         // (round 3, profiles/r03_g2_knobs.txt: on the towers the projective finish costs 11 tower products per point against the rounds' 6,
         //  so fewer points are left to it: Fq3 1.5 (MNT6 G2 2^19: 5.75 -> 5.95 M/s together with the one-chunk scratch budget), Fq2 2.5)
-        static const double env_left = getenv("GH_AFF_LEFTOVER") ? atof(getenv("GH_AFF_LEFTOVER")) : (C::F::DEG == 3 ? 1.5 : (C::F::DEG == 2 ? 2.5 : 4.5));
+        static const double env_left = env_double("GH_AFF_LEFTOVER", C::F::DEG == 3 ? 1.5 : (C::F::DEG == 2 ? 2.5 : 4.5));
         int R = 1;
         {
             const double mean = (double)n0 / (double)(total > 1 ? total - 1 : 1);
@@ -866,44 +790,40 @@ struct MsmJob {
         }
         tree_rounds = R;
         const size_t stride = (total + 63) & ~(size_t)63;
-        char nm[48];
-#define POOLT(name, ptr, bytes)                                     \
-    snprintf(nm, sizeof nm, "%s#%d", name, slot);                   \
-    if ((rc = pool_get(nm, bytes, (void**)&ptr))) return rc;
-        POOLT("aff_cnt", aff_cnt, (size_t)R * stride * 4)
-        POOLT("aff_st", aff_st, (size_t)R * stride * 4)
+        if ((rc = slot_buf("aff_cnt", slot, (size_t)R * stride * 4, &aff_cnt)) ||
+            (rc = slot_buf("aff_st", slot, (size_t)R * stride * 4, &aff_st))) return rc;
         GH_LAUNCH(aff_counts_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                            (const uint32_t*)counts, (uint32_t)total, R, stride, aff_cnt);
-        snprintf(nm, sizeof nm, "aff_scan#%d", slot);
+        const std::string scan_nm = slot_name("aff_scan", slot);
         for (int r = 1; r <= R; r++)
-            if ((rc = device_scan(aff_cnt + (size_t)(r - 1) * stride, aff_st + (size_t)(r - 1) * stride, total, nm, st))) return rc;
+            if ((rc = device_scan(aff_cnt + (size_t)(r - 1) * stride, aff_st + (size_t)(r - 1) * stride, total, scan_nm.c_str(), st))) return rc;
         // Chunks of buckets: the scratch lists of the rounds are sized per chunk, so that a 2^24-pair key (or a G2 key with
         // its shift table) does not need 300 GB of them.  ~420 bytes x lanes per list entry: the staged inputs, the two
         // output lists, the running products and the descriptors of a chunk.
         // (default 64 GB since round 3: a 2^20-pair G2 MSM then runs as ONE chunk -- 14.0 -> 14.4 M/s on MNT4 G2; the budget is cut to what
         //  is free next to the key anyway)
-        static const double env_scratch_gb = getenv("GH_AFF_SCRATCH_GB") ? atof(getenv("GH_AFF_SCRATCH_GB")) : 64.0;
+        static const double env_scratch_gb = env_double("GH_AFF_SCRATCH_GB", 64.0);
         uint32_t K = 1;
         {
             size_t free_b = 0, total_b = 0;
             HIPCHK(hipMemGetInfo(&free_b, &total_b));
             size_t have = 0;
             const char* names[6] = {"aff_desc", "aff_ptsA", "aff_ptsB", "aff_prefix", "aff_stage1", "aff_stage2"};
-            for (int i = 0; i < 6; i++) { snprintf(nm, sizeof nm, "%s#%d", names[i], slot); have += pool_cap(nm); }
+            for (const char* nm : names) have += pool_cap(slot_name(nm, slot).c_str());
             double budget = env_scratch_gb * 1073741824.0;
             const double avail = ((double)free_b + (double)have - 3.0 * 1073741824.0) * 0.9;     // what this slot may hold at most
             if (budget > avail) budget = avail;
             const double need = 430.0 * LANES * (double)n0 * 1.13;                                // incl. the pool's 1/8 slack
             if (budget < 256.0 * 1048576.0) {       // no room at all: the projective kernel runs
-                for (int i = 0; i < 6; i++) { snprintf(nm, sizeof nm, "%s#%d", names[i], slot); pool_release(nm); }
+                for (const char* nm : names) pool_release(slot_name(nm, slot).c_str());
                 tree = false;
                 return GH_OK;
             }
             while ((double)K * budget < need && K < 4096) K++;
         }
         uint32_t *d_bq, *d_tab;
-        POOLT("aff_bq", d_bq, ((size_t)K + 2) * 4)
-        POOLT("aff_tab", d_tab, ((size_t)K + 2) * (R + 1) * 4)
+        if ((rc = slot_buf("aff_bq", slot, ((size_t)K + 2) * 4, &d_bq)) ||
+            (rc = slot_buf("aff_tab", slot, ((size_t)K + 2) * (R + 1) * 4, &d_tab))) return rc;
         GH_LAUNCH(aff_chunks_kernel, dim3((K + 1 + 63) / 64), dim3(64), 0, st, (const uint32_t*)starts, (const uint32_t*)counts,
                            (const uint32_t*)aff_st, (const uint32_t*)aff_cnt, (uint32_t)total, R, stride, K, d_bq, d_tab);
         HIPCHK(hipGetLastError());
@@ -927,36 +847,29 @@ struct MsmJob {
         uint32_t* desc;
         void *ptsA, *ptsB, *prefix, *stage1, *stage2;     // T64 lists (aff_kernels.h)
         auto tiles = [&](uint32_t n_el) { return ((size_t)n_el + TPW - 1) / TPW + 1; };
-#undef POOLT
-#define POOLBIG(name, ptr, bytes)                                   \
-    snprintf(nm, sizeof nm, "%s#%d", name, slot);                   \
-    rc = pool_get(nm, bytes, (void**)&ptr);                         \
-    if (rc == GH_E_NOMEM) { (void)hipGetLastError(); tree = false; return GH_OK; } \
-    if (rc) return rc;
-        POOLBIG("aff_desc", desc, (max_desc + 64) * 4)
-        POOLBIG("aff_ptsA", ptsA, t64_bytes(tiles(max_n1), T64_PT_CHUNKS))
-        POOLBIG("aff_ptsB", ptsB, t64_bytes(tiles(max_n2), T64_PT_CHUNKS))
-        POOLBIG("aff_prefix", prefix, t64_bytes(tiles(max_n1), T64_FP_CHUNKS))
-        POOLBIG("aff_stage1", stage1, t64_bytes(tiles(max_n1), T64_PT_CHUNKS))
-        POOLBIG("aff_stage2", stage2, t64_bytes(tiles(max_n1), T64_PT_CHUNKS))
-#undef POOLBIG
+        if ((rc = slot_buf("aff_desc", slot, (max_desc + 64) * 4, &desc)) ||
+            (rc = slot_buf("aff_ptsA", slot, t64_bytes(tiles(max_n1), T64_PT_CHUNKS), &ptsA)) ||
+            (rc = slot_buf("aff_ptsB", slot, t64_bytes(tiles(max_n2), T64_PT_CHUNKS), &ptsB)) ||
+            (rc = slot_buf("aff_prefix", slot, t64_bytes(tiles(max_n1), T64_FP_CHUNKS), &prefix)) ||
+            (rc = slot_buf("aff_stage1", slot, t64_bytes(tiles(max_n1), T64_PT_CHUNKS), &stage1)) ||
+            (rc = slot_buf("aff_stage2", slot, t64_bytes(tiles(max_n1), T64_PT_CHUNKS), &stage2))) {
+            if (rc != GH_E_NOMEM) return rc;
+            (void)hipGetLastError();         // the lists do not fit: the projective kernel runs
+            tree = false;
+            return GH_OK;
+        }
         const uint32_t max_waves = (uint32_t)g.num_cus * 4u * (uint32_t)FS::WAVES;
         const bool aff_asm = (C::F::DEG >= 2 ? gh_asm::aff_enabled() : gh_asm::aff_g1_enabled()) && !h->aff_asm_off;
         const int asm_kind = std::is_same<C, Mnt4G2>::value ? 0 : (std::is_same<C, Mnt6G2>::value ? 1 : (std::is_same<C, Mnt6G1>::value ? 3 : 2));
-        // the assembly kernels run two waves per SIMD; GH_AFF_WAVES_MUL x that many waves are launched so that the blocks (equal
-        // work each) are dealt out dynamically instead of as one exact fill of the chip
-        static const int env_wmul = getenv("GH_AFF_WAVES_MUL") ? atoi(getenv("GH_AFF_WAVES_MUL")) : 1;
-        const uint32_t asm_max_waves = (uint32_t)g.num_cus * 4u * 2u * (uint32_t)(env_wmul > 0 && env_wmul <= 16 ? env_wmul : 1);
+        const uint32_t asm_max_waves = (uint32_t)g.num_cus * 4u * 2u;     // the assembly kernels run two waves per SIMD
         void* asm_accs = nullptr;
         uint32_t* asm_flag = nullptr;
         // Two copies of the per-round control data: a large round is issued as two halves (below)
         const size_t accs_half = t64_bytes((size_t)asm_max_waves + 4, T64_FP_CHUNKS);
         const size_t flag_words = 16 + (size_t)AFF_FIX_CAP;
         if (aff_asm) {
-            snprintf(nm, sizeof nm, "aff_accs#%d", slot);
-            if ((rc = pool_get(nm, 2 * accs_half, &asm_accs))) return rc;
-            snprintf(nm, sizeof nm, "aff_flag#%d", slot);
-            if ((rc = pool_get(nm, 2 * 4 * flag_words, (void**)&asm_flag))) return rc;   // control block + exception list, per half
+            if ((rc = slot_buf("aff_accs", slot, 2 * accs_half, &asm_accs))) return rc;
+            if ((rc = slot_buf("aff_flag", slot, 2 * 4 * flag_words, &asm_flag))) return rc;   // control block + exception list, per half
             HIPCHK(hipMemsetAsync(asm_flag, 0, 64, st));                    // word 4: "a round of this MSM was redone" (sticky)
             HIPCHK(hipMemsetAsync(asm_flag + flag_words, 0, 64, st));
         }
@@ -964,8 +877,8 @@ struct MsmJob {
         // 0.4 ms of latency with the card nearly idle.  A large round therefore goes out as two halves of its output range on two
         // streams, the second half one kernel behind the first: the inversion of either half runs beside a forward / backward
         // kernel of the other (GH_AFF_SPLIT=0: one piece; halves are whole tiles, so every list keeps its layout).
-        static const int env_split = getenv("GH_AFF_SPLIT") ? atoi(getenv("GH_AFF_SPLIT")) : 1;
-        static const int env_split_b = getenv("GH_AFF_SPLIT_B") ? atoi(getenv("GH_AFF_SPLIT_B")) : 32;   // smallest batch per lane group worth splitting
+        static const int env_split = env_int("GH_AFF_SPLIT", 1);
+        static const int env_split_b = env_int("GH_AFF_SPLIT_B", 32);   // smallest batch per lane group worth splitting
         const Aff<C>* rows = (const Aff<C>*)(merged ? h->d_table : h->d_points);
         // one piece of a round: outputs [o0, o0 + n_piece) (o0 a multiple of the tile size); which: 0 / 1 = control block, stream role
         struct Piece {
@@ -1089,9 +1002,8 @@ struct MsmJob {
                                    (const uint32_t*)nullptr, stR, mR, (const uint32_t*)nullptr, nbk, (const Aff<C>*)salts, buckets,
                                    (const uint32_t*)nullptr, 0u, 0u, heavy_chunk, (Proj<C>*)nullptr, bq[j], T(j, R));
             } else {
-                typedef typename std::conditional<C::F::DEG == 2, F2S<P4, 13, GH_F2S_DUAL != 0>, F3S<P6, 11, GH_F3S_TRIPLE>>::type FA;
                 const size_t fwaves = ((size_t)nbk + TPW - 1) / TPW;
-                GH_LAUNCH((msm_accumulate_split_kernel<C, FA, LANES, true>), dim3((unsigned)((fwaves * 64 + 255) / 256)), dim3(256), 0, st,
+                GH_LAUNCH((msm_accumulate_split_kernel<C, FS, LANES, true>), dim3((unsigned)((fwaves * 64 + 255) / 256)), dim3(256), 0, st,
                                    (const Aff<C>*)in, (const uint32_t*)nullptr, stR, mR, (const uint32_t*)nullptr, nbk, (const Aff<C>*)salts, buckets,
                                    (const uint32_t*)nullptr, 0u, 0u, heavy_chunk, (Proj<C>*)nullptr, bq[j], T(j, R));
             }
@@ -1112,44 +1024,27 @@ struct MsmJob {
         const size_t lds_wave = 64 * sizeof(Proj<C>);
         // level 1: one wave per segment of 64 * L1 bucket slots -> (runW, A, Bv) per segment
         WaveReduceIn<C> i0{buckets, 1, 0, Q, 0, (uint32_t)total}, none{nullptr, 0, 0, 0, 0, 0};
-        static const int env_wpb = getenv("GH_REDUCE_WPB") ? atoi(getenv("GH_REDUCE_WPB")) : 1;
-        int wpb = env_wpb >= 1 && (size_t)env_wpb * lds_wave <= 65536 && env_wpb <= 4 ? env_wpb : 1;   // waves per block
         const unsigned nb1 = (unsigned)(RW * segs_per_window), nb2 = (unsigned)(3 * RW);
         const uint32_t all = 0xFFFFFFFFu;
         // level 2: one wave per window and per array: weighted program on runW, plain sums of A and Bv
         WaveReduceIn<C> r0{seg_out, 3, 0, segs_per_window, 0, all}, r1{seg_out, 3, 1, segs_per_window, 1, all}, r2{seg_out, 3, 2, segs_per_window, 1, all};
-        bool launched = false;
+        // the programs' accumulators live in a slab of global memory each (msm_kernels.h, ReduceSlab / P3Slab)
+        uint32_t* slabs = nullptr;
+        const size_t progs = nb1 > nb2 ? nb1 : nb2;
         if constexpr (C::F::DEG >= 2) {
-            if (tpw != 64) {
-                typedef typename std::conditional<C::F::DEG == 2, F2S<P4, 13>, F3S<P6, 11, GH_F3S_TRIPLE>>::type FS;
-                constexpr int LANES = FS::LANES, TPW = C::F::DEG == 2 ? 32 : 16;
-                const size_t lds_split = 64 * sizeof(P3);
-                uint32_t* slabs = nullptr;
-                char nm[48];
-                snprintf(nm, sizeof nm, "reduce_slabs#%d", slot);
-                int rc = pool_get(nm, (size_t)(nb1 > nb2 ? nb1 : nb2) * P3Slab::WORDS * 4, (void**)&slabs);
-                if (rc) return rc;
-                GH_LAUNCH((msm_wave_reduce_split_kernel<C, FS, LANES, TPW>), dim3(nb1), dim3(64), lds_split, st,
-                                   i0, none, none, nb1, 1u, segs_per_window, L1, (const Aff<C>*)salts, seg_out, slabs);
-                GH_LAUNCH((msm_wave_reduce_split_kernel<C, FS, LANES, TPW>), dim3(nb2), dim3(64), lds_split, st,
-                                   r0, r1, r2, (uint32_t)RW, 3u, 1u, L2, (const Aff<C>*)salts, win_out, slabs);
-                launched = true;
-            }
-        }
-        if constexpr (C::F::DEG == 1) {
-        if (!launched) {
-            // the programs' accumulators live in a slab of global memory each (msm_kernels.h, ReduceSlab)
-            uint32_t* slabs = nullptr;
-            {
-                char nm[48];
-                snprintf(nm, sizeof nm, "reduce_slabs#%d", slot);
-                const size_t progs = nb1 > nb2 ? nb1 : nb2;
-                int rc = pool_get(nm, progs * ReduceSlab<C>::WORDS * 4, (void**)&slabs);
-                if (rc) return rc;
-            }
+            typedef typename std::conditional<C::F::DEG == 2, F2S<P4, 13>, F3S<P6, 11>>::type FS;
+            constexpr int LANES = FS::LANES, TPW = C::F::DEG == 2 ? 32 : 16;
+            const size_t lds_split = 64 * sizeof(P3);
+            if (int rc = slot_buf("reduce_slabs", slot, progs * P3Slab::WORDS * 4, &slabs)) return rc;
+            GH_LAUNCH((msm_wave_reduce_split_kernel<C, FS, LANES, TPW>), dim3(nb1), dim3(64), lds_split, st,
+                               i0, none, none, nb1, 1u, segs_per_window, L1, (const Aff<C>*)salts, seg_out, slabs);
+            GH_LAUNCH((msm_wave_reduce_split_kernel<C, FS, LANES, TPW>), dim3(nb2), dim3(64), lds_split, st,
+                               r0, r1, r2, (uint32_t)RW, 3u, 1u, L2, (const Aff<C>*)salts, win_out, slabs);
+        } else {
+            if (int rc = slot_buf("reduce_slabs", slot, progs * ReduceSlab<C>::WORDS * 4, &slabs)) return rc;
             // A stand-alone MSM has the chip to itself: the 512-register build of the program (one wave per SIMD, 88 B of spills
             // per lane instead of 680) -- inside a batch the reduction must fit beside the accumulation's waves (256 registers).
-            static const int env_w = getenv("GH_REDUCE_WAVES") ? atoi(getenv("GH_REDUCE_WAVES")) : 0;
+            static const int env_w = env_int("GH_REDUCE_WAVES", 0);
             const bool one_wave = env_w ? env_w == 1 : solo;
             if (lean) {
                 // level 1: serial part only, (run, wacc) per lane; level 2 per window: the weighted program over the lanes' run (item =
@@ -1159,28 +1054,27 @@ struct MsmJob {
                 WaveReduceIn<C> l0{lane_out, 2, 0, lanes_per_window, 0, all}, l1{lane_out, 2, 1, lanes_per_window, 1, all};
                 const unsigned nb2l = (unsigned)(2 * RW);
                 if (one_wave) {
-                    GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3((nb1 + wpb - 1) / wpb), dim3(64 * wpb), lds_wave * wpb, st,
+                    GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3(nb1), dim3(64), lds_wave, st,
                                        i0l, none, none, nb1, 1u, segs_per_window, L1, (const Aff<C>*)salts, lane_out, slabs);
-                    GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3((nb2l + wpb - 1) / wpb), dim3(64 * wpb), lds_wave * wpb, st,
+                    GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3(nb2l), dim3(64), lds_wave, st,
                                        l0, l1, none, (uint32_t)RW, 2u, 1u, (int)segs_per_window, (const Aff<C>*)salts, win_out, slabs);
                 } else {
-                    GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3((nb1 + wpb - 1) / wpb), dim3(64 * wpb), lds_wave * wpb, st,
+                    GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3(nb1), dim3(64), lds_wave, st,
                                        i0l, none, none, nb1, 1u, segs_per_window, L1, (const Aff<C>*)salts, lane_out, slabs);
-                    GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3((nb2l + wpb - 1) / wpb), dim3(64 * wpb), lds_wave * wpb, st,
+                    GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3(nb2l), dim3(64), lds_wave, st,
                                        l0, l1, none, (uint32_t)RW, 2u, 1u, (int)segs_per_window, (const Aff<C>*)salts, win_out, slabs);
                 }
             } else if (one_wave) {
-                GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3((nb1 + wpb - 1) / wpb), dim3(64 * wpb), lds_wave * wpb, st,
+                GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3(nb1), dim3(64), lds_wave, st,
                                    i0, none, none, nb1, 1u, segs_per_window, L1, (const Aff<C>*)salts, seg_out, slabs);
-                GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3((nb2 + wpb - 1) / wpb), dim3(64 * wpb), lds_wave * wpb, st,
+                GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3(nb2), dim3(64), lds_wave, st,
                                    r0, r1, r2, (uint32_t)RW, 3u, 1u, L2, (const Aff<C>*)salts, win_out, slabs);
             } else {
-                GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3((nb1 + wpb - 1) / wpb), dim3(64 * wpb), lds_wave * wpb, st,
+                GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3(nb1), dim3(64), lds_wave, st,
                                    i0, none, none, nb1, 1u, segs_per_window, L1, (const Aff<C>*)salts, seg_out, slabs);
-                GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3((nb2 + wpb - 1) / wpb), dim3(64 * wpb), lds_wave * wpb, st,
+                GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3(nb2), dim3(64), lds_wave, st,
                                    r0, r1, r2, (uint32_t)RW, 3u, 1u, L2, (const Aff<C>*)salts, win_out, slabs);
             }
-        }
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(g.pev[es][5], st));
@@ -1264,7 +1158,7 @@ int accumulate_lists(const void* points, const uint32_t* sorted, const uint32_t*
                            (const uint32_t*)nullptr, 0u, 0u, 0u, (Proj<C>*)nullptr, 0u, 0u);
       }
     } else {
-        typedef typename std::conditional<std::is_same<C, Mnt4G2>::value, F2S<P4, 13, GH_F2S_DUAL != 0>, F3S<P6, 11, GH_F3S_TRIPLE>>::type FS;
+        typedef typename std::conditional<C::F::DEG == 2, F2S<P4, 13>, F3S<P6, 11>>::type FS;
         constexpr int LANES = FS::LANES;
         const size_t waves = ((size_t)total + (64 / LANES) - 1) / (64 / LANES);
         GH_LAUNCH((msm_accumulate_split_kernel<C, FS, LANES>), dim3((unsigned)((waves * 64 + 255) / 256)), dim3(256), 0, st,

@@ -11,9 +11,11 @@
 //   2. exclusive scan of the histogram (msm_scan_*), bucket order by descending size
 //      (msm_size_*: counting sort on the bucket size so the 64 lanes of a wave get equal work).
 //   3. msm_scatter_kernel    counting-sort scatter: for every bucket the list of (pair index | sign).
-//   4. msm_accumulate_kernel one thread per bucket walks its list: gather the base (internal
-//                            layout, 208 B for G1), conditional negate, projective mixed add
-//                            (ec29.h proj_madd, 11 Fp-mul).  ~94 % of all work (as in the reference).
+//   4. msm_accumulate_xyzz_kernel  one thread per bucket walks its list: gather the base (internal
+//                            layout, 208 B for G1), conditional negate, mixed add into XYZZ accumulators
+//                            (madd-2008-s, 8 M + 2 S; its assembly build on G1 by default).  G2: one bucket per
+//                            lane pair / triple (msm_accumulate_split_kernel) or the affine rounds (aff_kernels.h).
+//                            ~94 % of all work (as in the reference).
 //      chunk mode + msm_heavy_combine_kernel: buckets longer than the heavy threshold are cut into
 //                            chunks that the same kernel sums like ordinary buckets, then combined
 //                            (skewed real-world witnesses -- many equal small scalars -- and
@@ -178,47 +180,10 @@ template <class T> __device__ __forceinline__ void st_words(T* p, const T& v) {
 // this launch covers bases [i0, i0 + cnt).  zs / zp: (W - 1) x slab field elements of scratch
 // (Z_w and the running products Z_1 .. Z_w).  bad[0] is set when a doubling chain reaches infinity
 // (a base of 2-power order: the caller then keeps the plain per-window path for this key).
-template <class C>
-__global__ void __launch_bounds__(64)
-msm_precompute_kernel(Aff<C>* __restrict__ table, const uint8_t* __restrict__ infinity, size_t n, size_t i0, size_t cnt,
-                      size_t slab, int c, int W, typename C::FC::T* __restrict__ zs, typename C::FC::T* __restrict__ zp,
-                      uint32_t* __restrict__ bad) {
-    typedef typename C::FC F;
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= cnt) return;
-    const size_t i = i0 + t;
-    if (infinity != nullptr && infinity[i] != 0) {   // never read (its digits are dropped); keep the rows defined
-        const Aff<C> b = ld_words(table + i);
-        for (int w = 1; w < W; w++) st_words(table + (size_t)w * n + i, b);
-        return;
-    }
-    const Aff<C> b = ld_words(table + i);
-    Proj<C> p{b.x, b.y, F::one()};
-    typename F::T run = F::one();
-    for (int w = 1; w < W; w++) {
-        for (int d = 0; d < c; d++) p = proj_dbl_call<C>(p);
-        if (F::is_zero(p.z)) { atomicOr(bad, 1u); return; }
-        st_words(table + (size_t)w * n + i, Aff<C>{p.x, p.y});
-        st_words(zs + (size_t)(w - 1) * slab + t, p.z);
-        run = F::mul(run, p.z);
-        st_words(zp + (size_t)(w - 1) * slab + t, run);
-    }
-    typename F::T inv = DevInv<F>::inv(run);   // 1 / (Z_1 ... Z_(W-1))
-    for (int w = W - 1; w >= 1; w--) {
-        typename F::T zi = inv;
-        if (w > 1) zi = F::mul(inv, ld_words(zp + (size_t)(w - 2) * slab + t));   // 1 / Z_w
-        inv = F::mul(inv, ld_words(zs + (size_t)(w - 1) * slab + t));
-        Aff<C> q = ld_words(table + (size_t)w * n + i);
-        q.x = F::mul(q.x, zi);
-        q.y = F::mul(q.y, zi);
-        st_words(table + (size_t)w * n + i, q);
-    }
-}
-
-// The same table with the doublings in JACOBIAN coordinates (round 3): dbl-2007-bl is 1 M + 8 S + a ZZ^2 against the 5 M + 6 S of
-// the homogeneous doubling above; for the prime-field curves (G1) the products are inlined as well, where the kernel above
-// calls them out of line -- 2^20 G1 bases, c = 21: 0.85 -> 0.40 s.  Row w holds (X, Y) of 2^(c w) P until the backward
-// sweep turns them into x = X / Z^2, y = Y / Z^3 with ONE inversion per base over the row Z's (Montgomery's trick, as above).
+// The doublings run in JACOBIAN coordinates (round 3): dbl-2007-bl is 1 M + 8 S + a ZZ^2 against the 5 M + 6 S of the
+// homogeneous doubling; for the prime-field curves (G1) the products are inlined as well, where the homogeneous round-1/2 kernel
+// called them out of line -- 2^20 G1 bases, c = 21: 0.85 -> 0.40 s.  Row w holds (X, Y) of 2^(c w) P until the backward
+// sweep turns them into x = X / Z^2, y = Y / Z^3 with ONE inversion per base over the row Z's (Montgomery's trick).
 template <class C, class F>
 __global__ void __launch_bounds__(F::DEG == 1 ? 256 : 64)
 msm_precompute_jac_kernel(Aff<C>* __restrict__ table, const uint8_t* __restrict__ infinity, size_t n, size_t i0, size_t cnt,
@@ -586,7 +551,7 @@ constexpr int MSM_BIN_UNROLL = 8;
 static __global__ void __launch_bounds__(MSM_BIN_THREADS) msm_bin_sort_kernel(const uint2* __restrict__ part, const uint32_t* __restrict__ block_off,
                                                                              uint32_t n_blocks, uint32_t bin_shift, uint32_t total,
                                                                              uint32_t* __restrict__ counts, uint32_t* __restrict__ starts,
-                                                                             uint32_t* __restrict__ sorted, uint32_t ordered) {
+                                                                             uint32_t* __restrict__ sorted) {
     extern __shared__ uint32_t cnt[];                 // 2^bin_shift
     __shared__ uint32_t wsum[MSM_BIN_THREADS / 64];
     const uint32_t bin = blockIdx.x, size = 1u << bin_shift, b0 = bin << bin_shift;
@@ -633,7 +598,7 @@ static __global__ void __launch_bounds__(MSM_BIN_THREADS) msm_bin_sort_kernel(co
     // each bucket's list comes out ordered by window (merged buckets) / by base index (per-window buckets).  The accumulation
     // walks its lists in step, so ordered lists keep the gathers of the waves in flight closer together: 1-2 % on the
     // accumulation and on the pipelined batch at 2^20 .. 2^24, and the sweep itself is no slower with the barriers
-    // (profiles/r03_sort_order_ab.txt, GH_SORT_ORDERED=0 = without them).  The loads of eight steps are issued together.
+    // (profiles/r03_sort_order_ab.txt).  The loads of eight steps are issued together.
     for (uint32_t base = lo; base < hi; base += MSM_BIN_THREADS * MSM_BIN_UNROLL) {      // uniform trip count: barriers inside
         uint2 pv[MSM_BIN_UNROLL];
 #pragma unroll
@@ -644,7 +609,7 @@ static __global__ void __launch_bounds__(MSM_BIN_THREADS) msm_bin_sort_kernel(co
 #pragma unroll
         for (int u = 0; u < MSM_BIN_UNROLL; u++) {
             if (pv[u].x != 0xFFFFFFFFu) sorted[atomicAdd(&cnt[pv[u].x - b0], 1u)] = pv[u].y;
-            if (ordered) __syncthreads();       // (GH_SORT_ORDERED=0: the A/B switch)
+            __syncthreads();
         }
     }
 }
@@ -721,159 +686,20 @@ msm_scatter_kernel(const int32_t* __restrict__ digits, size_t n, int num_windows
 }
 
 // ---------------------------------------------------------------- 4. bucket accumulation
-// order[] lists bucket ids by descending size: [0, n_heavy) are heavy (msm_heavy_*_kernel),
-// the rest is walked here one bucket per thread; empty buckets store infinity.
+// order[] lists bucket ids by descending size: [0, n_heavy) are heavy (msm_heavy_*_kernel), whose lists are cut into
+// chunks; the task list is [0, n_chunks) chunks of the heavy buckets (the longest tasks, scheduled first), then the buckets
+// order[n_heavy ..], one task per thread (G1) or lane group (G2, 4b); empty buckets store infinity.
 //
-// The loop body holds exactly ONE mixed addition and no function call, so the kernel's register
-// budget is its own.  The reference's `P == Q -> double` branch (swp.rs:492-495) is reached when a
-// bucket's running sum equals the incoming base (duplicate bases); instead of a doubling formula
-// the thread then takes a three-step detour through a fixed "salt" point S (S = G or 2G, whichever
-// has x != q.x, so q != +-S):  acc <- ((q + S) + q) - S = 2q, each step a generic mixed addition.
-// P + (-P) needs no branch: the formula yields Z = 0 and the next addition restarts from infinity.
+// The reference's `P == Q -> double` branch (swp.rs:492-495) is reached when a bucket's running sum equals the incoming
+// base (duplicate bases); instead of a doubling formula the thread then takes a three-step detour through a fixed "salt"
+// point S (S = G or 2G, whichever has x != q.x, so q != +-S):  acc <- ((q + S) + q) - S = 2q, each step a generic mixed
+// addition.  P + (-P) needs no branch: the formula yields Z = 0 and the next addition restarts from infinity.
 //
-// WAVES = minimum waves per SIMD the register allocation must allow (1: up to 512 VGPR+AGPR,
-// 2: up to 256); selected at run time (GH_ACC_WAVES) for A/B measurements.
-// AFFIN = true: the input is the output list of the affine rounds (aff_kernels.h): bucket g owns the records
-// [starts[g], starts[g] + counts[g]) of `bases` directly (no index list, no signs) and infinity markers are skipped.
-template <class C, int WAVES, bool AFFIN = false>
-__global__ void __launch_bounds__(256, WAVES)
-msm_accumulate_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __restrict__ sorted,
-                      const uint32_t* __restrict__ starts, const uint32_t* __restrict__ counts,
-                      const uint32_t* __restrict__ order, uint32_t total,
-                      const Aff<C>* __restrict__ salts, Proj<C>* __restrict__ buckets,
-                      const uint32_t* __restrict__ chunk_start, uint32_t n_heavy, uint32_t n_chunks, uint32_t chunk,
-                      Proj<C>* __restrict__ partials, uint32_t g_first = 0, uint32_t list_base = 0) {
-    typedef typename C::F F;
-    // task list: [0, n_chunks) chunks of the heavy buckets (the longest tasks, scheduled first),
-    //            then the buckets order[n_heavy ..] by descending size
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_chunks + (total - n_heavy)) return;
-    uint32_t beg, cnt;
-    Proj<C>* dst;
-    if constexpr (AFFIN) {       // bucket g_first + t of a chunk of buckets; its points sit at starts[g] - list_base of the chunk's list
-        const uint32_t g = g_first + t;
-        beg = starts[g] - list_base; cnt = counts[g];
-        dst = buckets + g;
-    } else if (t >= n_chunks) {         // one whole bucket per thread
-        const uint32_t g = order[n_heavy + (t - n_chunks)];
-        beg = starts[g]; cnt = counts[g];
-        dst = buckets + g;
-    } else {                     // chunk t: a slice of `chunk` entries of heavy bucket order[h] -> partials[t]
-        uint32_t lo = 0, hi = n_heavy;   // largest h with chunk_start[h] <= t
-        while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (chunk_start[mid] <= t) lo = mid; else hi = mid; }
-        const uint32_t g = order[lo], j = t - chunk_start[lo];
-        beg = starts[g] + j * chunk;
-        cnt = counts[g] - j * chunk;
-        if (cnt > chunk) cnt = chunk;
-        dst = partials + t;
-    }
-    // Y1 is needed at the start (u = y2 Z1 - Y1) and at the very end (Y3 = ... - vvv Y1) of an
-    // addition; in between it is parked in LDS (G1 only, 26 KiB per block, word-major so lanes
-    // hit distinct banks) -- that is the difference between fitting the 256-register budget and
-    // spilling to scratch.
-    constexpr bool PARK = (F::DEG == 1) && WAVES >= 2;
-    __shared__ uint32_t park[PARK ? NL : 1][PARK ? 256 : 1];
-    Proj<C> acc = proj_zero<C>();
-    uint32_t k = 0;
-    int phase = 0, salt_id = 0;     // phase 0: list entry k; 1: +S; 2: entry k again; 3: -S
-    uint32_t guard = 0;
-    while (k < cnt && guard < 4 * cnt + 8) {
-        guard++;
-        Aff<C> q;
-        if (phase == 1 || phase == 3) {
-            q = ld_aff<C>(salts + salt_id);
-            if (phase == 3) q.y = F::neg(q.y);
-        } else {
-            if constexpr (AFFIN) {   // T64 list (aff_kernels.h): element e in tile e / 64, slot e % 64
-                static_assert(!AFFIN || F::DEG == 1, "affine-round lists: prime-field curves");
-                const uint32_t e = beg + k;
-                F::comp(q.x, 0) = t64_ld_x(bases, e >> 6, e & 63u);
-                F::comp(q.y, 0) = t64_ld_y(bases, e >> 6, e & 63u);
-                if (phase == 0 && F::comp(q.x, 0).l[0] == AFF_MARK) { k++; continue; }   // a cancelled pair: nothing to add
-            } else {
-                const uint32_t e = sorted[beg + k];
-                q = ld_aff<C>(bases + (e & 0x7FFFFFFFu));
-                if (e >> 31) q.y = F::neg(q.y);
-            }
-        }
-        if (proj_is_zero<C>(acc)) {
-            acc.x = q.x; acc.y = q.y; acc.z = F::one();
-        } else {
-            // madd-1998-cmo (swp.rs:497-517)
-            typename F::T v = F::mul(q.x, acc.z);
-            typename F::T u = F::mul(q.y, acc.z);
-            if (phase == 0 && F::eq(u, acc.y) && F::eq(v, acc.x)) {   // acc == q: take the detour
-                salt_id = F::eq(q.x, ld_aff<C>(salts).x) ? 1 : 0;
-                phase = 1;
-                continue;
-            }
-            if constexpr (WAVES == 1) {
-                // one wave per SIMD (GH_ACC_WAVES=1; not the default): no fences, independent products next to each other.
-                // 2^20 pairs: 25.6 ms against 22.4 ms for the fenced order at two waves.  Explicitly interleaved product
-                // pairs (two accumulator chains alternating statement by statement: 2.8 us per product in isolation,
-                // tools/microbench/lone_wave.hip) need more than 256 live registers here and lose the gain to
-                // AGPR copies (1.9 K v_accvgpr moves per addition): 27.3 ms.
-                u = F::sub(u, acc.y);
-                v = F::sub(v, acc.x);
-                typename F::T vv = F::sqr(v), uu = F::sqr(u);
-                typename F::T r = F::mul(vv, acc.x), vvv = F::mul(v, vv);
-                typename F::T t = F::mul(uu, acc.z), z3 = F::mul(vvv, acc.z);
-                typename F::T a = F::sub(F::sub(t, vvv), F::dbl(r));
-                typename F::T x3 = F::mul(v, a), m1 = F::mul(vvv, acc.y);
-                acc.y = F::sub(F::mul(u, F::sub(r, a)), m1);
-                acc.x = x3;
-                acc.z = z3;
-            } else {
-            // operation order chosen to keep at most seven field elements live (register budget 256);
-            // the scheduling fences make hipcc keep that order instead of hoisting products
-#if defined(__HIP_DEVICE_COMPILE__)
-#define GH_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define GH_FENCE()
-#endif
-            u = F::sub(u, acc.y);
-            v = F::sub(v, acc.x);
-            if constexpr (PARK) {
-                const uint32_t* yw = reinterpret_cast<const uint32_t*>(&acc.y);
-#pragma unroll
-                for (int w = 0; w < NL; w++) park[w][threadIdx.x] = yw[w];
-            }
-            GH_FENCE();
-            typename F::T vv = F::sqr(v);
-            GH_FENCE();
-            typename F::T r = F::mul(vv, acc.x);        // acc.x dead
-            GH_FENCE();
-            typename F::T vvv = F::mul(v, vv);          // vv dead
-            GH_FENCE();
-            typename F::T uu = F::sqr(u);
-            GH_FENCE();
-            typename F::T a = F::sub(F::sub(F::mul(uu, acc.z), vvv), F::dbl(r));   // uu dead
-            GH_FENCE();
-            acc.x = F::mul(v, a);                       // v dead
-            GH_FENCE();
-            typename F::T rma = F::sub(r, a);           // r, a dead
-            GH_FENCE();
-            typename F::T y1 = acc.y;
-            if constexpr (PARK) {
-                uint32_t* yw = reinterpret_cast<uint32_t*>(&y1);
-#pragma unroll
-                for (int w = 0; w < NL; w++) yw[w] = park[w][threadIdx.x];
-            }
-            // (the dual product with one reduction, F::mul_sub_mul, was measured SLOWER here: its two
-            //  accumulators cost 360 B more spills per addition; 31.2 ms vs 28.8 ms at 2^20)
-            acc.y = F::sub(F::mul(u, rma), F::mul(vvv, y1));
-            GH_FENCE();
-            acc.z = F::mul(vvv, acc.z);
-#undef GH_FENCE
-            }
-        }
-        if (phase == 0 || phase == 3) { k++; phase = 0; } else phase++;
-    }
-    st_proj<C>(dst, acc);
-}
+// AFFIN = true: the input is the output list of the affine rounds (aff_kernels.h): bucket g_first + t owns the records
+// [starts[g] - list_base, + counts[g]) of `bases` directly (no index list, no signs) and infinity markers are skipped.
 
 // ---------------------------------------------------------------- 4-asm. task table of the assembly accumulation kernel
-// The task decode of msm_accumulate_kernel / msm_accumulate_xyzz_kernel (chunks of the heavy buckets first, then every other
+// The task decode of msm_accumulate_xyzz_kernel (chunks of the heavy buckets first, then every other
 // bucket by descending size) as a table, so that the assembly kernel (asmgen/g1_xyzz.py) starts from (beg, cnt, dst).
 struct AccTaskRec {
     uint32_t beg, cnt;
@@ -904,9 +730,8 @@ msm_acc_tasks_kernel(const uint32_t* __restrict__ starts, const uint32_t* __rest
 }
 
 // ---------------------------------------------------------------- 4a. G1 bucket accumulation on XYZZ accumulators
-// The same task list, the same list walk and the same salt detour as msm_accumulate_kernel, with the running sum in
-// extended Jacobian coordinates (ec29.h, Xyzz): madd-2008-s, 8 M + 2 S, and Y3 as one dual product on a single
-// accumulator chain (fp_mul2s) -- 12 194 v_mad_u64_u32 per bucket update where madd-1998-cmo issues 14 226.
+// The task list, list walk and salt detour of section 4, with the running sum in extended Jacobian coordinates (ec29.h, Xyzz):
+// madd-2008-s, 8 M + 2 S, and Y3 as one dual product on a single accumulator chain (fp_mul2s) -- 12 194 v_mad_u64_u32 per bucket update where madd-1998-cmo issues 14 226.
 // Register plan (256 VGPRs, two waves per SIMD): ZZ and ZZZ stay in registers; X and Y of the running sum live in LDS
 // (word-major, 2 x 26 KiB per block) and are read where the formula needs them (X: P and Q; Y: R and Y3), so the loop
 // never holds more than six field elements next to a product's own m / r arrays.
@@ -1036,14 +861,14 @@ msm_accumulate_xyzz_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __r
 //   even lane: c0 = a0 b0 + NR a1 b1        odd lane: c1 = a1 b0 + a0 b1
 // with the partner's coefficients fetched by DPP quad permutes (26 moves per operand: swap, broadcast of either half).
 // 22 Fp-product times per mixed addition and lane pair, against 31 on one lane -- but in registers.
-// DUAL = true: one dual product with a single reduction per lane (2028 mads, 4 operands + 2 accumulators live:
-// 512 registers, 1 wave / SIMD); DUAL = false: two plain products per lane (2704 mads, the register footprint
-// of the G1 kernel: 256 registers, 2 waves / SIMD -- what the VALU needs to be kept busy).
-template <class P, int NR, bool DUAL = true> struct F2S {
+// Each lane issues one dual product with a single reduction (2028 mads, 4 operands + 2 accumulators live: 512 registers,
+// 1 wave / SIMD).  Two plain products per lane at 2 waves / SIMD (2704 mads, 256 registers) spilled 0.8-1.8 KB and were
+// slower: accumulation 166 against 119 ms, affine rounds 91 against 68 ms (2^20 pairs).
+template <class P, int NR> struct F2S {
     typedef Fp T;
     static constexpr int DEG = 1;   // per-lane footprint
     static constexpr int LANES = 2;
-    static constexpr int WAVES = DUAL ? 1 : 2;
+    static constexpr int WAVES = 1;
     static __device__ __forceinline__ bool odd() { return (threadIdx.x & 1u) != 0; }
     static __device__ __forceinline__ T swap(const T& a) {
         T r;
@@ -1075,11 +900,7 @@ template <class P, int NR, bool DUAL = true> struct F2S {
         // per lane:  even: a0 b0 + (NR a1) b1      odd: a1 b0 + a0 b1
         // = own a times b0, the partner's a (times NR on the even lane: fp_mul_small_rt with k = NR / 1) times b1
         const T ao = fp_mul_small_rt<P>(swap(a), o ? 1u : (uint32_t)NR), b0 = bcast<0>(b), b1 = bcast<1>(b);
-        if constexpr (DUAL) {
-            return fp_mul2<P>(a, b0, ao, b1);
-        } else {
-            return fp_add<P>(fp_mul<P>(a, b0), fp_mul<P>(ao, b1));
-        }
+        return fp_mul2<P>(a, b0, ao, b1);
     }
     static __device__ __forceinline__ T mul_sub_mul(const T& a, const T& b, const T& c, const T& d) { return sub(mul(a, b), mul(c, d)); }
     static __device__ __forceinline__ T sqr(const T& a) { return mul(a, a); }
@@ -1106,16 +927,13 @@ template <class P, int NR, bool DUAL = true> struct F2S {
 // Fq3 = Fp[X]/(X^3 - NR) over lane triples (lanes 3g, 3g+1, 3g+2 hold c0, c1, c2; lane 63 of a wave
 // idles).  Schoolbook, three Fp products per lane:
 //   c_j = sum_{m <= j} a_(j-m) b_m + NR sum_{m > j} a_(j-m+3) b_m
-// TRIPLE = 0: three plain products in a rolled loop (4056 mads, 2 waves / SIMD); 1: ONE triple product with a single
-// reduction (fp_mul3: 2704 mads) inlined at every site (1 wave / SIMD; hipcc does not get through it); 2: that triple
-// product as one out-of-line function (GH_F3S_CALL_WAVES waves / SIMD) -- the default, see msm_impl.h.
-// The tower product of a lane triple as ONE out-of-line device function (F3S mode 2): lane rotations, the two NR multiples,
-// the operand selection and the triple product with its single reduction.  One body per kernel instead of one per
-// product site, which is what lets hipcc get through the kernels at all (mode 1, the same code inlined at every site,
-// had not compiled after an hour).  Two Fp arguments and an Fp result travel in VGPRs / on the stack.
-#ifndef GH_F3S_CALL_WAVES
-#define GH_F3S_CALL_WAVES 1
-#endif
+// A lane's three products are ONE triple product with a single reduction (fp_mul3: 2704 mads), issued as ONE out-of-line
+// device function (f3s_mul_outlined: lane rotations, the two NR multiples, the operand selection and the triple product),
+// at 1 wave / SIMD.  One body per kernel instead of one per product site is what lets hipcc get through the kernels at all:
+// the same code inlined at every site had not compiled after an hour.  Measured against it (2^19 pairs): three plain
+// products in a rolled loop (4056 mads, 2 waves / SIMD) took the projective accumulation 222 instead of 167 ms, the bucket
+// reduction 17.4 instead of 13.6 ms and the affine rounds 133 instead of 98 ms; the outlined product at 2 waves / SIMD
+// spilled 1.4 KB in the caller (140 ms).  Two Fp arguments and an Fp result travel in VGPRs / on the stack.
 template <class P, int NR> __device__ __attribute__((noinline)) Fp f3s_mul_outlined(Fp a, Fp b) {
     const int lane = threadIdx.x & 63, j = lane % 3, base = lane - j;
     const int s1 = base + (j + 1) % 3, s2 = base + (j + 2) % 3;
@@ -1132,11 +950,11 @@ template <class P, int NR> __device__ __attribute__((noinline)) Fp f3s_mul_outli
     return fp_mul3<P>(a, y1, x2, y2, x3, y3);
 }
 
-template <class P, int NR, int TRIPLE = 0> struct F3S {
+template <class P, int NR> struct F3S {
     typedef Fp T;
     static constexpr int DEG = 1;
     static constexpr int LANES = 3;
-    static constexpr int WAVES = TRIPLE == 1 ? 1 : (TRIPLE == 2 ? GH_F3S_CALL_WAVES : 2);
+    static constexpr int WAVES = 1;
     static __device__ __forceinline__ int comp() { return (int)((threadIdx.x & 63u) % 3u); }
     static __device__ __forceinline__ T rot(const T& a, int by) {   // coefficient held by lane (comp + by) mod 3 of this triple
         const int lane = threadIdx.x & 63, j = lane % 3, src = lane - j + (j + by) % 3;
@@ -1145,56 +963,16 @@ template <class P, int NR, int TRIPLE = 0> struct F3S {
         for (int i = 0; i < NL; i++) r.l[i] = (uint32_t)__shfl((int)a.l[i], src);
         return r;
     }
-    static __device__ __forceinline__ T sel3(int j, const T& x0, const T& x1, const T& x2) {
-        T r;
-#pragma unroll
-        for (int i = 0; i < NL; i++) r.l[i] = j == 0 ? x0.l[i] : (j == 1 ? x1.l[i] : x2.l[i]);
-        return r;
-    }
     static __device__ __forceinline__ T zero() { return fp_zero(); }
     static __device__ __forceinline__ T one() { return comp() == 0 ? fp_one<P>() : fp_zero(); }
     static __device__ __forceinline__ T add(const T& a, const T& b) { return fp_add<P>(a, b); }
     static __device__ __forceinline__ T sub(const T& a, const T& b) { return fp_sub<P>(a, b); }
     static __device__ __forceinline__ T dbl(const T& a) { return fp_dbl<P>(a); }
     static __device__ __forceinline__ T neg(const T& a) { return fp_neg<P>(a); }
-    // The three products of a lane run in a ROLLED loop (one fp_mul body per call site): with them
-    // unrolled the kernel held 33 inlined products and hipcc needed more than half an hour for it.
-    //   iteration m:  lane j takes a_((j - m) mod 3) * b_m, times NR when m > j (the wrapped terms)
-    static __device__ __forceinline__ T mul(const T& a, const T& b) {
-        if constexpr (TRIPLE == 2) return f3s_mul_outlined<P, NR>(a, b);
-        if constexpr (TRIPLE == 1) {
-            // c_j = a_j b_0 + [NR if j = 0] a_(j-1) b_1 + [NR if j < 2] a_(j-2) b_2     (indices mod 3)
-            const int j = comp();
-            const T an = rot(a, 1), ap = rot(a, 2), bn = rot(b, 1), bp = rot(b, 2);
-            const T apn = fp_mul_small<P, NR>(ap), ann = fp_mul_small<P, NR>(an);
-            T x2, x3;
-#pragma unroll
-            for (int i = 0; i < NL; i++) { x2.l[i] = j == 0 ? apn.l[i] : ap.l[i]; x3.l[i] = j < 2 ? ann.l[i] : an.l[i]; }
-            return fp_mul3<P>(a, sel3(j, b, bp, bn), x2, sel3(j, bn, b, bp), x3, sel3(j, bp, bn, b));
-        }
-        const int lane = threadIdx.x & 63, j = lane % 3, base = lane - j;
-        T acc = fp_zero();
-#pragma nounroll
-        for (int m = 0; m < 3; m++) {
-            const int ja = j - m < 0 ? j - m + 3 : j - m;
-            T x, y;
-#pragma unroll
-            for (int i = 0; i < NL; i++) {
-                x.l[i] = (uint32_t)__shfl((int)a.l[i], base + ja);
-                y.l[i] = (uint32_t)__shfl((int)b.l[i], base + m);
-            }
-            T t = fp_mul<P>(x, y);
-            const T tn = fp_mul_small<P, NR>(t);
-            const bool wrap = m > j;
-#pragma unroll
-            for (int i = 0; i < NL; i++) t.l[i] = wrap ? tn.l[i] : t.l[i];
-            acc = fp_add<P>(acc, t);
-        }
-        return acc;
-    }
+    static __device__ __forceinline__ T mul(const T& a, const T& b) { return f3s_mul_outlined<P, NR>(a, b); }
     static __device__ __forceinline__ T sqr(const T& a) { return mul(a, a); }
     static __device__ __forceinline__ T mul_sub_mul(const T& a, const T& b, const T& c, const T& d) { return sub(mul(a, b), mul(c, d)); }
-    static __device__ __forceinline__ T sub_lazy(const T& a, const T& b) { return fp_sub<P>(a, b); }   // triple / rolled products: reduced operands
+    static __device__ __forceinline__ T sub_lazy(const T& a, const T& b) { return fp_sub<P>(a, b); }   // the triple product takes reduced operands
     // norm-based inverse in Fp[X]/(X^3 - NR) (fp3.rs inverse), one Fp inversion per lane triple:
     //   c0 = a0^2 - NR a1 a2,  c1 = NR a2^2 - a0 a1,  c2 = a1^2 - a0 a2,  n = a0 c0 + NR (a2 c1 + a1 c2),  a^-1 = c / n
     // lane j holds a_j: it forms its own square and the product a_j a_(j+1), the rest travels by lane rotation.
@@ -1224,12 +1002,12 @@ template <class P, int NR, int TRIPLE = 0> struct F3S {
     static __device__ __forceinline__ bool eq(const T& a, const T& b) { return all3(fp_eq(a, b)); }
 };
 
-// Same task list and addition as msm_accumulate_kernel, LANES lanes per task (2: Fq2 pairs, 3: Fq3
+// Same task list, salt detour and addition (madd-1998-cmo) as section 4, LANES lanes per task (2: Fq2 pairs, 3: Fq3
 // triples; a wave carries 64 / LANES tasks, the remaining lane of a triple wave idles).
 #ifndef GH_SPLIT_WAVES
 #define GH_SPLIT_WAVES 1   // measured on Fq2 (twice): 119 ms at 1 wave/SIMD (512 registers) vs 135 ms at 2 (1.5 KB of spills), 2^20 pairs
 #endif
-// AFFIN: as for msm_accumulate_kernel -- the input is the T64 output list of the affine rounds.
+// AFFIN: as in section 4 -- the input is the T64 output list of the affine rounds.
 template <class C, class F, int LANES, bool AFFIN = false>
 __global__ void __launch_bounds__(256, F::WAVES)
 msm_accumulate_split_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __restrict__ sorted,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -62,6 +63,24 @@ std::mutex& api_mutex();     // the lock every ABI entry point holds (one device
 int pool_get(const char* name, size_t bytes, void** out);
 size_t pool_cap(const char* name);                 // current capacity of a cached buffer (0 if none)
 void pool_release(const char* prefix);             // free every cached buffer whose name starts with prefix ("" = all)
+// the cached buffer `name` of one MSM buffer slot: pool name "name#slot"
+inline std::string slot_name(const char* name, int slot) { return std::string(name) + "#" + std::to_string(slot); }
+template <class T> int slot_buf(const char* name, int slot, size_t bytes, T** out) {
+    return pool_get(slot_name(name, slot).c_str(), bytes, (void**)out);
+}
+// an integer / real knob from the environment: dflt when unset, atoi / atof of the value otherwise
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+inline double env_double(const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; }
+// Waits for every stream an MSM runs on, the second stream of a split affine round included: nothing may still read or write a
+// pooled buffer or a cached key when it is released.  Waits on all four even after an error; returns the first error.
+inline hipError_t sync_msm_streams() {
+    hipError_t e = hipSuccess;
+    for (hipStream_t s : {g.stream, g.stream_acc, g.stream_acc2, g.stream_red}) {
+        const hipError_t es = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = es;
+    }
+    return e;
+}
 int device_scan(const uint32_t* in, uint32_t* out, size_t n, const char* tmpname, hipStream_t stream = nullptr);   // nullptr: g.stream
 int auto_window(size_t n, int deg);
 void dist_teardown_locked();                      // dist.hip: gh_shutdown (API lock held) destroys the communicator with the context

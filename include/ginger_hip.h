@@ -214,7 +214,7 @@ int gh_msm_set_affine(int mode);
  * library stream, host fold by a host clock).  Any pointer may be NULL. */
 typedef struct {
     float sort_ms;        /* digit extraction + bucket sort */
-    float accumulate_ms;  /* msm_accumulate_kernel alone (dominant kernel), HIP events around the launch */
+    float accumulate_ms;  /* the bucket accumulation alone (dominant kernels), HIP events around its launches */
     float heavy_ms;       /* wave-cooperative path for over-long buckets */
     float reduce_ms;      /* bucket running-sum reduction kernels */
     float fold_ms;        /* window fold (host) + D2H of window sums */

@@ -55,7 +55,7 @@ static int run_tree(const uint64_t* bases_xy, size_t n_bases, const uint32_t* so
         }
         in = out;
     }
-    // finish: what msm_accumulate_kernel<.., AFFIN = true> does (markers skipped)
+    // finish: what msm_accumulate_xyzz_kernel<.., AFFIN = true> does (markers skipped)
     const uint32_t* stR = st.data() + (size_t)(R - 1) * stride;
     const uint32_t* mR = cnt.data() + (size_t)(R - 1) * stride;
     for (uint32_t b = 0; b < total; b++) {

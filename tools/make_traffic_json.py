@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from bench import kernels_sha
 
-ACC = ("msm_accumulate_kernel", "msm_accumulate_xyzz_kernel", "msm_accumulate_split_kernel", "aff_round_kernel", "aff_desc_kernel", "msm_heavy_combine_kernel",
+ACC = ("msm_accumulate_xyzz_kernel", "msm_accumulate_split_kernel", "aff_round_kernel", "aff_desc_kernel", "msm_heavy_combine_kernel",
        "gh_asm_acc_g1", "gh_asm_aff", "aff_inv_kernel", "aff_fix_kernel", "msm_acc_tasks_kernel")
 
 
