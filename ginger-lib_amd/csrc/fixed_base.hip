@@ -426,6 +426,33 @@ int fixed_run_affine(const FixedTable* t, const uint64_t* scalars, size_t n, uin
     return GH_E_BAD_ARG;
 }
 
+int fixed_table_create(gh_curve_t curve, const uint64_t* g_xyz, size_t scalar_size, int window, FixedTable** out) {
+    FixedTable* t = new FixedTable();
+    t->curve = curve;
+    if (int rc = fixed_build(curve, g_xyz, scalar_size, window, t)) {
+        delete t;
+        return rc;
+    }
+    *out = t;
+    return GH_OK;
+}
+int fixed_table_sums(const FixedTable* t, const void* d_scalars, size_t n, void* d_out_proj) {
+    if (n == 0) return GH_OK;
+    switch (t->curve) {
+        case GH_MNT4753_G1: return launch_fixed_sums<Mnt4G1>(t, d_scalars, n, d_out_proj);
+        case GH_MNT4753_G2: return launch_fixed_sums<Mnt4G2>(t, d_scalars, n, d_out_proj);
+        case GH_MNT6753_G1: return launch_fixed_sums<Mnt6G1>(t, d_scalars, n, d_out_proj);
+        case GH_MNT6753_G2: return launch_fixed_sums<Mnt6G2>(t, d_scalars, n, d_out_proj);
+    }
+    return GH_E_BAD_ARG;
+}
+void fixed_table_destroy(FixedTable* t) {
+    if (!t) return;
+    if (t->d_table) (void)hipFree(t->d_table);
+    t->magic = 0;
+    delete t;
+}
+
 }  // namespace gh_rt
 
 using namespace gh_rt;

@@ -235,6 +235,22 @@ bool mul_overflows(size_t a, size_t b, size_t* r) { return __builtin_mul_overflo
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------- lock-held helpers (runtime.h)
+namespace gh_rt {
+int poseidon_field(const gh_poseidon* h, gh_field_t* out) {
+    if (!valid(h)) { g_err = "not a Poseidon handle"; return GH_E_BAD_HANDLE; }
+    *out = h->field;
+    return GH_OK;
+}
+int poseidon_hash_dev_locked(gh_poseidon* h, const void* d_in, size_t n, size_t len, void* d_out) {
+    if (!valid(h)) { g_err = "not a Poseidon handle"; return GH_E_BAD_HANDLE; }
+    if (n == 0) return GH_OK;
+    if (int rc = prepare(h)) return rc;
+    return launch(h, d_in, n, len, d_out, 0);
+}
+void poseidon_trim_slab() { SlabTrim trim_; }
+}  // namespace gh_rt
+
 // ---------------------------------------------------------------------------------------------------- C ABI
 extern "C" {
 

@@ -13,6 +13,8 @@
 #include "../../include/ginger_hip.h"
 #include "fp29.h"
 
+struct gh_poseidon;
+
 namespace gh_rt {
 
 struct Domain {
@@ -163,5 +165,14 @@ int witness_map(gh_field_t field, void* d_a, void* d_b, void* d_c, uint32_t log_
 int sap_witness_map(gh_field_t field, void* d_a, void* d_c, uint32_t log_n, const uint64_t* d1, const uint64_t* d2, void* d_h);
 int batch_inverse(gh_field_t field, void* d_a, size_t n);
 int lagrange_coefficients(gh_field_t field, uint32_t log_n, const uint64_t* tau12, void* d_out);
+
+// ---- lock-held helpers for other units (schnorr.hip); the caller holds api_mutex() and has run ensure_init()
+struct FixedTable;                                 // fixed_base.hip: a window table of one base
+int fixed_table_create(gh_curve_t curve, const uint64_t* g_xyz, size_t scalar_size, int window, FixedTable** out);
+int fixed_table_sums(const FixedTable* t, const void* d_scalars, size_t n, void* d_out_proj);   // on g.stream, internal Proj<C>
+void fixed_table_destroy(FixedTable* t);
+int poseidon_field(const gh_poseidon* h, gh_field_t* out);                              // GH_E_BAD_HANDLE if h is none
+int poseidon_hash_dev_locked(gh_poseidon* h, const void* d_in, size_t n, size_t len, void* d_out);   // on g.stream, no sync
+void poseidon_trim_slab();                         // the release of a large slab every Poseidon entry point does on return
 
 }  // namespace gh_rt
