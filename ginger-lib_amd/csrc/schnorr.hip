@@ -2,22 +2,10 @@
 // the field-based Schnorr signature (primitives/src/signature/schnorr/field_based_schnorr.rs) built on it, the fixed-base
 // path of fixed_base.hip and the Poseidon kernels of poseidon.hip.  DESIGN.md section 12.
 //
-// Variable base, one lane per row (out[i] = k_i P_i, a different P_i per row):
-//   vb_table_kernel   the odd multiples (2 j + 1) P_i, j < 2^(W-1), by one doubling and 2^(W-1) - 1 projective additions, then
-//                     to affine by Montgomery's trick over the row's entries with ONE safegcd inversion (fp_inv, ~40 products);
-//                     the entries live in a per-row global slab, limb-major with the row index fastest (the lanes of a wave
-//                     read 256 consecutive bytes per limb)
-//   vb_mul_kernel     the regular signed-window recoding of schnorr_recode.h: W (M - 1) doublings and M - 1 mixed additions
-//                     for every row, digits read straight from the scalar's bits, one final correction for an even scalar.
-//                     Only the exceptional cases inside the mixed addition (P = +-Q, an accumulator at infinity) diverge.
-// Large batches are cut into chunks whose slab stays below VB_SLAB_BYTES.
-#include <string.h>
-#include <algorithm>
+// The kernels are those of vb_kernels.h.  Large batches are cut into chunks whose slab stays below VB_SLAB_BYTES.
 #include <chrono>
 #include <vector>
-#include "runtime.h"
-#include "msm_kernels.h"
-#include "schnorr_recode.h"
+#include "vb_kernels.h"
 #include "../../include/ginger_hip_schnorr.h"
 
 using namespace gh;
@@ -35,203 +23,12 @@ struct gh_schnorr {
 
 namespace {
 
-constexpr int BLOCK = 64;
 constexpr size_t VB_SLAB_BYTES = (size_t)1 << 30;     // bound of the variable-base slab; larger batches run in chunks
 constexpr size_t SLAB_KEEP_BYTES = (size_t)64 << 20;  // pooled buffers above this are released when an entry point returns
 constexpr int VB_W_DEFAULT = 4;                       // the fastest of the sweep w = 4, 5, 6
 constexpr int NPHASES = 6;
 float g_phase_ms[NPHASES];
 float g_total_ms = 0;
-
-// ---------------------------------------------------------------------------------------------------- device helpers
-// slot s of the row's slab: NL words, stride T (rows of the chunk)
-struct RowSlab {
-    uint32_t* base;
-    size_t stride;
-    __device__ __forceinline__ Fp ld(int slot) const {
-        Fp r;
-        const uint32_t* q = base + (size_t)slot * NL * stride;
-#pragma unroll
-        for (int i = 0; i < NL; i++) r.l[i] = q[(size_t)i * stride];
-        return r;
-    }
-    __device__ __forceinline__ void st(int slot, const Fp& v) const {
-        uint32_t* q = base + (size_t)slot * NL * stride;
-#pragma unroll
-        for (int i = 0; i < NL; i++) q[(size_t)i * stride] = v.l[i];
-    }
-};
-// entry j: slots 4 j (x), 4 j + 1 (y), 4 j + 2 (z), 4 j + 3 (prefix product of the Montgomery trick)
-constexpr int SLOTS_PER_ENTRY = 4;
-
-// internal Montgomery -> the integer itself, 24 LE words
-template <class P> GH_HD void fp_to_int(uint32_t* w, const Fp& a) {
-    Fp one = fp_zero();
-    one.l[0] = 1;
-    fp_pack(w, fp_mul<P>(a, one));
-}
-// an integer below p (24 LE words) -> internal Montgomery
-template <class P> GH_HD Fp fp_from_int(const uint32_t* w) { return fp_mul<P>(fp_unpack(w), fp_const<P>(P::R2I)); }
-GH_HD bool bit752(const uint32_t* w) { return (w[23] >> 16) & 1u; }
-
-// ---------------------------------------------------------------------------------------------------- variable base
-template <class C, int W>
-__global__ void __launch_bounds__(BLOCK)
-vb_table_kernel(const uint32_t* __restrict__ xy /* n x 48 words, ABI */, const uint8_t* __restrict__ inf, size_t row0, size_t cnt,
-                int negate, uint32_t* __restrict__ slab) {
-    typedef typename C::FC F;
-    typedef typename C::PF PF;
-    constexpr int E = VbWindow<W>::E;
-    const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= cnt) return;
-    const size_t i = row0 + t;
-    const RowSlab s{slab + t, cnt};
-    if (inf && inf[i]) return;                               // vb_mul_kernel writes infinity without reading the slab
-    Proj<C> p{fp_from_abi<PF>(xy + i * 48), fp_from_abi<PF>(xy + i * 48 + 24), F::one()};
-    if (negate) p.y = F::neg(p.y);
-    const Proj<C> d = proj_dbl_call<C>(p);
-    Fp run = F::one();
-#pragma unroll 1
-    for (int j = 0; j < E; j++) {
-        if (j) p = proj_add_call<C>(p, d);
-        s.st(SLOTS_PER_ENTRY * j, p.x);
-        s.st(SLOTS_PER_ENTRY * j + 1, p.y);
-        s.st(SLOTS_PER_ENTRY * j + 2, p.z);
-        s.st(SLOTS_PER_ENTRY * j + 3, run);                  // product of the non-zero Z before entry j
-        if (!F::is_zero(p.z)) run = F::mul(run, p.z);
-    }
-    Fp inv = fp_inv<PF>(run);
-#pragma unroll 1
-    for (int j = E - 1; j >= 0; j--) {
-        const Fp z = s.ld(SLOTS_PER_ENTRY * j + 2);
-        if (F::is_zero(z)) continue;                         // only for a base off the curve: its row is garbage, not a fault
-        const Fp zi = F::mul(inv, s.ld(SLOTS_PER_ENTRY * j + 3));
-        inv = F::mul(inv, z);
-        s.st(SLOTS_PER_ENTRY * j, F::mul(s.ld(SLOTS_PER_ENTRY * j), zi));
-        s.st(SLOTS_PER_ENTRY * j + 1, F::mul(s.ld(SLOTS_PER_ENTRY * j + 1), zi));
-    }
-}
-
-template <class C, int W>
-__global__ void __launch_bounds__(BLOCK)
-vb_mul_kernel(const uint32_t* __restrict__ slab, const uint32_t* __restrict__ scalars /* n x 24 words, canonical */,
-              const uint8_t* __restrict__ inf, size_t row0, size_t cnt, Proj<C>* __restrict__ out) {
-    typedef typename C::F F;
-    constexpr int M = VbWindow<W>::M;
-    const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= cnt) return;
-    const size_t i = row0 + t;
-    if (inf && inf[i]) {
-        st_words(out + i, proj_zero<C>());
-        return;
-    }
-    const RowSlab s{const_cast<uint32_t*>(slab) + t, cnt};
-    const uint32_t* k = scalars + i * 24;
-    auto entry = [&](uint32_t idx, bool neg) {
-        Aff<C> a{s.ld(SLOTS_PER_ENTRY * idx), s.ld(SLOTS_PER_ENTRY * idx + 1)};
-        const Fp ny = F::neg(a.y);
-        if (neg) a.y = ny;
-        return a;
-    };
-    uint32_t idx;
-    bool neg;
-    vb_digit<W>(k, M - 1, idx, neg);
-    const Aff<C> top = entry(idx, false);
-    Proj<C> q{top.x, top.y, F::one()};
-#pragma unroll 1
-    for (int j = M - 2; j >= 0; j--) {
-#pragma unroll 1
-        for (int b = 0; b < W; b++) q = proj_dbl<C>(q);
-        vb_digit<W>(k, j, idx, neg);
-        q = proj_madd<C>(q, entry(idx, neg));
-    }
-    if (!(k[0] & 1u)) q = proj_madd<C>(q, entry(0, true));   // k was run as k | 1
-    st_words(out + i, q);
-}
-
-// ---------------------------------------------------------------------------------------------------- pipeline kernels
-// internal projective -> ABI (gh_proj_mul's layout), infinity as (0, 1, 0)
-template <class C>
-__global__ void __launch_bounds__(256) proj_to_abi_kernel(const Proj<C>* __restrict__ in, size_t n, uint32_t* __restrict__ out) {
-    typedef typename C::FC F;
-    typedef typename C::PF PF;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Proj<C> p = ld_words(in + i);
-    if (F::is_zero(p.z)) p = proj_zero<C>();
-    fp_to_abi<PF>(out + i * 72, p.x);
-    fp_to_abi<PF>(out + i * 72 + 24, p.y);
-    fp_to_abi<PF>(out + i * 72 + 48, p.z);
-}
-
-// a[i] (+ b[i] if b) to affine by Montgomery's trick over runs of NORM_RUN points; x, y in ABI form at
-// out_xy + i * row_words + off (y 24 words later), infinity as (0, 1); out_inf (nullable) the infinity bytes
-constexpr int NORM_RUN = 16;
-template <class C>
-__global__ void __launch_bounds__(BLOCK)
-normalize_kernel(Proj<C>* __restrict__ a, const Proj<C>* __restrict__ b, size_t n, Fp* __restrict__ zp, uint32_t* __restrict__ out_xy,
-                 size_t row_words, size_t off, uint8_t* __restrict__ out_inf) {
-    typedef typename C::FC F;
-    typedef typename C::PF PF;
-    const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    const size_t i0 = t * NORM_RUN;
-    if (i0 >= n) return;
-    const int cnt = (int)(n - i0 < (size_t)NORM_RUN ? n - i0 : (size_t)NORM_RUN);
-    Fp run = F::one();
-    for (int j = 0; j < cnt; j++) {
-        Proj<C> p = ld_words(a + i0 + j);
-        if (b) {
-            p = proj_add_call<C>(p, ld_words(b + i0 + j));
-            st_words(a + i0 + j, p);
-        }
-        st_words(zp + i0 + j, run);
-        if (!F::is_zero(p.z)) run = F::mul(run, p.z);
-    }
-    Fp inv = fp_inv<PF>(run);
-    for (int j = cnt - 1; j >= 0; j--) {
-        const Proj<C> p = ld_words(a + i0 + j);
-        uint32_t* w = out_xy + (i0 + j) * row_words + off;
-        const bool zero = F::is_zero(p.z);
-        if (out_inf) out_inf[i0 + j] = zero;
-        if (zero) {
-            fp_to_abi<PF>(w, fp_zero());
-            fp_to_abi<PF>(w + 24, F::one());
-            continue;
-        }
-        const Fp zi = F::mul(inv, ld_words(zp + i0 + j));
-        inv = F::mul(inv, p.z);
-        fp_to_abi<PF>(w, F::mul(p.x, zi));
-        fp_to_abi<PF>(w + 24, F::mul(p.y, zi));
-    }
-}
-
-// scalar-field Montgomery (ABI) -> canonical integers; zero (nullable) flags k == 0
-template <class PS>
-__global__ void __launch_bounds__(256) mont_to_int_kernel(const uint32_t* __restrict__ in, size_t n, uint32_t* __restrict__ out,
-                                                          uint8_t* __restrict__ zero) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Fp v = fp_from_abi<PS>(in + i * 24);
-    fp_to_int<PS>(out + i * 24, v);
-    if (zero) zero[i] = fp_is_zero(v);
-}
-
-// verify step 1: e, s (data-field Montgomery) -> canonical integers; status 2 (Err) if either is >= 2^752, its scalars zeroed
-template <class PF>
-__global__ void __launch_bounds__(256) sig_prep_kernel(const uint32_t* __restrict__ sig /* n x 48 words */, size_t n,
-                                                       uint32_t* __restrict__ e_int, uint32_t* __restrict__ s_int,
-                                                       uint8_t* __restrict__ status) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t* e = e_int + i * 24;
-    uint32_t* s = s_int + i * 24;
-    fp_to_int<PF>(e, fp_from_abi<PF>(sig + i * 48));
-    fp_to_int<PF>(s, fp_from_abi<PF>(sig + i * 48 + 24));
-    const bool err = bit752(e) || bit752(s);
-    if (err)
-        for (int w = 0; w < 24; w++) e[w] = s[w] = 0u;
-    status[i] = err ? 2 : 0;
-}
 
 // hash rows m_0 .. m_(len-1) | R.x | R.y | pk.x: the message and pk.x (0 for the point at infinity); R comes from normalize_kernel
 __global__ void __launch_bounds__(256) rows_kernel(const uint64_t* __restrict__ msg, const uint64_t* __restrict__ pk_xy,
@@ -255,51 +52,7 @@ __global__ void __launch_bounds__(256) compare_kernel(const uint64_t* __restrict
     status[i] = eq;
 }
 
-// sign, after the hash: e < 2^752, s = k + e sk in the scalar field, s < 2^752, s into the data field; status 1, or 0 and a
-// zero row (k == 0 was flagged by mont_to_int_kernel in status)
-template <class PF, class PS>
-__global__ void __launch_bounds__(256) sign_finish_kernel(const uint32_t* __restrict__ e_abi, const uint32_t* __restrict__ sk,
-                                                          const uint32_t* __restrict__ nonce, size_t n, uint32_t* __restrict__ sig,
-                                                          uint8_t* __restrict__ status) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t* o = sig + i * 48;
-    uint32_t e[24], s[24];
-    const Fp ef = fp_from_abi<PF>(e_abi + i * 24);
-    fp_to_int<PF>(e, ef);
-    bool ok = status[i] == 0 && !bit752(e);                  // status[i] == 1 here: k == 0
-    if (ok) {
-        const Fp es = fp_from_int<PS>(e);                    // e < 2^752 < r
-        const Fp sv = fp_add<PS>(fp_from_abi<PS>(nonce + i * 24), fp_mul<PS>(es, fp_from_abi<PS>(sk + i * 24)));
-        fp_to_int<PS>(s, sv);
-        ok = !bit752(s);
-    }
-    if (ok) {
-        fp_to_abi<PF>(o, ef);
-        fp_to_abi<PF>(o + 24, fp_from_int<PF>(s));           // s < 2^752 < p
-    } else {
-        for (int w = 0; w < 48; w++) o[w] = 0u;
-    }
-    status[i] = ok;
-}
-
-// keyverify: y^2 == x^3 + a x + b, or the point at infinity
-template <class C>
-__global__ void __launch_bounds__(256) on_curve_kernel(const uint32_t* __restrict__ xy, const uint8_t* __restrict__ inf, size_t n, Fp b,
-                                                       uint8_t* __restrict__ ok) {
-    typedef typename C::FC F;
-    typedef typename C::PF PF;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (inf[i]) { ok[i] = 1; return; }
-    const Fp x = fp_from_abi<PF>(xy + i * 48), y = fp_from_abi<PF>(xy + i * 48 + 24);
-    const Fp rhs = F::add(F::add(F::mul(F::sqr(x), x), C::mul_by_a(x)), b);
-    ok[i] = F::eq(F::sqr(y), rhs);
-}
-
 // ---------------------------------------------------------------------------------------------------- host side
-inline unsigned blocks(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
 int vb_window() {
     static const int w = gh_rt::env_int("GH_SCHNORR_WINDOW", VB_W_DEFAULT);   // measurement knob: 4, 5 or 6; anything else: the default
     return (w == 4 || w == 5 || w == 6) ? w : VB_W_DEFAULT;
@@ -347,79 +100,9 @@ struct Trim {
     }
 };
 
-template <class P> bool below(const uint64_t* x) {
-    static const uint64_t p4[12] = GH_P4_P_64, p6[12] = GH_P6_P_64;
-    const uint64_t* p = std::is_same<P, P6>::value ? p6 : p4;
-    for (int i = 11; i >= 0; i--)
-        if (x[i] != p[i]) return x[i] < p[i];
-    return false;
-}
-template <class P> bool all_below(const uint64_t* x, size_t count) {
-    for (size_t i = 0; i < count; i++)
-        if (!below<P>(x + 12 * i)) return false;
-    return true;
-}
-bool mul_overflows(size_t a, size_t b, size_t* r) { return __builtin_mul_overflow(a, b, r); }
-
 bool valid(const gh_schnorr* h) { return h && h->magic == 0x6768536eu; }
 
-// events of the phases: ev[0] start, ev[k] end of phase k
-struct Phases {
-    int k = 0;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    int mark() {
-        HIPCHK(hipEventRecord(g.ev[k], g.stream));
-        k++;
-        return GH_OK;
-    }
-    int finish() {
-        HIPCHK(hipEventSynchronize(g.ev[k - 1]));
-        for (int i = 0; i < NPHASES; i++) g_phase_ms[i] = 0;
-        for (int i = 1; i < k && i <= NPHASES; i++) HIPCHK(hipEventElapsedTime(&g_phase_ms[i - 1], g.ev[i - 1], g.ev[i]));
-        g_total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return GH_OK;
-    }
-};
-
-// the curve's types: C the group, PF its base (= data) field, PS its scalar field
-template <class C> struct Scheme;
-template <> struct Scheme<Mnt6G1> { typedef P6 PF; typedef P4 PS; static constexpr gh_field_t field = GH_MNT4753_FR; };
-template <> struct Scheme<Mnt4G1> { typedef P4 PF; typedef P6 PS; static constexpr gh_field_t field = GH_MNT6753_FR; };
-
-template <class C> void generator_xyz(uint64_t* g_xyz) {
-    const bool m6 = std::is_same<C, Mnt6G1>::value;
-    static const uint64_t gx4[12] = GH_MNT4753_G1_GX0_M_64, gy4[12] = GH_MNT4753_G1_GY0_M_64, one4[12] = GH_P4_R_64;
-    static const uint64_t gx6[12] = GH_MNT6753_G1_GX0_M_64, gy6[12] = GH_MNT6753_G1_GY0_M_64, one6[12] = GH_P6_R_64;
-    memcpy(g_xyz, m6 ? gx6 : gx4, 96);
-    memcpy(g_xyz + 12, m6 ? gy6 : gy4, 96);
-    memcpy(g_xyz + 24, m6 ? one6 : one4, 96);
-}
-
-// The generator's table: the caller's window, or (window 0) gh_fixed_base_window(n), rebuilt when a later call's n asks for a
-// larger window than the table has -- a handle first used on a few rows does not keep a tiny table for large batches.
-// The window grows with log n, so a handle rebuilds at most a few times.
-int ensure_table(gh_schnorr* h, size_t n) {
-    const int w = std::max(1, std::min(h->window ? h->window : gh_fixed_base_window(n), 22));
-    if (h->table && w <= h->table_window) return GH_OK;
-    if (h->table) {
-        HIPCHK(hipStreamSynchronize(g.stream));
-        gh_rt::fixed_table_destroy(h->table);
-        h->table = nullptr;
-        h->table_window = 0;
-    }
-    uint64_t g_xyz[36];
-    if (h->curve == GH_MNT6753_G1) generator_xyz<Mnt6G1>(g_xyz);
-    else generator_xyz<Mnt4G1>(g_xyz);
-    if (int rc = gh_rt::fixed_table_create(h->curve, g_xyz, VB_BITS, w, &h->table)) return rc;
-    h->table_window = w;
-    return GH_OK;
-}
-
-template <class T> int dbuf(const char* name, size_t count, T** out) { return gh_rt::pool_get(name, std::max<size_t>(count * sizeof(T), 64), (void**)out); }
-template <class T> int up(T* d, const T* h, size_t count) {
-    if (count) HIPCHK(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, g.stream));
-    return GH_OK;
-}
+int ensure_table(gh_schnorr* h, size_t n) { return generator_table(h->curve, h->window, n, &h->table, &h->table_window); }
 
 template <class C> int run_public_keys(gh_schnorr* h, const uint64_t* sk, size_t n, uint64_t* out_xy, uint8_t* out_inf) {
     typedef typename Scheme<C>::PS PS;
@@ -472,7 +155,7 @@ template <class C> int run_sign(gh_schnorr* h, const uint64_t* sk, const uint64_
     if (!rc) rc = dbuf("schnorr_xy", n * 24, &d_sig);
     if (!rc) rc = dbuf("schnorr_st", n, &d_st);
     if (rc) return rc;
-    Phases ph;
+    Phases ph{g_phase_ms, NPHASES, &g_total_ms};
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_sk, sk, n * 12)) || (rc = up(d_nonce, nonce, n * 12)) || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_pkinf, pk_inf, n)) ||
         (rc = up(d_msg, msg, n * len * 12)) || (rc = ph.mark()))
@@ -519,7 +202,7 @@ template <class C> int run_verify(gh_schnorr* h, const uint64_t* pk_xy, const ui
     if (!rc) rc = dbuf("schnorr_e", n * 12, &d_e);
     if (!rc) rc = dbuf("schnorr_st", n, &d_st);
     if (rc) return rc;
-    Phases ph;
+    Phases ph{g_phase_ms, NPHASES, &g_total_ms};
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_sig, sig, n * 24)) || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_pkinf, pk_inf, n)) || (rc = up(d_msg, msg, n * len * 12)) ||
         (rc = ph.mark()))
