@@ -18,10 +18,6 @@
 #include "vb_kernels.h"
 #include "../../include/ginger_hip_ecvrf.h"
 
-using namespace gh;
-using gh_rt::g;
-using gh_rt::g_err;
-
 struct gh_bh {
     uint32_t magic = 0x67684268u;
     gh_curve_t curve;
@@ -37,21 +33,15 @@ struct gh_ecvrf {
     gh_curve_t curve;
     gh_poseidon_t hash = nullptr;
     gh_bh_t bh = nullptr;
-    int window = 0;                       // the caller's fixed-base window, 0 = automatic
-    gh_rt::FixedTable* table = nullptr;   // the generator's window table (scalar_size 753), built on first use
-    int table_window = 0;
+    GeneratorTable gen;
 };
 
 namespace {
 
-constexpr size_t VB_SLAB_BYTES = (size_t)1 << 30;     // bound of the variable-base slabs of one chunk together
-constexpr size_t SLAB_KEEP_BYTES = (size_t)64 << 20;  // pooled buffers above this are released when an entry point returns
 constexpr int VB_W = 4;                               // gh_batch_mul's default window
 constexpr int BH_ENTRIES = 4;                         // {1, 2, 3, 4} g
-constexpr int NPHASES = 7;
-enum { PH_UPLOAD, PH_GROUP_HASH, PH_FIXED_BASE, PH_VARIABLE_BASE, PH_NORMALISE, PH_HASH, PH_FINISH };
-float g_phase_ms[NPHASES];
-float g_total_ms = 0;
+enum { PH_UPLOAD, PH_GROUP_HASH, PH_FIXED_BASE, PH_VARIABLE_BASE, PH_NORMALISE, PH_HASH, PH_FINISH, NPHASES };
+Timing g_tm{NPHASES};
 
 // ---------------------------------------------------------------------------------------------------- Bowe-Hopwood
 template <class C>
@@ -201,12 +191,6 @@ __global__ void __launch_bounds__(256) verdict_kernel(const uint64_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-template <class C> Fp curve_b() {
-    typedef typename Scheme<C>::PF PF;
-    static const uint64_t b4[12] = GH_MNT4753_G1_B0_M_64, b6[12] = GH_MNT6753_G1_B0_M_64;
-    return fp_from_abi<PF>((const uint32_t*)(std::is_same<C, Mnt6G1>::value ? b6 : b4));
-}
-
 // the generators' table on the device, on first use
 template <class C> int bh_ensure(gh_bh* b) {
     if (b->d_tab) return GH_OK;
@@ -249,37 +233,13 @@ template <class C> int bh_launch(gh_bh* b, const uint8_t* d_in, size_t stride, s
     return GH_OK;
 }
 
-constexpr size_t VB_ROW_BYTES = (size_t)VbWindow<VB_W>::E * SLOTS_PER_ENTRY * NL * 4;   // one row of one slab
-// rows per chunk: `slabs` slabs of a chunk stay below VB_SLAB_BYTES together
-size_t vb_chunk(size_t n, int slabs) {
-    return std::min(n, std::max<size_t>(BLOCK, (VB_SLAB_BYTES / (VB_ROW_BYTES * slabs)) / BLOCK * BLOCK));
-}
-
-// one table of (+-) P per row, then out[j][i] = k[j]_i (+-) P_i for each of the `count` scalar vectors, on g.stream
-template <class C> int vb_single(const void* d_xy, const uint8_t* d_inf, int negate, const uint32_t* const* d_k, Proj<C>* const* d_out,
-                                 int count, size_t n) {
-    const size_t chunk = vb_chunk(n, 1);
-    uint32_t* slab = nullptr;
-    if (int rc = gh_rt::pool_get("ecvrf_slab", chunk * VB_ROW_BYTES, (void**)&slab)) return rc;
-    for (size_t r0 = 0; r0 < n; r0 += chunk) {
-        const size_t cnt = std::min(chunk, n - r0);
-        GH_LAUNCH((vb_table_kernel<C, VB_W>), dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_xy, d_inf, r0, cnt,
-                  negate, slab);
-        for (int j = 0; j < count; j++)
-            GH_LAUNCH((vb_mul_kernel<C, VB_W>), dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)slab, d_k[j], d_inf, r0,
-                      cnt, d_out[j]);
-    }
-    HIPCHK(hipGetLastError());
-    return GH_OK;
-}
-
 // out[i] = k1_i (+-) P1_i + k2_i (+-) P2_i, on g.stream
 template <class C> int vb_joint(const void* d_xy1, const uint8_t* d_inf1, int neg1, const uint32_t* d_k1, const void* d_xy2,
                                 const uint8_t* d_inf2, int neg2, const uint32_t* d_k2, size_t n, Proj<C>* d_out) {
-    const size_t chunk = vb_chunk(n, 2);
+    const size_t chunk = vb_chunk<VB_W>(n, 2);
     uint32_t *slab1 = nullptr, *slab2 = nullptr;
-    if (int rc = gh_rt::pool_get("ecvrf_slab", chunk * VB_ROW_BYTES, (void**)&slab1)) return rc;
-    if (int rc = gh_rt::pool_get("ecvrf_slab2", chunk * VB_ROW_BYTES, (void**)&slab2)) return rc;
+    if (int rc = gh_rt::pool_get("vb_slab", chunk * vb_row_bytes<VB_W>(), (void**)&slab1)) return rc;
+    if (int rc = gh_rt::pool_get("vb_slab2", chunk * vb_row_bytes<VB_W>(), (void**)&slab2)) return rc;
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t cnt = std::min(chunk, n - r0);
         GH_LAUNCH((vb_table_kernel<C, VB_W>), dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_xy1, d_inf1, r0, cnt,
@@ -293,24 +253,7 @@ template <class C> int vb_joint(const void* d_xy1, const uint8_t* d_inf1, int ne
     return GH_OK;
 }
 
-struct Trim {
-    ~Trim() {
-        // every pooled buffer of this unit (pool names are matched as prefixes: "ecvrf_slab" covers "ecvrf_slab2")
-        bool synced = false;
-        for (const char* b : {"ecvrf_slab", "ecvrf_slab2", "ecvrf_in", "ecvrf_msg", "ecvrf_msgint", "ecvrf_pk", "ecvrf_pkinf", "ecvrf_gm",
-                              "ecvrf_gminf", "ecvrf_gamma", "ecvrf_gammainf", "ecvrf_cs", "ecvrf_k", "ecvrf_p", "ecvrf_zp", "ecvrf_xy",
-                              "ecvrf_inf", "ecvrf_rows", "ecvrf_h", "ecvrf_st", "ecvrf_ok"})
-            if (gh_rt::pool_cap(b) > SLAB_KEEP_BYTES) {
-                if (!synced) (void)hipStreamSynchronize(g.stream);   // an error return may leave kernels in flight
-                synced = true;
-                gh_rt::pool_release(b);
-            }
-        gh_rt::poseidon_trim_slab();
-    }
-};
-
 bool valid(const gh_bh* h) { return h && h->magic == 0x67684268u; }
-bool valid(const gh_ecvrf* h) { return h && h->magic == 0x67685672u; }
 
 // mh = BH(to_bytes(m_0) || ... ) of the Montgomery message rows on the device, normalised: x || y rows (n x 24 words) and infinity
 template <class C> int message_on_curve(gh_bh* b, const uint64_t* d_msg, size_t n, size_t len, uint32_t* d_mint, Proj<C>* d_p, Fp* d_zp,
@@ -319,8 +262,7 @@ template <class C> int message_on_curve(gh_bh* b, const uint64_t* d_msg, size_t 
     if (n * len) GH_LAUNCH((mont_to_int_kernel<PF>), dim3(blocks(n * len, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_msg, n * len, d_mint,
                            (uint8_t*)nullptr);
     if (int rc = bh_launch<C>(b, (const uint8_t*)d_mint, len * 96, len * 96, n, d_p)) return rc;
-    GH_LAUNCH((normalize_kernel<C>), dim3(blocks(blocks(n, NORM_RUN), BLOCK)), dim3(BLOCK), 0, g.stream, d_p, (const Proj<C>*)nullptr, n,
-              d_zp, (uint32_t*)d_mh, (size_t)48, (size_t)0, d_mhinf);
+    if (int rc = launch_normalize<C>(d_p, nullptr, n, d_zp, d_mh, 48, 0, d_mhinf)) return rc;
     HIPCHK(hipGetLastError());
     return GH_OK;
 }
@@ -330,25 +272,21 @@ template <class C> int run_bh_hash(gh_bh* b, const uint8_t* input, size_t n, siz
     Proj<C>* d_p;
     Fp* d_zp;
     uint64_t* d_xy;
-    int rc = dbuf("ecvrf_in", n * nbytes, &d_in);
-    if (!rc) rc = dbuf("ecvrf_p", n, &d_p);
-    if (!rc) rc = dbuf("ecvrf_zp", n, &d_zp);
-    if (!rc) rc = dbuf("ecvrf_xy", n * 24, &d_xy);
-    if (!rc) rc = dbuf("ecvrf_inf", n, &d_inf);
+    int rc = dbuf("vb_in", n * nbytes, &d_in);
+    if (!rc) rc = dbuf("vb_p", n, &d_p);
+    if (!rc) rc = dbuf("vb_zp", n, &d_zp);
+    if (!rc) rc = dbuf("vb_xy", n * 24, &d_xy);
+    if (!rc) rc = dbuf("vb_inf", n, &d_inf);
     if (rc || (rc = up(d_in, input, n * nbytes)) || (rc = bh_ensure<C>(b))) return rc;
     HIPCHK(hipEventRecord(g.ev[0], g.stream));
     if ((rc = bh_launch<C>(b, d_in, nbytes, nbytes, n, d_p))) return rc;
     HIPCHK(hipEventRecord(g.ev[1], g.stream));
-    GH_LAUNCH((normalize_kernel<C>), dim3(blocks(blocks(n, NORM_RUN), BLOCK)), dim3(BLOCK), 0, g.stream, d_p, (const Proj<C>*)nullptr, n,
-              d_zp, (uint32_t*)d_xy, (size_t)48, (size_t)0, d_inf);
+    if ((rc = launch_normalize<C>(d_p, nullptr, n, d_zp, d_xy, 48, 0, d_inf))) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_xy, d_xy, n * 192, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipMemcpyAsync(out_inf, d_inf, n, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
-    for (int i = 0; i < NPHASES; i++) g_phase_ms[i] = 0;
-    HIPCHK(hipEventElapsedTime(&g_phase_ms[PH_GROUP_HASH], g.ev[0], g.ev[1]));   // the hash kernel
-    g_total_ms = g_phase_ms[PH_GROUP_HASH];
-    return GH_OK;
+    return g_tm.single(PH_GROUP_HASH, g.ev[0], g.ev[1]);     // the hash kernel
 }
 
 template <class C> int run_double_mul(const uint64_t* xy1, const uint8_t* inf1, const uint64_t* k1, const uint64_t* xy2, const uint8_t* inf2,
@@ -356,11 +294,11 @@ template <class C> int run_double_mul(const uint64_t* xy1, const uint8_t* inf1, 
     uint64_t *d_xy, *d_k, *d_out;
     uint8_t* d_inf = nullptr;
     Proj<C>* d_p;
-    int rc = dbuf("ecvrf_pk", n * 48, &d_xy);
-    if (!rc) rc = dbuf("ecvrf_k", n * 24, &d_k);
-    if (!rc) rc = dbuf("ecvrf_p", n, &d_p);
-    if (!rc) rc = dbuf("ecvrf_rows", n * 36, &d_out);
-    if (!rc && (inf1 || inf2)) rc = dbuf("ecvrf_inf", 2 * n, &d_inf);
+    int rc = dbuf("vb_pk", n * 48, &d_xy);
+    if (!rc) rc = dbuf("vb_k", n * 24, &d_k);
+    if (!rc) rc = dbuf("vb_p", n, &d_p);
+    if (!rc) rc = dbuf("vb_rows", n * 36, &d_out);
+    if (!rc && (inf1 || inf2)) rc = dbuf("vb_inf", 2 * n, &d_inf);
     if (rc || (rc = up(d_xy, xy1, n * 24)) || (rc = up(d_xy + n * 24, xy2, n * 24)) || (rc = up(d_k, k1, n * 12)) ||
         (rc = up(d_k + n * 12, k2, n * 12)))
         return rc;
@@ -377,36 +315,7 @@ template <class C> int run_double_mul(const uint64_t* xy1, const uint8_t* inf1, 
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_xyz, d_out, n * 288, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
-    for (int i = 0; i < NPHASES; i++) g_phase_ms[i] = 0;
-    HIPCHK(hipEventElapsedTime(&g_phase_ms[PH_VARIABLE_BASE], g.ev[0], g.ev[1]));   // the tables and the joint kernel
-    g_total_ms = g_phase_ms[PH_VARIABLE_BASE];
-    return GH_OK;
-}
-
-template <class C> int run_public_keys(gh_ecvrf* h, const uint64_t* sk, size_t n, uint64_t* out_xy, uint8_t* out_inf) {
-    typedef typename Scheme<C>::PS PS;
-    if (int rc = generator_table(h->curve, h->window, n, &h->table, &h->table_window)) return rc;
-    uint64_t *d_sk, *d_xy;
-    uint32_t* d_k;
-    Proj<C>* d_p;
-    Fp* d_zp;
-    uint8_t* d_inf;
-    int rc = dbuf("ecvrf_in", n * 12, &d_sk);
-    if (!rc) rc = dbuf("ecvrf_k", n * 24, &d_k);
-    if (!rc) rc = dbuf("ecvrf_p", n, &d_p);
-    if (!rc) rc = dbuf("ecvrf_zp", n, &d_zp);
-    if (!rc) rc = dbuf("ecvrf_xy", n * 24, &d_xy);
-    if (!rc) rc = dbuf("ecvrf_inf", n, &d_inf);
-    if (rc || (rc = up(d_sk, sk, n * 12))) return rc;
-    GH_LAUNCH((mont_to_int_kernel<PS>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_sk, n, d_k, (uint8_t*)nullptr);
-    if ((rc = gh_rt::fixed_table_sums(h->table, d_k, n, d_p))) return rc;
-    GH_LAUNCH((normalize_kernel<C>), dim3(blocks(blocks(n, NORM_RUN), BLOCK)), dim3(BLOCK), 0, g.stream, d_p, (const Proj<C>*)nullptr, n,
-              d_zp, (uint32_t*)d_xy, (size_t)48, (size_t)0, d_inf);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out_xy, d_xy, n * 192, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipMemcpyAsync(out_inf, d_inf, n, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    return GH_OK;
+    return g_tm.single(PH_VARIABLE_BASE, g.ev[0], g.ev[1]);  // the tables and the joint kernel
 }
 
 // prove: mh = BH(m); gamma = sk mh and b = r mh from ONE table of mh; a = r G on the fixed-base path; c = H(m || pk.x || a.x || b.x);
@@ -416,34 +325,34 @@ template <class C> int run_prove(gh_ecvrf* h, const uint64_t* sk, const uint64_t
                                  uint8_t* out_status) {
     typedef typename Scheme<C>::PF PF;
     typedef typename Scheme<C>::PS PS;
-    if (int rc = generator_table(h->curve, h->window, n, &h->table, &h->table_window)) return rc;
+    if (int rc = h->gen.ensure(h->curve, n)) return rc;
     const size_t rw = (len + 3) * 12;
     uint64_t *d_sk, *d_nonce, *d_pk, *d_msg, *d_mh, *d_xy3, *d_rows, *d_c, *d_cs;
     uint8_t *d_pkinf, *d_mhinf, *d_inf3, *d_st;
     uint32_t *d_mint, *d_ski, *d_ri;
     Proj<C>* d_p3;                                           // a | b | gamma
     Fp* d_zp;
-    int rc = dbuf("ecvrf_in", n * 24, &d_sk);
-    if (!rc) rc = dbuf("ecvrf_pk", n * 24, &d_pk);
-    if (!rc) rc = dbuf("ecvrf_pkinf", n, &d_pkinf);
-    if (!rc) rc = dbuf("ecvrf_msg", n * len * 12, &d_msg);
-    if (!rc) rc = dbuf("ecvrf_msgint", n * len * 24, &d_mint);
-    if (!rc) rc = dbuf("ecvrf_gm", n * 24, &d_mh);
-    if (!rc) rc = dbuf("ecvrf_gminf", n, &d_mhinf);
-    if (!rc) rc = dbuf("ecvrf_k", n * 48, &d_ski);
-    if (!rc) rc = dbuf("ecvrf_p", 3 * n, &d_p3);
-    if (!rc) rc = dbuf("ecvrf_zp", 3 * n, &d_zp);
-    if (!rc) rc = dbuf("ecvrf_xy", 3 * n * 24, &d_xy3);
-    if (!rc) rc = dbuf("ecvrf_inf", 3 * n, &d_inf3);
-    if (!rc) rc = dbuf("ecvrf_rows", n * rw, &d_rows);
-    if (!rc) rc = dbuf("ecvrf_h", n * 12, &d_c);
-    if (!rc) rc = dbuf("ecvrf_cs", n * 24, &d_cs);
-    if (!rc) rc = dbuf("ecvrf_st", n, &d_st);
+    int rc = dbuf("vb_in", n * 24, &d_sk);
+    if (!rc) rc = dbuf("vb_pk", n * 24, &d_pk);
+    if (!rc) rc = dbuf("vb_pkinf", n, &d_pkinf);
+    if (!rc) rc = dbuf("vb_msg", n * len * 12, &d_msg);
+    if (!rc) rc = dbuf("vb_msgint", n * len * 24, &d_mint);
+    if (!rc) rc = dbuf("vb_gm", n * 24, &d_mh);
+    if (!rc) rc = dbuf("vb_gminf", n, &d_mhinf);
+    if (!rc) rc = dbuf("vb_k", n * 48, &d_ski);
+    if (!rc) rc = dbuf("vb_p", 3 * n, &d_p3);
+    if (!rc) rc = dbuf("vb_zp", 3 * n, &d_zp);
+    if (!rc) rc = dbuf("vb_xy", 3 * n * 24, &d_xy3);
+    if (!rc) rc = dbuf("vb_inf", 3 * n, &d_inf3);
+    if (!rc) rc = dbuf("vb_rows", n * rw, &d_rows);
+    if (!rc) rc = dbuf("vb_h", n * 12, &d_c);
+    if (!rc) rc = dbuf("vb_cs", n * 24, &d_cs);
+    if (!rc) rc = dbuf("vb_st", n, &d_st);
     if (rc) return rc;
     d_nonce = d_sk + n * 12;
     d_ri = d_ski + n * 24;
     Proj<C>*d_a = d_p3, *d_b = d_p3 + n, *d_g = d_p3 + 2 * n;
-    Phases ph{g_phase_ms, NPHASES, &g_total_ms};
+    Phases ph{g_tm};
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_sk, sk, n * 12)) || (rc = up(d_nonce, nonce, n * 12)) || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_pkinf, pk_inf, n)) ||
         (rc = up(d_msg, msg, n * len * 12)) || (rc = ph.mark()))
@@ -451,12 +360,11 @@ template <class C> int run_prove(gh_ecvrf* h, const uint64_t* sk, const uint64_t
     if ((rc = message_on_curve<C>(h->bh, d_msg, n, len, d_mint, d_a, d_zp, d_mh, d_mhinf)) || (rc = ph.mark())) return rc;
     GH_LAUNCH((mont_to_int_kernel<PS>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_sk, n, d_ski, (uint8_t*)nullptr);
     GH_LAUNCH((mont_to_int_kernel<PS>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_nonce, n, d_ri, d_st);
-    if ((rc = gh_rt::fixed_table_sums(h->table, d_ri, n, d_a)) || (rc = ph.mark())) return rc;                       // a = r G
+    if ((rc = gh_rt::fixed_table_sums(h->gen.table, d_ri, n, d_a)) || (rc = ph.mark())) return rc;                       // a = r G
     const uint32_t* ks[2] = {d_ski, d_ri};
     Proj<C>* outs[2] = {d_g, d_b};
-    if ((rc = vb_single<C>(d_mh, d_mhinf, 0, ks, outs, 2, n)) || (rc = ph.mark())) return rc;                        // gamma, b
-    GH_LAUNCH((normalize_kernel<C>), dim3(blocks(blocks(3 * n, NORM_RUN), BLOCK)), dim3(BLOCK), 0, g.stream, d_p3, (const Proj<C>*)nullptr,
-              3 * n, d_zp, (uint32_t*)d_xy3, (size_t)48, (size_t)0, d_inf3);
+    if ((rc = vb_single<C, VB_W>(d_mh, d_mhinf, 0, ks, outs, 2, n)) || (rc = ph.mark())) return rc;                        // gamma, b
+    if ((rc = launch_normalize<C>(d_p3, nullptr, 3 * n, d_zp, d_xy3, 48, 0, d_inf3))) return rc;
     GH_LAUNCH(c_rows_kernel, dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)d_msg, (const uint64_t*)d_pk, (const uint8_t*)d_pkinf,
               (const uint64_t*)d_xy3, (const uint64_t*)(d_xy3 + n * 24), n, len, d_rows);
     HIPCHK(hipGetLastError());
@@ -480,35 +388,35 @@ template <class C> int run_proof_to_hash(gh_ecvrf* h, const uint64_t* pk_xy, con
                                          const uint64_t* gamma_xy, const uint8_t* gamma_inf, const uint64_t* cs, uint64_t* out_hash,
                                          uint8_t* out_status) {
     typedef typename Scheme<C>::PF PF;
-    if (int rc = generator_table(h->curve, h->window, n, &h->table, &h->table_window)) return rc;
+    if (int rc = h->gen.ensure(h->curve, n)) return rc;
     const size_t rw = (len + 3) * 12;
     uint64_t *d_cs, *d_pk, *d_gm, *d_msg, *d_mh, *d_xy2, *d_rows, *d_c2, *d_out;
     uint8_t *d_pkinf, *d_gminf, *d_mhinf, *d_st, *d_ok;
     uint32_t *d_mint, *d_ci;
     Proj<C>* d_p3;                                           // s G | c (-pk) | v
     Fp* d_zp;
-    int rc = dbuf("ecvrf_cs", n * 24, &d_cs);
-    if (!rc) rc = dbuf("ecvrf_pk", n * 24, &d_pk);
-    if (!rc) rc = dbuf("ecvrf_pkinf", n, &d_pkinf);
-    if (!rc) rc = dbuf("ecvrf_gamma", n * 24, &d_gm);
-    if (!rc) rc = dbuf("ecvrf_gammainf", n, &d_gminf);
-    if (!rc) rc = dbuf("ecvrf_msg", n * len * 12, &d_msg);
-    if (!rc) rc = dbuf("ecvrf_msgint", n * len * 24, &d_mint);
-    if (!rc) rc = dbuf("ecvrf_gm", n * 24, &d_mh);
-    if (!rc) rc = dbuf("ecvrf_gminf", n, &d_mhinf);
-    if (!rc) rc = dbuf("ecvrf_k", n * 48, &d_ci);
-    if (!rc) rc = dbuf("ecvrf_p", 3 * n, &d_p3);
-    if (!rc) rc = dbuf("ecvrf_zp", 2 * n, &d_zp);
-    if (!rc) rc = dbuf("ecvrf_xy", 2 * n * 24, &d_xy2);
-    if (!rc) rc = dbuf("ecvrf_rows", n * rw, &d_rows);
-    if (!rc) rc = dbuf("ecvrf_h", n * 24, &d_c2);
-    if (!rc) rc = dbuf("ecvrf_st", n, &d_st);
-    if (!rc) rc = dbuf("ecvrf_ok", n, &d_ok);
+    int rc = dbuf("vb_cs", n * 24, &d_cs);
+    if (!rc) rc = dbuf("vb_pk", n * 24, &d_pk);
+    if (!rc) rc = dbuf("vb_pkinf", n, &d_pkinf);
+    if (!rc) rc = dbuf("vb_gamma", n * 24, &d_gm);
+    if (!rc) rc = dbuf("vb_gammainf", n, &d_gminf);
+    if (!rc) rc = dbuf("vb_msg", n * len * 12, &d_msg);
+    if (!rc) rc = dbuf("vb_msgint", n * len * 24, &d_mint);
+    if (!rc) rc = dbuf("vb_gm", n * 24, &d_mh);
+    if (!rc) rc = dbuf("vb_gminf", n, &d_mhinf);
+    if (!rc) rc = dbuf("vb_k", n * 48, &d_ci);
+    if (!rc) rc = dbuf("vb_p", 3 * n, &d_p3);
+    if (!rc) rc = dbuf("vb_zp", 2 * n, &d_zp);
+    if (!rc) rc = dbuf("vb_xy", 2 * n * 24, &d_xy2);
+    if (!rc) rc = dbuf("vb_rows", n * rw, &d_rows);
+    if (!rc) rc = dbuf("vb_h", n * 24, &d_c2);
+    if (!rc) rc = dbuf("vb_st", n, &d_st);
+    if (!rc) rc = dbuf("vb_ok", n, &d_ok);
     if (rc) return rc;
     uint32_t* d_si = d_ci + n * 24;
     d_out = d_c2 + n * 12;
     Proj<C>*d_sg = d_p3, *d_cpk = d_p3 + n, *d_v = d_p3 + 2 * n;
-    Phases ph{g_phase_ms, NPHASES, &g_total_ms};
+    Phases ph{g_tm};
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_cs, cs, n * 24)) || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_pkinf, pk_inf, n)) || (rc = up(d_gm, gamma_xy, n * 24)) ||
         (rc = up(d_gminf, gamma_inf, n)) || (rc = up(d_msg, msg, n * len * 12)) || (rc = ph.mark()))
@@ -517,16 +425,15 @@ template <class C> int run_proof_to_hash(gh_ecvrf* h, const uint64_t* pk_xy, con
     GH_LAUNCH((on_curve_kernel<C>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_gm, (const uint8_t*)d_gminf, n,
               curve_b<C>(), d_ok);
     if ((rc = message_on_curve<C>(h->bh, d_msg, n, len, d_mint, d_sg, d_zp, d_mh, d_mhinf)) || (rc = ph.mark())) return rc;
-    if ((rc = gh_rt::fixed_table_sums(h->table, d_si, n, d_sg)) || (rc = ph.mark())) return rc;                      // s G
+    if ((rc = gh_rt::fixed_table_sums(h->gen.table, d_si, n, d_sg)) || (rc = ph.mark())) return rc;                      // s G
     const uint32_t* ks[1] = {d_ci};
     Proj<C>* outs[1] = {d_cpk};
-    if ((rc = vb_single<C>(d_pk, d_pkinf, 1, ks, outs, 1, n)) ||                                                      // c (-pk)
+    if ((rc = vb_single<C, VB_W>(d_pk, d_pkinf, 1, ks, outs, 1, n)) ||                                                      // c (-pk)
         (rc = vb_joint<C>(d_mh, d_mhinf, 0, d_si, d_gm, d_gminf, 1, d_ci, n, d_v)) || (rc = ph.mark()))              // s mh + c (-gamma)
         return rc;
-    GH_LAUNCH((normalize_kernel<C>), dim3(blocks(blocks(n, NORM_RUN), BLOCK)), dim3(BLOCK), 0, g.stream, d_sg, (const Proj<C>*)d_cpk, n, d_zp,
-              (uint32_t*)d_xy2, (size_t)48, (size_t)0, (uint8_t*)nullptr);                                         // u
-    GH_LAUNCH((normalize_kernel<C>), dim3(blocks(blocks(n, NORM_RUN), BLOCK)), dim3(BLOCK), 0, g.stream, d_v, (const Proj<C>*)nullptr, n,
-              d_zp + n, (uint32_t*)(d_xy2 + n * 24), (size_t)48, (size_t)0, (uint8_t*)nullptr);                     // v
+    if ((rc = launch_normalize<C>(d_sg, d_cpk, n, d_zp, d_xy2, 48, 0, nullptr)) ||                                  // u
+        (rc = launch_normalize<C>(d_v, nullptr, n, d_zp + n, d_xy2 + n * 24, 48, 0, nullptr)))                    // v
+        return rc;
     GH_LAUNCH(c_rows_kernel, dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)d_msg, (const uint64_t*)d_pk, (const uint8_t*)d_pkinf,
               (const uint64_t*)d_xy2, (const uint64_t*)(d_xy2 + n * 24), n, len, d_rows);
     HIPCHK(hipGetLastError());
@@ -545,21 +452,6 @@ template <class C> int run_proof_to_hash(gh_ecvrf* h, const uint64_t* pk_xy, con
     return ph.finish();
 }
 
-template <class C> int run_keyverify(const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n, uint8_t* out_ok) {
-    uint64_t* d_pk;
-    uint8_t *d_inf, *d_ok;
-    int rc = dbuf("ecvrf_pk", n * 24, &d_pk);
-    if (!rc) rc = dbuf("ecvrf_pkinf", n, &d_inf);
-    if (!rc) rc = dbuf("ecvrf_ok", n, &d_ok);
-    if (rc || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_inf, pk_inf, n))) return rc;
-    GH_LAUNCH((on_curve_kernel<C>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_pk, (const uint8_t*)d_inf, n, curve_b<C>(),
-              d_ok);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out_ok, d_ok, n, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    return GH_OK;
-}
-
 // y^2 == x^3 + a x + b on the host (the generators of gh_bh_create)
 template <class C> bool on_curve_host(const uint64_t* xy) {
     typedef typename Scheme<C>::PF PF;
@@ -569,25 +461,17 @@ template <class C> bool on_curve_host(const uint64_t* xy) {
     return F::eq(F::sqr(y), rhs);
 }
 
-bool g1(gh_curve_t c) { return c == GH_MNT6753_G1 || c == GH_MNT4753_G1; }
-template <class C> bool data_below(const uint64_t* x, size_t count) { return all_below<typename Scheme<C>::PF>(x, count); }
-template <class C> bool scalar_below(const uint64_t* x, size_t count) { return all_below<typename Scheme<C>::PS>(x, count); }
-
-// the checks prove / proof_to_hash / keyverify share: sizes, the group hash's capacity, the moduli of pk and the message
+// the checks prove / proof_to_hash share: sizes, the group hash's capacity, the moduli of pk and the message
 template <class C> int check_common(const gh_ecvrf* h, const uint64_t* pk_xy, const uint64_t* msg, size_t n, size_t len) {
-    size_t nm = 0, b = 0;
-    if (mul_overflows(n, len, &nm) || mul_overflows(nm, 96 * 4, &b) || mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
-    if (len && len > h->bh->num_windows * h->bh->window_size / 256) {
+    if (len > h->bh->num_windows * h->bh->window_size / 256) {
         g_err = "the message is longer than the group hash takes (768 len > 3 num_windows window_size)";
         return GH_E_BAD_ARG;
     }
-    if (!data_below<C>(pk_xy, 2 * n)) { g_err = "a public-key coordinate is not below the modulus"; return GH_E_BAD_ARG; }
-    if (msg && !data_below<C>(msg, nm)) { g_err = "a message element is not below the modulus"; return GH_E_BAD_ARG; }
-    return GH_OK;
+    return check_rows<C>(pk_xy, msg, n, len);
 }
 
 int checked(gh_ecvrf* h) {
-    if (!valid(h)) { g_err = "not an EC-VRF handle"; return GH_E_BAD_HANDLE; }
+    if (!h || h->magic != 0x67685672u) { g_err = "not an EC-VRF handle"; return GH_E_BAD_HANDLE; }
     return GH_OK;
 }
 
@@ -596,28 +480,22 @@ int checked(gh_ecvrf* h) {
 // ---------------------------------------------------------------------------------------------------- C ABI
 using namespace gh_rt;
 
-#define GH_ECVRF_DISPATCH(curve, fn, ...) ((curve) == GH_MNT6753_G1 ? fn<Mnt6G1>(__VA_ARGS__) : fn<Mnt4G1>(__VA_ARGS__))
-
 extern "C" {
 
 int gh_bh_create(gh_curve_t curve, const uint64_t* gen_xy, const uint8_t* gen_inf, size_t num_windows, size_t window_size, gh_bh_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
     *out = nullptr;
-    if (!g1(curve)) { g_err = "the Bowe-Hopwood group must be a G1 curve"; return GH_E_BAD_ARG; }
+    if (!is_g1(curve)) { g_err = "the Bowe-Hopwood group must be a G1 curve"; return GH_E_BAD_ARG; }
     size_t ng = 0, b = 0;
     if (!num_windows || !window_size || mul_overflows(num_windows, window_size, &ng) || mul_overflows(ng, 192 * 8, &b)) {
         g_err = "num_windows and window_size must be positive and their product small enough";
         return GH_E_BAD_ARG;
     }
     if (!gen_xy) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    const bool m6 = curve == GH_MNT6753_G1;
-    if (!(m6 ? data_below<Mnt6G1>(gen_xy, 2 * ng) : data_below<Mnt4G1>(gen_xy, 2 * ng))) {
-        g_err = "a generator coordinate is not below the modulus";
-        return GH_E_BAD_ARG;
-    }
+    if (!GH_G1_DISPATCH(curve, data_below, gen_xy, 2 * ng)) { g_err = "a generator coordinate is not below the modulus"; return GH_E_BAD_ARG; }
     for (size_t i = 0; i < ng; i++)
-        if (!(gen_inf && gen_inf[i]) && !(m6 ? on_curve_host<Mnt6G1>(gen_xy + 24 * i) : on_curve_host<Mnt4G1>(gen_xy + 24 * i))) {
+        if (!(gen_inf && gen_inf[i]) && !GH_G1_DISPATCH(curve, on_curve_host, gen_xy + 24 * i)) {
             g_err = "a generator is not on the curve";
             return GH_E_BAD_ARG;
         }
@@ -660,47 +538,36 @@ int gh_bh_hash(gh_bh_t h, const uint8_t* input, size_t n, size_t nbytes, uint64_
     }
     if (n == 0) return GH_OK;
     if (int rc = ensure_init()) return rc;
-    return GH_ECVRF_DISPATCH(h->curve, run_bh_hash, h, input, n, nbytes, out_xy, out_inf);
+    return GH_G1_DISPATCH(h->curve, run_bh_hash, h, input, n, nbytes, out_xy, out_inf);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_batch_double_mul(gh_curve_t curve, const uint64_t* xy1, const uint8_t* inf1, const uint64_t* k1, const uint64_t* xy2, const uint8_t* inf2,
                         const uint64_t* k2, size_t n, uint64_t* out_xyz) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     Trim trim_;
-    if (curve == GH_MNT4753_G2 || curve == GH_MNT6753_G2) { g_err = "gh_batch_double_mul: G1 curves only"; return GH_E_UNSUPPORTED; }
-    if (!g1(curve)) { g_err = "unknown curve id"; return GH_E_BAD_ARG; }
-    if (n && (!xy1 || !k1 || !xy2 || !k2 || !out_xyz)) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    size_t b;
-    if (mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
-    const bool m6 = curve == GH_MNT6753_G1;
-    if (!(m6 ? data_below<Mnt6G1>(xy1, 2 * n) && data_below<Mnt6G1>(xy2, 2 * n) : data_below<Mnt4G1>(xy1, 2 * n) && data_below<Mnt4G1>(xy2, 2 * n))) {
+    if (int rc = check_batch("gh_batch_double_mul", curve, n, xy1 && k1 && xy2 && k2 && out_xyz)) return rc;
+    if (!GH_G1_DISPATCH(curve, data_below, xy1, 2 * n) || !GH_G1_DISPATCH(curve, data_below, xy2, 2 * n)) {
         g_err = "a base coordinate is not below the modulus";
         return GH_E_BAD_ARG;
     }
-    for (size_t i = 0; i < n; i++)
-        if ((k1[12 * i + 11] >> 49) || (k2[12 * i + 11] >> 49)) { g_err = "a scalar is not below 2^753"; return GH_E_BAD_ARG; }
+    if (!below_2_753(k1, n) || !below_2_753(k2, n)) { g_err = "a scalar is not below 2^753"; return GH_E_BAD_ARG; }
     if (n == 0) return GH_OK;
     if (int rc = ensure_init()) return rc;
-    return GH_ECVRF_DISPATCH(curve, run_double_mul, xy1, inf1, k1, xy2, inf2, k2, n, out_xyz);
+    return GH_G1_DISPATCH(curve, run_double_mul, xy1, inf1, k1, xy2, inf2, k2, n, out_xyz);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_ecvrf_create(gh_curve_t curve, gh_poseidon_t hash, gh_bh_t group_hash, int window, gh_ecvrf_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     if (!hash || !group_hash || !out) { g_err = "null argument"; return GH_E_BAD_ARG; }
     *out = nullptr;
-    if (!g1(curve)) { g_err = "the EC-VRF group must be a G1 curve"; return GH_E_BAD_ARG; }
-    if (window < 0 || window > 22) { g_err = "fixed-base window must be 0 or in [1, 22]"; return GH_E_BAD_ARG; }
-    gh_field_t f;
-    if (poseidon_field(hash, &f)) { g_err = "not a Poseidon handle"; return GH_E_BAD_ARG; }
-    const gh_field_t need = curve == GH_MNT6753_G1 ? Scheme<Mnt6G1>::field : Scheme<Mnt4G1>::field;
-    if (f != need) { g_err = "the hash's field is not the curve's base field"; return GH_E_BAD_ARG; }
+    if (int rc = check_create("EC-VRF", curve, hash, window)) return rc;
     if (!valid(group_hash)) { g_err = "not a Bowe-Hopwood handle"; return GH_E_BAD_ARG; }
     if (group_hash->curve != curve) { g_err = "the group hash is over another curve"; return GH_E_BAD_ARG; }
     auto* h = new gh_ecvrf();
     h->curve = curve;
     h->hash = hash;
     h->bh = group_hash;
-    h->window = window;
+    h->gen.window = window;
     *out = h;
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
@@ -708,8 +575,8 @@ int gh_ecvrf_create(gh_curve_t curve, gh_poseidon_t hash, gh_bh_t group_hash, in
 int gh_ecvrf_free(gh_ecvrf_t h) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     if (!h) return GH_OK;
-    if (!valid(h)) { g_err = "not an EC-VRF handle"; return GH_E_BAD_HANDLE; }
-    fixed_table_destroy(h->table);
+    if (int rc = checked(h)) return rc;
+    h->gen.destroy();
     h->magic = 0;
     delete h;
     return GH_OK;
@@ -719,14 +586,7 @@ int gh_ecvrf_public_keys(gh_ecvrf_t h, const uint64_t* sk, size_t n, uint64_t* o
     std::lock_guard<std::mutex> lk(api_mutex());
     Trim trim_;
     if (int rc = checked(h)) return rc;
-    if (n && (!sk || !out_pk_xy || !out_pk_inf)) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    size_t b;
-    if (mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
-    const bool m6 = h->curve == GH_MNT6753_G1;
-    if (!(m6 ? scalar_below<Mnt6G1>(sk, n) : scalar_below<Mnt4G1>(sk, n))) { g_err = "a secret key is not below the modulus"; return GH_E_BAD_ARG; }
-    if (n == 0) return GH_OK;
-    if (int rc = ensure_init()) return rc;
-    return GH_ECVRF_DISPATCH(h->curve, run_public_keys, h, sk, n, out_pk_xy, out_pk_inf);
+    return public_keys_api(h->gen, h->curve, sk, n, out_pk_xy, out_pk_inf);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_ecvrf_prove(gh_ecvrf_t h, const uint64_t* sk, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* msg, size_t n, size_t len,
@@ -738,16 +598,14 @@ int gh_ecvrf_prove(gh_ecvrf_t h, const uint64_t* sk, const uint64_t* pk_xy, cons
         g_err = "null argument";
         return GH_E_BAD_ARG;
     }
-    const bool m6 = h->curve == GH_MNT6753_G1;
-    if (int rc = m6 ? check_common<Mnt6G1>(h, pk_xy, len ? msg : nullptr, n, len) : check_common<Mnt4G1>(h, pk_xy, len ? msg : nullptr, n, len))
-        return rc;
-    if (!(m6 ? scalar_below<Mnt6G1>(sk, n) && scalar_below<Mnt6G1>(nonce, n) : scalar_below<Mnt4G1>(sk, n) && scalar_below<Mnt4G1>(nonce, n))) {
+    if (int rc = GH_G1_DISPATCH(h->curve, check_common, h, pk_xy, len ? msg : nullptr, n, len)) return rc;
+    if (!GH_G1_DISPATCH(h->curve, scalar_below, sk, n) || !GH_G1_DISPATCH(h->curve, scalar_below, nonce, n)) {
         g_err = "a secret key or nonce is not below the modulus";
         return GH_E_BAD_ARG;
     }
     if (n == 0) return GH_OK;
     if (int rc = ensure_init()) return rc;
-    return GH_ECVRF_DISPATCH(h->curve, run_prove, h, sk, pk_xy, pk_inf, msg, n, len, nonce, out_gamma_xy, out_gamma_inf, out_cs, out_status);
+    return GH_G1_DISPATCH(h->curve, run_prove, h, sk, pk_xy, pk_inf, msg, n, len, nonce, out_gamma_xy, out_gamma_inf, out_cs, out_status);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_ecvrf_proof_to_hash(gh_ecvrf_t h, const uint64_t* pk_xy, const uint8_t* pk_inf, const uint64_t* msg, size_t n, size_t len,
@@ -759,35 +617,24 @@ int gh_ecvrf_proof_to_hash(gh_ecvrf_t h, const uint64_t* pk_xy, const uint8_t* p
         g_err = "null argument";
         return GH_E_BAD_ARG;
     }
-    const bool m6 = h->curve == GH_MNT6753_G1;
-    if (int rc = m6 ? check_common<Mnt6G1>(h, pk_xy, len ? msg : nullptr, n, len) : check_common<Mnt4G1>(h, pk_xy, len ? msg : nullptr, n, len))
-        return rc;
-    if (!(m6 ? data_below<Mnt6G1>(gamma_xy, 2 * n) : data_below<Mnt4G1>(gamma_xy, 2 * n))) { g_err = "a gamma coordinate is not below the modulus"; return GH_E_BAD_ARG; }
-    if (!(m6 ? data_below<Mnt6G1>(cs, 2 * n) : data_below<Mnt4G1>(cs, 2 * n))) { g_err = "a proof element is not below the modulus"; return GH_E_BAD_ARG; }
+    if (int rc = GH_G1_DISPATCH(h->curve, check_common, h, pk_xy, len ? msg : nullptr, n, len)) return rc;
+    if (!GH_G1_DISPATCH(h->curve, data_below, gamma_xy, 2 * n)) { g_err = "a gamma coordinate is not below the modulus"; return GH_E_BAD_ARG; }
+    if (!GH_G1_DISPATCH(h->curve, data_below, cs, 2 * n)) { g_err = "a proof element is not below the modulus"; return GH_E_BAD_ARG; }
     if (n == 0) return GH_OK;
     if (int rc = ensure_init()) return rc;
-    return GH_ECVRF_DISPATCH(h->curve, run_proof_to_hash, h, pk_xy, pk_inf, msg, n, len, gamma_xy, gamma_inf, cs, out_hash, out_status);
+    return GH_G1_DISPATCH(h->curve, run_proof_to_hash, h, pk_xy, pk_inf, msg, n, len, gamma_xy, gamma_inf, cs, out_hash, out_status);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_ecvrf_keyverify(gh_ecvrf_t h, const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n, uint8_t* out_ok) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     Trim trim_;
     if (int rc = checked(h)) return rc;
-    if (n && (!pk_xy || !pk_inf || !out_ok)) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    const bool m6 = h->curve == GH_MNT6753_G1;
-    if (int rc = m6 ? check_common<Mnt6G1>(h, pk_xy, nullptr, n, 0) : check_common<Mnt4G1>(h, pk_xy, nullptr, n, 0)) return rc;
-    if (n == 0) return GH_OK;
-    if (int rc = ensure_init()) return rc;
-    return GH_ECVRF_DISPATCH(h->curve, run_keyverify, pk_xy, pk_inf, n, out_ok);
+    return keyverify_api(h->curve, pk_xy, pk_inf, n, out_ok);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_ecvrf_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if ((!phase_ms && max_phases > 0) || max_phases < 0) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    const int cnt = std::min(max_phases, NPHASES);
-    for (int i = 0; i < cnt; i++) phase_ms[i] = g_phase_ms[i];
-    if (total_ms) *total_ms = g_total_ms;
-    return cnt;
+    return g_tm.copy_out(phase_ms, max_phases, total_ms);
 } catch (...) { return gh_rt::api_exception(); }
 
 }  // extern "C"

@@ -161,6 +161,20 @@ void pool_release(const char* prefix) {
         }
     }
 }
+void pool_trim(const char* prefix, size_t keep_bytes) {
+    const size_t len = strlen(prefix);
+    bool synced = false;
+    for (auto it = g.pool.begin(); it != g.pool.end();) {
+        if (it->first.compare(0, len, prefix) != 0 || it->second.cap <= keep_bytes) {
+            ++it;
+            continue;
+        }
+        if (!synced) (void)hipStreamSynchronize(g.stream);
+        synced = true;
+        (void)hipFree(it->second.p);
+        it = g.pool.erase(it);
+    }
+}
 
 // generic exclusive scan of n u32 on the library stream
 int device_scan(const uint32_t* in, uint32_t* out, size_t n, const char* tmpname, hipStream_t stream) {

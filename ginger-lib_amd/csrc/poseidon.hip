@@ -124,11 +124,8 @@ template <class P, int K, bool SLAB> int launch_k(const gh_poseidon* h, const vo
 
 // The slab of K = 8 over a full pass is 48 slots x 104 B x num_cus x 512 lanes (654 MB on 256 CUs).  The pool would keep it
 // for the life of the process; every entry point lets go of a slab above 64 MB when it returns (its work is finished then).
-constexpr size_t SLAB_KEEP_BYTES = (size_t)64 << 20;
 struct SlabTrim {
-    ~SlabTrim() {
-        if (gh_rt::pool_cap("poseidon_slab") > SLAB_KEEP_BYTES) gh_rt::pool_release("poseidon_slab");
-    }
+    ~SlabTrim() { gh_rt::pool_trim("poseidon_slab", gh_rt::SLAB_KEEP_BYTES); }
 };
 
 bool force_slab() {

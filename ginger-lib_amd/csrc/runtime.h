@@ -65,6 +65,10 @@ std::mutex& api_mutex();     // the lock every ABI entry point holds (one device
 int pool_get(const char* name, size_t bytes, void** out);
 size_t pool_cap(const char* name);                 // current capacity of a cached buffer (0 if none)
 void pool_release(const char* prefix);             // free every cached buffer whose name starts with prefix ("" = all)
+// Free every cached buffer whose name starts with prefix and whose capacity is above keep_bytes; the others stay.  Waits for
+// g.stream before the first free: the caller may be on an error return with kernels in flight.
+void pool_trim(const char* prefix, size_t keep_bytes);
+constexpr size_t SLAB_KEEP_BYTES = (size_t)64 << 20;   // what Poseidon, Schnorr and EC-VRF entry points trim their buffers to on return
 // the cached buffer `name` of one MSM buffer slot: pool name "name#slot"
 inline std::string slot_name(const char* name, int slot) { return std::string(name) + "#" + std::to_string(slot); }
 template <class T> int slot_buf(const char* name, int slot, size_t bytes, T** out) {
@@ -166,7 +170,7 @@ int sap_witness_map(gh_field_t field, void* d_a, void* d_c, uint32_t log_n, cons
 int batch_inverse(gh_field_t field, void* d_a, size_t n);
 int lagrange_coefficients(gh_field_t field, uint32_t log_n, const uint64_t* tau12, void* d_out);
 
-// ---- lock-held helpers for other units (schnorr.hip); the caller holds api_mutex() and has run ensure_init()
+// ---- lock-held helpers for other units (schnorr.hip, ecvrf.hip); the caller holds api_mutex() and has run ensure_init()
 struct FixedTable;                                 // fixed_base.hip: a window table of one base
 int fixed_table_create(gh_curve_t curve, const uint64_t* g_xyz, size_t scalar_size, int window, FixedTable** out);
 int fixed_table_sums(const FixedTable* t, const void* d_scalars, size_t n, void* d_out_proj);   // on g.stream, internal Proj<C>

@@ -1,6 +1,6 @@
-// vb_kernels.h -- the per-row variable-base kernels and the pipeline kernels that schnorr.hip and ecvrf.hip both instantiate
-// (DESIGN.md sections 12 and 13).  Everything sits in an anonymous namespace: every unit that includes this header gets
-// its own instances of the kernels.
+// vb_kernels.h -- the per-row variable-base kernels, the pipeline kernels and the host steps that schnorr.hip and ecvrf.hip
+// share (DESIGN.md sections 12 and 13).  Everything sits in an anonymous namespace: every unit that includes this header
+// gets its own instances of the kernels.
 //
 // Variable base, one lane per row (out[i] = k_i P_i, a different P_i per row):
 //   vb_table_kernel   the odd multiples (2 j + 1) P_i, j < 2^(W-1), by one doubling and 2^(W-1) - 1 projective additions, then
@@ -21,6 +21,8 @@
 namespace {
 
 using namespace gh;
+using gh_rt::g;
+using gh_rt::g_err;
 
 constexpr int BLOCK = 64;
 
@@ -273,11 +275,19 @@ template <class P> bool all_below(const uint64_t* x, size_t count) {
 }
 bool mul_overflows(size_t a, size_t b, size_t* r) { return __builtin_mul_overflow(a, b, r); }
 
-// the curve's types: C the group, PF its base (= data) field, PS its scalar field
+// the curve's types: C the group, PF its base (= data) field, PS its scalar field; field: the hash's field id
 template <class C> struct Scheme;
 template <> struct Scheme<Mnt6G1> { typedef P6 PF; typedef P4 PS; static constexpr gh_field_t field = GH_MNT4753_FR; };
 template <> struct Scheme<Mnt4G1> { typedef P4 PF; typedef P6 PS; static constexpr gh_field_t field = GH_MNT6753_FR; };
+inline bool is_g1(gh_curve_t c) { return c == GH_MNT6753_G1 || c == GH_MNT4753_G1; }
+#define GH_G1_DISPATCH(curve, fn, ...) ((curve) == GH_MNT6753_G1 ? fn<Mnt6G1>(__VA_ARGS__) : fn<Mnt4G1>(__VA_ARGS__))
+template <class C> bool data_below(const uint64_t* x, size_t count) { return all_below<typename Scheme<C>::PF>(x, count); }
+template <class C> bool scalar_below(const uint64_t* x, size_t count) { return all_below<typename Scheme<C>::PS>(x, count); }
 
+template <class C> Fp curve_b() {
+    static const uint64_t b4[12] = GH_MNT4753_G1_B0_M_64, b6[12] = GH_MNT6753_G1_B0_M_64;
+    return fp_from_abi<typename Scheme<C>::PF>((const uint32_t*)(std::is_same<C, Mnt6G1>::value ? b6 : b4));
+}
 template <class C> void generator_xyz(uint64_t* g_xyz) {
     const bool m6 = std::is_same<C, Mnt6G1>::value;
     static const uint64_t gx4[12] = GH_MNT4753_G1_GX0_M_64, gy4[12] = GH_MNT4753_G1_GY0_M_64, one4[12] = GH_P4_R_64;
@@ -290,49 +300,211 @@ template <class C> void generator_xyz(uint64_t* g_xyz) {
 // The generator's fixed-base table of a handle: the caller's window, or (window 0) gh_fixed_base_window(n), rebuilt when a
 // later call's n asks for a larger window than the table has -- a handle first used on a few rows does not keep a tiny table
 // for large batches.  The window grows with log n, so a handle rebuilds at most a few times.
-inline int generator_table(gh_curve_t curve, int window, size_t n, gh_rt::FixedTable** table, int* table_window) {
-    const int w = std::max(1, std::min(window ? window : gh_fixed_base_window(n), 22));
-    if (*table && w <= *table_window) return GH_OK;
-    if (*table) {
-        HIPCHK(hipStreamSynchronize(gh_rt::g.stream));
-        gh_rt::fixed_table_destroy(*table);
-        *table = nullptr;
-        *table_window = 0;
+struct GeneratorTable {
+    int window = 0;                       // the caller's fixed-base window, 0 = automatic
+    gh_rt::FixedTable* table = nullptr;   // the generator's window table (scalar_size 753), built on first use
+    int table_window = 0;                 // the window it was built with
+    int ensure(gh_curve_t curve, size_t n) {
+        const int w = std::max(1, std::min(window ? window : gh_fixed_base_window(n), 22));
+        if (table && w <= table_window) return GH_OK;
+        if (table) {
+            HIPCHK(hipStreamSynchronize(g.stream));
+            destroy();
+        }
+        uint64_t g_xyz[36];
+        if (curve == GH_MNT6753_G1) generator_xyz<Mnt6G1>(g_xyz);
+        else generator_xyz<Mnt4G1>(g_xyz);
+        if (int rc = gh_rt::fixed_table_create(curve, g_xyz, VB_BITS, w, &table)) return rc;
+        table_window = w;
+        return GH_OK;
     }
-    uint64_t g_xyz[36];
-    if (curve == GH_MNT6753_G1) generator_xyz<Mnt6G1>(g_xyz);
-    else generator_xyz<Mnt4G1>(g_xyz);
-    if (int rc = gh_rt::fixed_table_create(curve, g_xyz, VB_BITS, w, table)) return rc;
-    *table_window = w;
-    return GH_OK;
-}
+    void destroy() {
+        gh_rt::fixed_table_destroy(table);
+        table = nullptr;
+        table_window = 0;
+    }
+};
 
+// A unit's timing record, what its *_last_timing reports.  Each unit has its own instance: the two report separately.
+struct Timing {
+    static constexpr int MAX_PHASES = 7;  // g.ev holds 8 events
+    int nph;
+    float ms[MAX_PHASES] = {};
+    float total_ms = 0;
+    // a call that times one phase only, between two recorded and completed events
+    int single(int phase, hipEvent_t ev0, hipEvent_t ev1) {
+        for (int i = 0; i < nph; i++) ms[i] = 0;
+        HIPCHK(hipEventElapsedTime(&ms[phase], ev0, ev1));
+        total_ms = ms[phase];
+        return GH_OK;
+    }
+    // the body of a *_last_timing: the count of phases written, or an error
+    int copy_out(float* phase_ms, int max_phases, float* total) const {
+        if ((!phase_ms && max_phases > 0) || max_phases < 0) { g_err = "null argument"; return GH_E_BAD_ARG; }
+        const int cnt = std::min(max_phases, nph);
+        for (int i = 0; i < cnt; i++) phase_ms[i] = ms[i];
+        if (total) *total = total_ms;
+        return cnt;
+    }
+};
 // the phases of an entry point on g.stream: ev[0] start, ev[k] end of phase k; finish() writes the unit's timing record
 struct Phases {
-    float* ms;                            // nph phase times
-    int nph;
-    float* total_ms;
+    Timing& tm;
     int k = 0;
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     int mark() {
-        HIPCHK(hipEventRecord(gh_rt::g.ev[k], gh_rt::g.stream));
+        HIPCHK(hipEventRecord(g.ev[k], g.stream));
         k++;
         return GH_OK;
     }
     int finish() {
-        HIPCHK(hipEventSynchronize(gh_rt::g.ev[k - 1]));
-        for (int i = 0; i < nph; i++) ms[i] = 0;
-        for (int i = 1; i < k && i <= nph; i++) HIPCHK(hipEventElapsedTime(&ms[i - 1], gh_rt::g.ev[i - 1], gh_rt::g.ev[i]));
-        *total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        HIPCHK(hipEventSynchronize(g.ev[k - 1]));
+        for (int i = 0; i < tm.nph; i++) tm.ms[i] = 0;
+        for (int i = 1; i < k && i <= tm.nph; i++) HIPCHK(hipEventElapsedTime(&tm.ms[i - 1], g.ev[i - 1], g.ev[i]));
+        tm.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return GH_OK;
     }
 };
 
-// pooled device buffers and uploads on g.stream
+// Pooled device buffers and uploads on g.stream.  Both units draw from the one "vb_" namespace of the pool: every entry
+// point holds api_mutex() and synchronises before it returns, so the two never hold a buffer at once.  An entry point keeps a
+// Trim: when it returns, every "vb_" buffer above SLAB_KEEP_BYTES is released, and Poseidon's slab by the same rule.
 template <class T> int dbuf(const char* name, size_t count, T** out) { return gh_rt::pool_get(name, std::max<size_t>(count * sizeof(T), 64), (void**)out); }
 template <class T> int up(T* d, const T* h, size_t count) {
-    if (count) HIPCHK(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, gh_rt::g.stream));
+    if (count) HIPCHK(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, g.stream));
     return GH_OK;
+}
+struct Trim {
+    ~Trim() {
+        gh_rt::pool_trim("vb_", gh_rt::SLAB_KEEP_BYTES);
+        gh_rt::poseidon_trim_slab();
+    }
+};
+
+// ---- the variable-base launches; large batches are cut into chunks whose slabs stay below VB_SLAB_BYTES together
+constexpr size_t VB_SLAB_BYTES = (size_t)1 << 30;
+template <int W> constexpr size_t vb_row_bytes() { return (size_t)VbWindow<W>::E * SLOTS_PER_ENTRY * NL * 4; }   // one row of one slab
+template <int W> size_t vb_chunk(size_t n, int slabs) {
+    return std::min(n, std::max<size_t>(BLOCK, (VB_SLAB_BYTES / (vb_row_bytes<W>() * slabs)) / BLOCK * BLOCK));
+}
+
+// one table of (+-) P per row, then d_out[j][i] = d_k[j]_i (+-) P_i for each of the `count` scalar vectors (n x 24 words,
+// canonical) as internal Proj<C>, on g.stream
+template <class C, int W>
+int vb_single(const void* d_xy, const uint8_t* d_inf, int negate, const uint32_t* const* d_k, Proj<C>* const* d_out, int count, size_t n) {
+    const size_t chunk = vb_chunk<W>(n, 1);
+    uint32_t* slab = nullptr;
+    if (int rc = gh_rt::pool_get("vb_slab", chunk * vb_row_bytes<W>(), (void**)&slab)) return rc;
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t cnt = std::min(chunk, n - r0);
+        GH_LAUNCH((vb_table_kernel<C, W>), dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_xy, d_inf, r0, cnt, negate,
+                  slab);
+        for (int j = 0; j < count; j++)
+            GH_LAUNCH((vb_mul_kernel<C, W>), dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)slab, d_k[j], d_inf, r0, cnt,
+                      d_out[j]);
+    }
+    HIPCHK(hipGetLastError());
+    return GH_OK;
+}
+
+// ---- the pipeline steps
+template <class C>
+int launch_normalize(Proj<C>* a, const Proj<C>* b, size_t n, Fp* zp, void* out_xy, size_t row_words, size_t off, uint8_t* out_inf) {
+    GH_LAUNCH((normalize_kernel<C>), dim3(blocks(blocks(n, NORM_RUN), BLOCK)), dim3(BLOCK), 0, g.stream, a, b, n, zp, (uint32_t*)out_xy,
+              row_words, off, out_inf);
+    return GH_OK;
+}
+
+// pk = sk G through the handle's table
+template <class C> int run_public_keys(GeneratorTable& gt, gh_curve_t curve, const uint64_t* sk, size_t n, uint64_t* out_xy, uint8_t* out_inf) {
+    typedef typename Scheme<C>::PS PS;
+    if (int rc = gt.ensure(curve, n)) return rc;
+    uint64_t *d_sk, *d_xy;
+    uint32_t* d_k;
+    Proj<C>* d_p;
+    Fp* d_zp;
+    uint8_t* d_inf;
+    int rc = dbuf("vb_in", n * 12, &d_sk);
+    if (!rc) rc = dbuf("vb_k", n * 24, &d_k);
+    if (!rc) rc = dbuf("vb_p", n, &d_p);
+    if (!rc) rc = dbuf("vb_zp", n, &d_zp);
+    if (!rc) rc = dbuf("vb_xy", n * 24, &d_xy);
+    if (!rc) rc = dbuf("vb_inf", n, &d_inf);
+    if (rc || (rc = up(d_sk, sk, n * 12))) return rc;
+    GH_LAUNCH((mont_to_int_kernel<PS>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_sk, n, d_k, (uint8_t*)nullptr);
+    if ((rc = gh_rt::fixed_table_sums(gt.table, d_k, n, d_p)) || (rc = launch_normalize<C>(d_p, nullptr, n, d_zp, d_xy, 48, 0, d_inf))) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_xy, d_xy, n * 192, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(out_inf, d_inf, n, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return GH_OK;
+}
+// the body of gh_*_public_keys after the handle check
+inline int public_keys_api(GeneratorTable& gt, gh_curve_t curve, const uint64_t* sk, size_t n, uint64_t* out_xy, uint8_t* out_inf) {
+    if (n && (!sk || !out_xy || !out_inf)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    size_t b;
+    if (mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (!GH_G1_DISPATCH(curve, scalar_below, sk, n)) { g_err = "a secret key is not below the modulus"; return GH_E_BAD_ARG; }
+    if (n == 0) return GH_OK;
+    if (int rc = gh_rt::ensure_init()) return rc;
+    return GH_G1_DISPATCH(curve, run_public_keys, gt, curve, sk, n, out_xy, out_inf);
+}
+
+template <class C> int run_keyverify(const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n, uint8_t* out_ok) {
+    uint64_t* d_pk;
+    uint8_t *d_inf, *d_ok;
+    int rc = dbuf("vb_pk", n * 24, &d_pk);
+    if (!rc) rc = dbuf("vb_pkinf", n, &d_inf);
+    if (!rc) rc = dbuf("vb_ok", n, &d_ok);
+    if (rc || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_inf, pk_inf, n))) return rc;
+    GH_LAUNCH((on_curve_kernel<C>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_pk, (const uint8_t*)d_inf, n, curve_b<C>(),
+              d_ok);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_ok, d_ok, n, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return GH_OK;
+}
+
+// ---- the argument checks
+// sizes and the moduli of pk and the message (msg null: none), shared by sign / verify / prove / proof_to_hash / keyverify
+template <class C> int check_rows(const uint64_t* pk_xy, const uint64_t* msg, size_t n, size_t len) {
+    size_t nm = 0, b = 0;
+    if (mul_overflows(n, len, &nm) || mul_overflows(nm, 96 * 4, &b) || mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (!data_below<C>(pk_xy, 2 * n)) { g_err = "a public-key coordinate is not below the modulus"; return GH_E_BAD_ARG; }
+    if (msg && !data_below<C>(msg, nm)) { g_err = "a message element is not below the modulus"; return GH_E_BAD_ARG; }
+    return GH_OK;
+}
+// the body of gh_*_keyverify after the handle check
+inline int keyverify_api(gh_curve_t curve, const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n, uint8_t* out_ok) {
+    if (n && (!pk_xy || !pk_inf || !out_ok)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (int rc = GH_G1_DISPATCH(curve, check_rows, pk_xy, nullptr, n, 0)) return rc;
+    if (n == 0) return GH_OK;
+    if (int rc = gh_rt::ensure_init()) return rc;
+    return GH_G1_DISPATCH(curve, run_keyverify, pk_xy, pk_inf, n, out_ok);
+}
+// what gh_*_create checks of the curve, the window and the hash; `scheme` names the caller in the message
+inline int check_create(const char* scheme, gh_curve_t curve, gh_poseidon* hash, int window) {
+    if (!is_g1(curve)) { g_err = std::string("the ") + scheme + " group must be a G1 curve"; return GH_E_BAD_ARG; }
+    if (window < 0 || window > 22) { g_err = "fixed-base window must be 0 or in [1, 22]"; return GH_E_BAD_ARG; }
+    gh_field_t f;
+    if (gh_rt::poseidon_field(hash, &f)) { g_err = "not a Poseidon handle"; return GH_E_BAD_ARG; }
+    const gh_field_t need = curve == GH_MNT6753_G1 ? Scheme<Mnt6G1>::field : Scheme<Mnt4G1>::field;
+    if (f != need) { g_err = "the hash's field is not the curve's base field"; return GH_E_BAD_ARG; }
+    return GH_OK;
+}
+// what gh_batch_mul / gh_batch_double_mul (`fn`) check of the curve, the pointers (non_null) and the row count
+inline int check_batch(const char* fn, gh_curve_t curve, size_t n, bool non_null) {
+    if (curve == GH_MNT4753_G2 || curve == GH_MNT6753_G2) { g_err = std::string(fn) + ": G1 curves only"; return GH_E_UNSUPPORTED; }
+    if (!is_g1(curve)) { g_err = "unknown curve id"; return GH_E_BAD_ARG; }
+    if (n && !non_null) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    size_t b;
+    if (mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    return GH_OK;
+}
+inline bool below_2_753(const uint64_t* k, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (k[12 * i + 11] >> 49) return false;
+    return true;
 }
 
 }  // namespace

@@ -15,57 +15,29 @@ EcVrfMNT6 the same over "mnt6753_fr" with "mnt4753_g1".  Layouts are schnorr.py'
 the Montgomery form x * 2^768; secrets and nonces are in the Montgomery form of the group's scalar field; a point is
 (xy: (n, 24), inf: (n,) uint8); gamma is such a point and cs the rows c || s (24 limbs); messages have shape (n, len, 12).
 """
-import ctypes
-
 import numpy as np
 
-from . import CURVES, GingerHipError, _check, _ptr, load_library
-from .schnorr import _msg, _pk, _rows
+from . import GingerHipError, _check, _ptr    # noqa: F401 (GingerHipError: re-exported)
+from . import _handles
+from ._handles import _bytes, _cid, _msg, _pk, _rows, ci, sz, vp
 
+_ARGTYPES = {"gh_bh_create": [ci, vp, vp, sz, sz, _handles.OUT_HANDLE], "gh_bh_free": [vp], "gh_bh_hash": [vp, vp, sz, sz, vp, vp],
+             "gh_batch_double_mul": [ci, vp, vp, vp, vp, vp, vp, sz, vp], "gh_ecvrf_create": [ci, vp, vp, ci, _handles.OUT_HANDLE],
+             "gh_ecvrf_free": [vp], "gh_ecvrf_public_keys": [vp, vp, sz, vp, vp],
+             "gh_ecvrf_prove": [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp],
+             "gh_ecvrf_proof_to_hash": [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp], "gh_ecvrf_keyverify": [vp, vp, vp, sz, vp],
+             "gh_ecvrf_last_timing": _handles.TIMING}
 # every symbol include/ginger_hip_ecvrf.h declares (kept apart from the ABI / dist / Poseidon / Schnorr lists)
-ECVRF_SYMBOLS = ["gh_bh_create", "gh_bh_free", "gh_bh_hash", "gh_batch_double_mul", "gh_ecvrf_create", "gh_ecvrf_free",
-                 "gh_ecvrf_public_keys", "gh_ecvrf_prove", "gh_ecvrf_proof_to_hash", "gh_ecvrf_keyverify", "gh_ecvrf_last_timing"]
+ECVRF_SYMBOLS = list(_ARGTYPES)
 PHASES = ["upload", "group_hash", "fixed_base", "variable_base", "normalise", "hash", "finish"]
-_bound = None
-
-
-def _lib():
-    global _bound
-    lib = load_library()
-    if _bound is lib:
-        return lib
-    missing = [s for s in ECVRF_SYMBOLS if not hasattr(lib, s)]
-    if missing:
-        raise GingerHipError("libginger_hip.so lacks EC-VRF symbols: %s" % missing)
-    vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-    lib.gh_bh_create.argtypes = [ci, vp, vp, sz, sz, ctypes.POINTER(vp)]
-    lib.gh_bh_free.argtypes = [vp]
-    lib.gh_bh_hash.argtypes = [vp, vp, sz, sz, vp, vp]
-    lib.gh_batch_double_mul.argtypes = [ci, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.gh_ecvrf_create.argtypes = [ci, vp, vp, ci, ctypes.POINTER(vp)]
-    lib.gh_ecvrf_free.argtypes = [vp]
-    lib.gh_ecvrf_public_keys.argtypes = [vp, vp, sz, vp, vp]
-    lib.gh_ecvrf_prove.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
-    lib.gh_ecvrf_proof_to_hash.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
-    lib.gh_ecvrf_keyverify.argtypes = [vp, vp, vp, sz, vp]
-    lib.gh_ecvrf_last_timing.argtypes = [ctypes.POINTER(ctypes.c_float), ci, ctypes.POINTER(ctypes.c_float)]
-    _bound = lib
-    return lib
-
-
-def _cid(curve):
-    return CURVES[curve] if isinstance(curve, str) else int(curve)
+_lib = _handles.binder("EC-VRF", _ARGTYPES)
 
 
 def last_timing():
     """({phase: milliseconds} of the last prove / proof_to_hash / evaluate / batch_double_mul, total milliseconds); evaluate
     records its group_hash phase only, batch_double_mul its variable_base phase only"""
-    buf = (ctypes.c_float * len(PHASES))()
-    tot = ctypes.c_float()
-    n = _lib().gh_ecvrf_last_timing(buf, len(PHASES), ctypes.byref(tot))
-    if n < 0:
-        _check(n)
-    return {PHASES[i]: buf[i] for i in range(n)}, tot.value
+    ms, tot = _handles.last_timing(_lib().gh_ecvrf_last_timing, len(PHASES))
+    return dict(zip(PHASES, ms)), tot
 
 
 def batch_double_mul(curve, xy1, k1, xy2, k2, inf1=None, inf2=None):
@@ -76,28 +48,27 @@ def batch_double_mul(curve, xy1, k1, xy2, k2, inf1=None, inf2=None):
     n = xy1.shape[0]
     if xy2.shape[0] != n or k1.shape[0] != n or k2.shape[0] != n:
         raise ValueError("two bases and two scalars per row")
-    infs = [None if f is None else np.ascontiguousarray(np.asarray(f, dtype=np.uint8).reshape(n)) for f in (inf1, inf2)]
+    infs = [None if f is None else _bytes(f, n) for f in (inf1, inf2)]
     out = np.zeros((n, 36), dtype=np.uint64)
     p = [None if f is None else _ptr(f) for f in infs]
     _check(_lib().gh_batch_double_mul(_cid(curve), _ptr(xy1), p[0], _ptr(k1), _ptr(xy2), p[1], _ptr(k2), n, _ptr(out)))
     return out
 
 
-class BoweHopwoodPedersenCRH:
+class BoweHopwoodPedersenCRH(_handles.Handle):
     """generators[num_windows][window_size] as segment-major rows: gen_xy (num_windows * window_size, 24), gen_inf (same
     count) or None"""
+
+    _lib, _prefix = staticmethod(_lib), "gh_bh"
 
     def __init__(self, curve, gen_xy, gen_inf, num_windows, window_size):
         self.curve = curve
         self.num_windows, self.window_size = int(num_windows), int(window_size)
         xy = _rows(gen_xy, 24)
-        inf = None if gen_inf is None else np.ascontiguousarray(np.asarray(gen_inf, dtype=np.uint8).reshape(-1))
+        inf = None if gen_inf is None else _bytes(gen_inf)
         if xy.shape[0] != self.num_windows * self.window_size or (inf is not None and inf.shape[0] != xy.shape[0]):
             raise ValueError("num_windows * window_size generators")
-        h = ctypes.c_void_p()
-        _check(_lib().gh_bh_create(_cid(curve), _ptr(xy), None if inf is None else _ptr(inf), self.num_windows, self.window_size,
-                                   ctypes.byref(h)))
-        self.handle = h
+        self._create(_cid(curve), _ptr(xy), None if inf is None else _ptr(inf), self.num_windows, self.window_size)
 
     def evaluate(self, data):
         """data: uint8 (n, nbytes) -> (xy (n, 24), inf (n,))"""
@@ -110,37 +81,14 @@ class BoweHopwoodPedersenCRH:
         _check(_lib().gh_bh_hash(self.handle, _ptr(d), n, nbytes, _ptr(xy), _ptr(inf)))
         return xy, inf
 
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib().gh_bh_free(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class FieldBasedEcVrf(_handles.KeyOps, _handles.Handle):
+    _lib, _prefix = staticmethod(_lib), "gh_ecvrf"
 
-
-class FieldBasedEcVrf:
     def __init__(self, params, bh, curve, window=0):
         self.params, self.bh = params, bh        # kept alive: the handle uses both
         self.curve = curve
-        h = ctypes.c_void_p()
-        _check(_lib().gh_ecvrf_create(_cid(curve), params.handle, bh.handle, int(window), ctypes.byref(h)))
-        self.handle = h
-
-    def keygen_from(self, sk):
-        """(pk, sk) of keygen for the given secrets: pk = sk G"""
-        return self.get_public_key(sk), sk
-
-    def get_public_key(self, sk):
-        sk = _rows(sk, 12)
-        n = sk.shape[0]
-        xy = np.zeros((n, 24), dtype=np.uint64)
-        inf = np.zeros(n, dtype=np.uint8)
-        _check(_lib().gh_ecvrf_public_keys(self.handle, _ptr(sk), n, _ptr(xy), _ptr(inf)))
-        return xy, inf
+        self._create(_cid(curve), params.handle, bh.handle, int(window))
 
     def prove(self, sk, pk, msg, nonces):
         """-> ((gamma_xy, gamma_inf), cs (n, 24), status (n,) uint8): 1 proved, 0 the nonce was rejected (its cs row is zero)"""
@@ -174,20 +122,3 @@ class FieldBasedEcVrf:
         _check(_lib().gh_ecvrf_proof_to_hash(self.handle, _ptr(xy), _ptr(inf), _ptr(m), n, m.shape[1], _ptr(gxy), _ptr(ginf), _ptr(c),
                                              _ptr(out), _ptr(st)))
         return out, st
-
-    def keyverify(self, pk):
-        xy, inf = _pk(pk)
-        ok = np.zeros(xy.shape[0], dtype=np.uint8)
-        _check(_lib().gh_ecvrf_keyverify(self.handle, _ptr(xy), _ptr(inf), xy.shape[0], _ptr(ok)))
-        return ok.astype(bool)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib().gh_ecvrf_free(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -15,40 +15,18 @@ import json
 
 import numpy as np
 
-from . import FIELDS, GingerHipError, _check, _ptr, _u64, load_library
+from . import FIELDS, GingerHipError, _check, _ptr, _u64    # noqa: F401 (GingerHipError: re-exported)
+from . import _handles
+from ._handles import _rows, ci, sz, u32, vp
 
+_ARGTYPES = {"gh_poseidon_create": [ci, u32, u32, vp, sz, vp, vp, vp, _handles.OUT_HANDLE], "gh_poseidon_free": [vp],
+             "gh_poseidon_permute": [vp, vp, sz], "gh_poseidon_hash": [vp, vp, sz, sz, vp], "gh_poseidon_hash_dev": [vp, vp, sz, sz, vp],
+             "gh_poseidon_merkle_tree": [vp, vp, sz, u32, vp, vp, vp], "gh_poseidon_merkle_verify": [vp, vp, vp, vp, sz, u32, vp, vp],
+             "gh_poseidon_set_tuning": [ci, sz], "gh_poseidon_last_timing": _handles.TIMING}
 # every symbol include/ginger_hip_poseidon.h declares (kept apart from ABI_SYMBOLS / DIST_SYMBOLS)
-POSEIDON_SYMBOLS = ["gh_poseidon_create", "gh_poseidon_free", "gh_poseidon_permute", "gh_poseidon_hash", "gh_poseidon_hash_dev",
-                    "gh_poseidon_merkle_tree", "gh_poseidon_merkle_verify", "gh_poseidon_set_tuning", "gh_poseidon_last_timing"]
+POSEIDON_SYMBOLS = list(_ARGTYPES)
 SIZE_MAX = (1 << 64) - 1
-_bound = None
-
-
-def _lib():
-    global _bound
-    lib = load_library()
-    if _bound is lib:
-        return lib
-    missing = [s for s in POSEIDON_SYMBOLS if not hasattr(lib, s)]
-    if missing:
-        raise GingerHipError("libginger_hip.so lacks Poseidon symbols: %s" % missing)
-    vp, sz, u32, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-    lib.gh_poseidon_create.argtypes = [ci, u32, u32, vp, sz, vp, vp, vp, ctypes.POINTER(vp)]
-    lib.gh_poseidon_free.argtypes = [vp]
-    lib.gh_poseidon_permute.argtypes = [vp, vp, sz]
-    lib.gh_poseidon_hash.argtypes = [vp, vp, sz, sz, vp]
-    lib.gh_poseidon_hash_dev.argtypes = [vp, vp, sz, sz, vp]
-    lib.gh_poseidon_merkle_tree.argtypes = [vp, vp, sz, u32, vp, vp, vp]
-    lib.gh_poseidon_merkle_verify.argtypes = [vp, vp, vp, vp, sz, u32, vp, vp]
-    lib.gh_poseidon_set_tuning.argtypes = [ci, sz]
-    lib.gh_poseidon_last_timing.argtypes = [ctypes.POINTER(ctypes.c_float), ci, ctypes.POINTER(ctypes.c_float)]
-    _bound = lib
-    return lib
-
-
-def _rows(a):
-    a = _u64(a, 12)
-    return a.reshape(-1, 12)
+_lib = _handles.binder("Poseidon", _ARGTYPES)
 
 
 def _hex_rows(vals):
@@ -63,16 +41,12 @@ def set_tuning(states_per_lane=0, host_tail_nodes=None):
 
 def last_timing(max_levels=64):
     """(per-level milliseconds of the last tree build, bottom-up, then the padding chain; total milliseconds)."""
-    buf = (ctypes.c_float * max_levels)()
-    tot = ctypes.c_float()
-    n = _lib().gh_poseidon_last_timing(buf, max_levels, ctypes.byref(tot))
-    if n < 0:
-        _check(n)
-    return [buf[i] for i in range(n)], tot.value
+    return _handles.last_timing(_lib().gh_poseidon_last_timing, max_levels)
 
 
-class PoseidonParameters:
+class PoseidonParameters(_handles.Handle):
     """One parameter set (T = 3, rate 2); the handle holds its constants in the device's internal form."""
+    _lib, _prefix = staticmethod(_lib), "gh_poseidon"
 
     def __init__(self, field, r_f, r_p, round_cst, mds, c2, after_zero_perm):
         self.field = field
@@ -84,10 +58,8 @@ class PoseidonParameters:
         self.after_zero_perm = _rows(after_zero_perm)
         if self.mds.shape[0] != 9 or self.c2.shape[0] != 1 or self.after_zero_perm.shape[0] != 3:
             raise ValueError("mds needs 9 elements, c2 one, after_zero_perm three")
-        h = ctypes.c_void_p()
-        _check(_lib().gh_poseidon_create(self.field_id, self.r_f, self.r_p, _ptr(self.round_cst), self.round_cst.shape[0],
-                                         _ptr(self.mds), _ptr(self.c2), _ptr(self.after_zero_perm), ctypes.byref(h)))
-        self.handle = h
+        self._create(self.field_id, self.r_f, self.r_p, _ptr(self.round_cst), self.round_cst.shape[0], _ptr(self.mds), _ptr(self.c2),
+                     _ptr(self.after_zero_perm))
 
     @classmethod
     def from_json(cls, obj, tag):
@@ -107,17 +79,6 @@ class PoseidonParameters:
             raise ValueError("states must be whole triples of elements")
         _check(_lib().gh_poseidon_permute(self.handle, _ptr(st), st.size // 36))
         return st
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib().gh_poseidon_free(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class PoseidonHash:
