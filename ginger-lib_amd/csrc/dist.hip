@@ -109,17 +109,6 @@ int load_rccl() {
         if (r_ != ncclSuccess) { g_err = std::string(#call " failed: ") + R.GetErrorString(r_); return GH_E_DIST; } \
     } while (0)
 
-int deg_of(gh_curve_t c) { return c == GH_MNT4753_G2 ? 2 : (c == GH_MNT6753_G2 ? 3 : 1); }
-const MsmOps* ops_for(gh_curve_t c) {
-    switch (c) {
-        case GH_MNT4753_G1: return msm_ops_mnt4753_g1();
-        case GH_MNT4753_G2: return msm_ops_mnt4753_g2();
-        case GH_MNT6753_G1: return msm_ops_mnt6753_g1();
-        case GH_MNT6753_G2: return msm_ops_mnt6753_g2();
-        default: return nullptr;
-    }
-}
-
 // both locks held
 void teardown() {
     if (D.comm) R.CommDestroy(D.comm);
@@ -131,9 +120,9 @@ void teardown() {
 
 // both locks held.  partials / outs: count x words u64
 int exchange_fold(gh_curve_t curve, const uint64_t* partials, size_t count, uint64_t* outs, double* exchange_us) {
-    const MsmOps* ops = ops_for(curve);
-    if (!ops) { g_err = "unknown curve id"; return GH_E_BAD_ARG; }
-    const size_t words = (size_t)36 * deg_of(curve), block = words * count;
+    const MsmOps* ops = ops_of(curve);
+    if (!ops) return GH_E_BAD_ARG;
+    const size_t words = (size_t)36 * curve_deg(curve), block = words * count;
     std::vector<uint64_t> all(block * (size_t)D.world);
     const auto t0 = std::chrono::steady_clock::now();
     if (D.comm) {
@@ -268,7 +257,7 @@ int gh_partials_allgather_fold_batch(gh_curve_t curve, const uint64_t* partials_
     double total = 0;
     for (size_t k0 = 0; k0 < count; k0 += MAX_BATCH) {     // one exchange per MAX_BATCH partial sums
         const size_t cnt = count - k0 < MAX_BATCH ? count - k0 : MAX_BATCH;
-        const size_t words = (size_t)36 * deg_of(curve);
+        const size_t words = (size_t)36 * curve_deg(curve);
         double us = 0;
         const int rc = exchange_fold(curve, partials_xyz + k0 * words, cnt, outs_xyz + k0 * words, &us);
         if (rc) return rc;

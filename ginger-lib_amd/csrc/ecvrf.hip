@@ -24,8 +24,8 @@ struct gh_bh {
     size_t num_windows = 0, window_size = 0;
     std::vector<uint64_t> gen_xy;         // host copy, segment-major x || y rows
     std::vector<uint8_t> gen_inf;
-    void* d_tab = nullptr;                // {1, 2, 3, 4} g as Aff<C>, built on first use
-    uint8_t* d_inf = nullptr;             // the generators' infinity bytes
+    gh_rt::DevMem d_tab;                  // {1, 2, 3, 4} g as Aff<C>, built on first use
+    gh_rt::DevMem d_inf;                  // the generators' infinity bytes
 };
 
 struct gh_ecvrf {
@@ -193,33 +193,19 @@ __global__ void __launch_bounds__(256) verdict_kernel(const uint64_t* __restrict
 // ---------------------------------------------------------------------------------------------------- host side
 // the generators' table on the device, on first use
 template <class C> int bh_ensure(gh_bh* b) {
-    if (b->d_tab) return GH_OK;
+    if (b->d_tab.get()) return GH_OK;
     const size_t ng = b->num_windows * b->window_size;
-    uint32_t* d_gen = nullptr;
-    void* d_tab = nullptr;
-    uint8_t* d_inf = nullptr;
-    hipError_t e = hipMalloc(&d_tab, ng * BH_ENTRIES * sizeof(Aff<C>));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_inf, ng);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_gen, ng * 192);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_gen, b->gen_xy.data(), ng * 192, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_inf, b->gen_inf.data(), ng, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess && gh_rt::scratch_guard((const void*)bh_table_kernel<C>, (size_t)blocks(ng, BLOCK) * BLOCK)) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(bh_table_kernel<C>, dim3(blocks(ng, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_gen,
-                           (const uint8_t*)d_inf, ng, (Aff<C>*)d_tab);
-        e = hipGetLastError();
-    }
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(d_gen);
-    if (e != hipSuccess) {
-        (void)hipFree(d_tab);
-        (void)hipFree(d_inf);
-        g_err = std::string("Bowe-Hopwood table: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? GH_E_NOMEM : GH_E_HIP;
-    }
-    b->d_tab = d_tab;
-    b->d_inf = d_inf;
+    gh_rt::DevMem d_gen, d_tab, d_inf;     // table and flags move into the handle once the table is built
+    int rc;
+    if ((rc = d_tab.alloc(ng * BH_ENTRIES * sizeof(Aff<C>))) || (rc = d_inf.alloc(ng)) || (rc = d_gen.alloc(ng * 192))) return rc;
+    HIPCHK(hipMemcpyAsync(d_gen.get(), b->gen_xy.data(), ng * 192, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(d_inf.get(), b->gen_inf.data(), ng, hipMemcpyHostToDevice, g.stream));
+    GH_LAUNCH(bh_table_kernel<C>, dim3(blocks(ng, BLOCK)), dim3(BLOCK), 0, g.stream, d_gen.as<const uint32_t>(),
+              d_inf.as<const uint8_t>(), ng, d_tab.as<Aff<C>>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(g.stream));
+    b->d_tab = std::move(d_tab);
+    b->d_inf = std::move(d_inf);
     return GH_OK;
 }
 
@@ -227,7 +213,7 @@ template <class C> int bh_ensure(gh_bh* b) {
 template <class C> int bh_launch(gh_bh* b, const uint8_t* d_in, size_t stride, size_t nbytes, size_t n, Proj<C>* d_p) {
     if (int rc = bh_ensure<C>(b)) return rc;
     const size_t nchunks = (8 * nbytes + 2) / 3;
-    GH_LAUNCH((bh_hash_kernel<C>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const Aff<C>*)b->d_tab, (const uint8_t*)b->d_inf,
+    GH_LAUNCH((bh_hash_kernel<C>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, b->d_tab.as<const Aff<C>>(), b->d_inf.as<const uint8_t>(),
               d_in, stride, nbytes, nchunks, n, d_p);
     HIPCHK(hipGetLastError());
     return GH_OK;
@@ -515,11 +501,7 @@ int gh_bh_free(gh_bh_t h) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     if (!h) return GH_OK;
     if (!valid(h)) { g_err = "not a Bowe-Hopwood handle"; return GH_E_BAD_HANDLE; }
-    if (h->d_tab) {
-        (void)hipStreamSynchronize(g.stream);
-        (void)hipFree(h->d_tab);
-        (void)hipFree(h->d_inf);
-    }
+    if (h->d_tab.get()) (void)hipStreamSynchronize(g.stream);
     h->magic = 0;
     delete h;
     return GH_OK;

@@ -15,6 +15,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <vector>
 #include "runtime.h"
 #include "msm_kernels.h"
@@ -213,20 +214,24 @@ chain_bases_kernel(Aff<C> p0, Aff<C> h, size_t n, Aff<C>* __restrict__ out, type
 namespace gh_rt {
 using namespace gh;
 
-template <class C> struct CurveIdOf;
-template <> struct CurveIdOf<Mnt4G1> { static constexpr gh_curve_t id = GH_MNT4753_G1; };
-template <> struct CurveIdOf<Mnt4G2> { static constexpr gh_curve_t id = GH_MNT4753_G2; };
-template <> struct CurveIdOf<Mnt6G1> { static constexpr gh_curve_t id = GH_MNT6753_G1; };
-template <> struct CurveIdOf<Mnt6G2> { static constexpr gh_curve_t id = GH_MNT6753_G2; };
-
 struct FixedTable {
-    uint32_t magic = 0x67684654u;
+    static constexpr uint32_t MAGIC = 0x67684654u;
+    uint32_t magic = MAGIC;
     gh_curve_t curve;
     int window = 0;
     uint32_t outerc = 0, scalar_size = 0;
     void* d_table = nullptr;
     bool has_marks = false;     // some entry is the point at infinity (g = 0 or of small order): only fixed_msm_kernel skips those
+    FixedTable() = default;
+    FixedTable(const FixedTable&) = delete;
+    FixedTable& operator=(const FixedTable&) = delete;
+    ~FixedTable() { dev_free(d_table); magic = 0; }
 };
+// the checked cast of a handle of the C ABI: null for a null pointer or for memory that is not a live table
+static FixedTable* table_of(gh_fixed_table_t handle) {
+    FixedTable* t = reinterpret_cast<FixedTable*>(handle);
+    return t && t->magic == FixedTable::MAGIC ? t : nullptr;
+}
 
 template <class C> int build_table(const uint64_t* g_xyz, size_t scalar_size, int window, FixedTable* t) {
     typedef typename HostCurveOf<C>::type HC;
@@ -249,38 +254,30 @@ template <class C> int build_table(const uint64_t* g_xyz, size_t scalar_size, in
         }
     }
     const size_t entries = (size_t)outerc << window;
-    Proj<C>* d_g = nullptr;
+    DevMem table, d_g;                 // the table becomes t->d_table once it is built
     uint32_t* d_flag = nullptr;
     uint32_t h_flag = 0;
-    if (int rc = pool_get("fixed_flag", 4, (void**)&d_flag)) return rc;
-    HIPCHK(hipMalloc(&t->d_table, entries * sizeof(Aff<C>)));
-    hipError_t e = hipMalloc((void**)&d_g, outerc * sizeof(Proj<C>));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_g, gouter.data(), outerc * sizeof(Proj<C>), hipMemcpyHostToDevice, g.stream);
+    int rc;
+    if ((rc = pool_get("fixed_flag", 4, (void**)&d_flag)) || (rc = table.alloc(entries * sizeof(Aff<C>))) ||
+        (rc = d_g.alloc(outerc * sizeof(Proj<C>)))) return rc;
+    hipError_t e = hipMemcpyAsync(d_g.get(), gouter.data(), outerc * sizeof(Proj<C>), hipMemcpyHostToDevice, g.stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 4, g.stream);
     if (e == hipSuccess) {
-        GH_LAUNCH((fixed_table_kernel<C>), dim3((unsigned)((entries + 63) / 64)), dim3(64), 0, g.stream, (const Proj<C>*)d_g,
-                           window, outerc, last_in_window, (Aff<C>*)t->d_table, d_flag);
+        GH_LAUNCH((fixed_table_kernel<C>), dim3((unsigned)((entries + 63) / 64)), dim3(64), 0, g.stream, d_g.as<const Proj<C>>(),
+                           window, outerc, last_in_window, table.as<Aff<C>>(), d_flag);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, g.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    t->has_marks = h_flag != 0;
-    if (d_g) (void)hipFree(d_g);
     if (e != hipSuccess) {
-        (void)hipFree(t->d_table);
-        t->d_table = nullptr;
         g_err = std::string("fixed-base table: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? GH_E_NOMEM : GH_E_HIP;
     }
+    t->d_table = table.release();
+    t->has_marks = h_flag != 0;
     t->window = window; t->outerc = outerc; t->scalar_size = (uint32_t)scalar_size;
     return GH_OK;
 }
-
-template <class C> const MsmOps* fixed_ops();
-template <> const MsmOps* fixed_ops<Mnt4G1>() { return msm_ops_mnt4753_g1(); }
-template <> const MsmOps* fixed_ops<Mnt4G2>() { return msm_ops_mnt4753_g2(); }
-template <> const MsmOps* fixed_ops<Mnt6G1>() { return msm_ops_mnt6753_g1(); }
-template <> const MsmOps* fixed_ops<Mnt6G2>() { return msm_ops_mnt6753_g2(); }
 
 // d_out[i] = sum over rows of table[outer][digit_outer(scalar i)] on g.stream (scalars already on the device)
 template <class C> int launch_fixed_sums(const FixedTable* t, const void* d_s, size_t n, void* d_o) {
@@ -299,7 +296,7 @@ template <class C> int launch_fixed_sums(const FixedTable* t, const void* d_s, s
     GH_LAUNCH(fixed_digits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, t->window, t->outerc, t->scalar_size,
                        (const uint32_t*)d_s, n, d_list, d_starts, d_counts, d_order);
     HIPCHK(hipGetLastError());
-    return fixed_ops<C>()->acc_lists(t->d_table, d_list, d_starts, d_counts, d_order, (uint32_t)n, d_o, g.stream);
+    return ops_of(CurveId<C>::id)->acc_lists(t->d_table, d_list, d_starts, d_counts, d_order, (uint32_t)n, d_o, g.stream);
 }
 
 template <class C> int run_fixed(const FixedTable* t, const uint64_t* scalars, size_t n, uint64_t* out_xyz) {
@@ -352,8 +349,8 @@ template <class C> int run_fixed_affine(const FixedTable* t, const uint64_t* sca
 template <class C> int chain_bases(const uint64_t* p0_xy, const uint64_t* h_xy, size_t n, BasesBase** out) {
     typedef typename C::F F;
     typedef typename C::FC::T FT;
-    BasesBase* hb = new BasesBase();
-    hb->curve = CurveIdOf<C>::id;
+    std::unique_ptr<BasesBase> hb(new BasesBase());    // an early return frees the key and its points
+    hb->curve = CurveId<C>::id;
     hb->n = n;
     if (n > 0) {
         Aff<C> p0, h;
@@ -361,25 +358,21 @@ template <class C> int chain_bases(const uint64_t* p0_xy, const uint64_t* h_xy, 
         p0.x = F::from_abi(w); p0.y = F::from_abi(w + 24 * F::DEG);
         w = reinterpret_cast<const uint32_t*>(h_xy);
         h.x = F::from_abi(w); h.y = F::from_abi(w + 24 * F::DEG);
-        FT* zs = nullptr;
-        hipError_t e = hipMalloc(&hb->d_points, n * sizeof(Aff<C>));
-        if (e == hipSuccess) e = hipMalloc((void**)&zs, n * sizeof(FT));
-        if (e == hipSuccess) {
-            const size_t threads = (n + CHAIN_RUN - 1) / CHAIN_RUN;
-            GH_LAUNCH((chain_bases_kernel<C>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, g.stream, p0, h, n,
-                               (Aff<C>*)hb->d_points, zs);
-            e = hipGetLastError();
-        }
+        DevMem points, zs;
+        int rc;
+        if ((rc = points.alloc(n * sizeof(Aff<C>))) || (rc = zs.alloc(n * sizeof(FT)))) return rc;
+        hb->d_points = points.release();
+        const size_t threads = (n + CHAIN_RUN - 1) / CHAIN_RUN;
+        GH_LAUNCH((chain_bases_kernel<C>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, g.stream, p0, h, n,
+                           (Aff<C>*)hb->d_points, zs.as<FT>());
+        hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-        if (zs) (void)hipFree(zs);
         if (e != hipSuccess) {
-            if (hb->d_points) (void)hipFree(hb->d_points);
-            delete hb;
             g_err = std::string("chain bases: ") + hipGetErrorString(e);
             return e == hipErrorOutOfMemory ? GH_E_NOMEM : GH_E_HIP;
         }
     }
-    *out = hb;
+    *out = hb.release();
     return GH_OK;
 }
 
@@ -396,62 +389,18 @@ template <class C> int download_bases(const BasesBase* hb, size_t first, size_t 
     return GH_OK;
 }
 
-int fixed_build(gh_curve_t curve, const uint64_t* g_xyz, size_t scalar_size, int window, FixedTable* t) {
-    switch (curve) {
-        case GH_MNT4753_G1: return build_table<Mnt4G1>(g_xyz, scalar_size, window, t);
-        case GH_MNT4753_G2: return build_table<Mnt4G2>(g_xyz, scalar_size, window, t);
-        case GH_MNT6753_G1: return build_table<Mnt6G1>(g_xyz, scalar_size, window, t);
-        case GH_MNT6753_G2: return build_table<Mnt6G2>(g_xyz, scalar_size, window, t);
-    }
-    g_err = "unknown curve id";
-    return GH_E_BAD_ARG;
-}
-int fixed_run(const FixedTable* t, const uint64_t* scalars, size_t n, uint64_t* out_xyz) {
-    switch (t->curve) {
-        case GH_MNT4753_G1: return run_fixed<Mnt4G1>(t, scalars, n, out_xyz);
-        case GH_MNT4753_G2: return run_fixed<Mnt4G2>(t, scalars, n, out_xyz);
-        case GH_MNT6753_G1: return run_fixed<Mnt6G1>(t, scalars, n, out_xyz);
-        case GH_MNT6753_G2: return run_fixed<Mnt6G2>(t, scalars, n, out_xyz);
-    }
-    return GH_E_BAD_ARG;
-}
-
-int fixed_run_affine(const FixedTable* t, const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* out_inf, int canonical) {
-    switch (t->curve) {
-        case GH_MNT4753_G1: return run_fixed_affine<Mnt4G1>(t, scalars, n, out_xy, out_inf, canonical);
-        case GH_MNT4753_G2: return run_fixed_affine<Mnt4G2>(t, scalars, n, out_xy, out_inf, canonical);
-        case GH_MNT6753_G1: return run_fixed_affine<Mnt6G1>(t, scalars, n, out_xy, out_inf, canonical);
-        case GH_MNT6753_G2: return run_fixed_affine<Mnt6G2>(t, scalars, n, out_xy, out_inf, canonical);
-    }
-    return GH_E_BAD_ARG;
-}
-
 int fixed_table_create(gh_curve_t curve, const uint64_t* g_xyz, size_t scalar_size, int window, FixedTable** out) {
-    FixedTable* t = new FixedTable();
+    std::unique_ptr<FixedTable> t(new FixedTable());
     t->curve = curve;
-    if (int rc = fixed_build(curve, g_xyz, scalar_size, window, t)) {
-        delete t;
-        return rc;
-    }
-    *out = t;
+    if (int rc = GH_CURVE_DISPATCH(curve, build_table, g_xyz, scalar_size, window, t.get())) return rc;
+    *out = t.release();
     return GH_OK;
 }
 int fixed_table_sums(const FixedTable* t, const void* d_scalars, size_t n, void* d_out_proj) {
     if (n == 0) return GH_OK;
-    switch (t->curve) {
-        case GH_MNT4753_G1: return launch_fixed_sums<Mnt4G1>(t, d_scalars, n, d_out_proj);
-        case GH_MNT4753_G2: return launch_fixed_sums<Mnt4G2>(t, d_scalars, n, d_out_proj);
-        case GH_MNT6753_G1: return launch_fixed_sums<Mnt6G1>(t, d_scalars, n, d_out_proj);
-        case GH_MNT6753_G2: return launch_fixed_sums<Mnt6G2>(t, d_scalars, n, d_out_proj);
-    }
-    return GH_E_BAD_ARG;
+    return GH_CURVE_DISPATCH(t->curve, launch_fixed_sums, t, d_scalars, n, d_out_proj);
 }
-void fixed_table_destroy(FixedTable* t) {
-    if (!t) return;
-    if (t->d_table) (void)hipFree(t->d_table);
-    t->magic = 0;
-    delete t;
-}
+void fixed_table_destroy(FixedTable* t) { delete t; }
 
 }  // namespace gh_rt
 
@@ -470,32 +419,30 @@ int gh_fixed_base_table(gh_curve_t curve, const uint64_t* g_xyz, size_t scalar_s
     if (window < 1 || window > 22 || scalar_size < 1 || scalar_size > 768) { g_err = "fixed-base window must be in [1, 22], scalar_size in [1, 768]"; return GH_E_BAD_ARG; }
     int rc = ensure_init();
     if (rc) return rc;
-    FixedTable* t = new FixedTable();
-    t->curve = curve;
-    rc = fixed_build(curve, g_xyz, scalar_size, window, t);
-    if (rc) { delete t; return rc; }
+    FixedTable* t = nullptr;
+    if ((rc = fixed_table_create(curve, g_xyz, scalar_size, window, &t))) return rc;
     *out = reinterpret_cast<gh_fixed_table_t>(t);
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_fixed_base_msm(gh_fixed_table_t table, const uint64_t* scalars, size_t n, uint64_t* out_xyz) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    FixedTable* t = reinterpret_cast<FixedTable*>(table);
-    if (!t || t->magic != 0x67684654u) { g_err = "bad fixed-base table handle"; return GH_E_BAD_HANDLE; }
+    FixedTable* t = table_of(table);
+    if (!t) { g_err = "bad fixed-base table handle"; return GH_E_BAD_HANDLE; }
     if (n && (!scalars || !out_xyz)) { g_err = "null argument"; return GH_E_BAD_ARG; }
     int rc = ensure_init();
     if (rc) return rc;
-    return fixed_run(t, scalars, n, out_xyz);
+    return GH_CURVE_DISPATCH(t->curve, run_fixed, t, scalars, n, out_xyz);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_fixed_base_msm_affine(gh_fixed_table_t table, const uint64_t* scalars, size_t n, uint64_t* out_xy, uint8_t* out_inf, int canonical) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    FixedTable* t = reinterpret_cast<FixedTable*>(table);
-    if (!t || t->magic != 0x67684654u) { g_err = "bad fixed-base table handle"; return GH_E_BAD_HANDLE; }
+    FixedTable* t = table_of(table);
+    if (!t) { g_err = "bad fixed-base table handle"; return GH_E_BAD_HANDLE; }
     if (n && (!scalars || !out_xy || !out_inf)) { g_err = "null argument"; return GH_E_BAD_ARG; }
     int rc = ensure_init();
     if (rc) return rc;
-    return fixed_run_affine(t, scalars, n, out_xy, out_inf, canonical);
+    return GH_CURVE_DISPATCH(t->curve, run_fixed_affine, t, scalars, n, out_xy, out_inf, canonical);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_bases_generate_chain(gh_curve_t curve, const uint64_t* p0_xy, const uint64_t* step_xy, size_t n, gh_bases_t* out_handle) try {
@@ -505,42 +452,27 @@ int gh_bases_generate_chain(gh_curve_t curve, const uint64_t* p0_xy, const uint6
     int rc = ensure_init();
     if (rc) return rc;
     BasesBase* h = nullptr;
-    switch (curve) {
-        case GH_MNT4753_G1: rc = chain_bases<Mnt4G1>(p0_xy, step_xy, n, &h); break;
-        case GH_MNT4753_G2: rc = chain_bases<Mnt4G2>(p0_xy, step_xy, n, &h); break;
-        case GH_MNT6753_G1: rc = chain_bases<Mnt6G1>(p0_xy, step_xy, n, &h); break;
-        case GH_MNT6753_G2: rc = chain_bases<Mnt6G2>(p0_xy, step_xy, n, &h); break;
-        default: g_err = "unknown curve id"; return GH_E_BAD_ARG;
-    }
-    if (rc) return rc;
+    if ((rc = GH_CURVE_DISPATCH(curve, chain_bases, p0_xy, step_xy, n, &h))) return rc;
     *out_handle = reinterpret_cast<gh_bases_t>(h);
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_bases_download(gh_bases_t handle, size_t first, size_t count, uint64_t* out_xy) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
-    if (!h || h->magic != 0x6768424au) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
+    BasesBase* h = bases_of(handle);
+    if (!h) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
     if (count == 0) return GH_OK;
     if (!out_xy || first > h->n || count > h->n - first) { g_err = "range outside the resident bases"; return GH_E_BAD_ARG; }
     int rc = ensure_init();
     if (rc) return rc;
-    switch (h->curve) {
-        case GH_MNT4753_G1: return download_bases<Mnt4G1>(h, first, count, out_xy);
-        case GH_MNT4753_G2: return download_bases<Mnt4G2>(h, first, count, out_xy);
-        case GH_MNT6753_G1: return download_bases<Mnt6G1>(h, first, count, out_xy);
-        case GH_MNT6753_G2: return download_bases<Mnt6G2>(h, first, count, out_xy);
-    }
-    return GH_E_BAD_ARG;
+    return GH_CURVE_DISPATCH(h->curve, download_bases, h, first, count, out_xy);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_fixed_base_free(gh_fixed_table_t table) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    FixedTable* t = reinterpret_cast<FixedTable*>(table);
-    if (!t || t->magic != 0x67684654u) { g_err = "bad fixed-base table handle"; return GH_E_BAD_HANDLE; }
-    if (t->d_table) (void)hipFree(t->d_table);
-    t->magic = 0;
-    delete t;
+    FixedTable* t = table_of(table);
+    if (!t) { g_err = "bad fixed-base table handle"; return GH_E_BAD_HANDLE; }
+    fixed_table_destroy(t);
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
 

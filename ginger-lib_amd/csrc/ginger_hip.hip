@@ -1,6 +1,9 @@
 // ginger_hip.hip -- the C ABI declared in include/ginger_hip.h plus the process-wide runtime
-// (device context, workspace pool, prefix scan).  Per-curve MSM code lives in msm_<curve>.hip,
-// the transforms in ntt.hip.  Build: __graft_entry__.py build() (hipcc --offload-arch=gfx950).
+// (device context, workspace pool, prefix scan, the map from a curve id to its MsmOps) and the
+// content-addressed key cache.  Per-curve MSM code lives in msm_<curve>.hip, the transforms in
+// ntt.hip, the fixed-base entry points in fixed_base.hip.  Every entry point holds api_mutex()
+// whenever it writes g_err; ownership of device memory: runtime.h (DevMem), DESIGN.md section 8a.
+// Build: __graft_entry__.py build() (hipcc --offload-arch=gfx950).
 #include <atomic>
 #include <condition_variable>
 #include <exception>
@@ -212,7 +215,7 @@ int auto_window(size_t n, int deg) {
     return c < 4 ? 4 : c;
 }
 
-static const MsmOps* ops_of(gh_curve_t curve) {
+const MsmOps* ops_of(gh_curve_t curve) {
     switch (curve) {
         case GH_MNT4753_G1: return msm_ops_mnt4753_g1();
         case GH_MNT4753_G2: return msm_ops_mnt4753_g2();
@@ -220,6 +223,17 @@ static const MsmOps* ops_of(gh_curve_t curve) {
         case GH_MNT6753_G2: return msm_ops_mnt6753_g2();
         default: g_err = "unknown curve id"; return nullptr;
     }
+}
+
+// host <-> device copies of the entry points that take host buffers, on g.stream; the caller holds the lock
+static int to_device(void* d_dst, const void* h_src, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, g.stream));
+    return GH_OK;
+}
+static int to_host_sync(void* h_dst, const void* d_src, size_t bytes) {   // the one wait of such an entry point
+    HIPCHK(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return GH_OK;
 }
 
 }  // namespace gh_rt
@@ -246,20 +260,11 @@ int gh_shutdown(void) try {
     dist_teardown_locked();              // a communicator must not outlive the streams and the device binding it was made on
     if (!g.ready) return GH_OK;
     (void)sync_msm_streams();
-    for (auto& kv : g.pool) if (kv.second.p) hipFree(kv.second.p);
-    g.pool.clear();
+    pool_release("");
     for (auto& f : g.at_shutdown) f();   // function-local device / pinned allocations (msm_impl.h)
     g.at_shutdown.clear();
     for (int f = 0; f < 2; f++) {
-        for (auto& kv : g.domains[f]) {
-            Domain& d = kv.second;
-            if (d.tw) hipFree(d.tw);
-            if (d.coset) hipFree(d.coset);
-            if (d.coset_inv) hipFree(d.coset_inv);
-            if (d.scratch) hipFree(d.scratch);
-            if (d.scratch2) hipFree(d.scratch2);
-            if (d.d_size_inv) hipFree(d.d_size_inv);
-        }
+        for (auto& kv : g.domains[f]) kv.second.release();
         g.domains[f].clear();
     }
     for (auto& ev : g.ev) hipEventDestroy(ev);
@@ -320,7 +325,7 @@ int gh_bases_upload_wire(gh_curve_t curve, const uint8_t* bytes, size_t n_points
     if (!ops) return GH_E_BAD_ARG;
     int rc = ensure_init();
     if (rc) return rc;
-    const int deg = curve == GH_MNT4753_G2 ? 2 : (curve == GH_MNT6753_G2 ? 3 : 1);
+    const int deg = curve_deg(curve);
     static const uint64_t p4[12] = GH_P4_P_64, p6[12] = GH_P6_P_64;
     const uint64_t* mod = (curve == GH_MNT4753_G1 || curve == GH_MNT4753_G2) ? p4 : p6;
     const size_t rec = (size_t)192 * deg + 1, words = (size_t)24 * deg;
@@ -347,23 +352,16 @@ int gh_bases_upload_wire(gh_curve_t curve, const uint8_t* bytes, size_t n_points
 
 int gh_bases_free(gh_bases_t handle) try {
     std::lock_guard<std::mutex> lk(g_mu);
-    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
-    if (!h || h->magic != 0x6768424au) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
-    if (h->d_points) hipFree(h->d_points);
-    if (h->d_inf) hipFree(h->d_inf);
-    if (h->d_table) hipFree(h->d_table);
-    if (h->d_dup_starts) hipFree(h->d_dup_starts);
-    if (h->d_dup_members) hipFree(h->d_dup_members);
-    if (h->d_dup_chunks) hipFree(h->d_dup_chunks);
-    h->magic = 0;
+    BasesBase* h = bases_of(handle);
+    if (!h) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
     delete h;
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_bases_precompute_rows(gh_bases_t handle, int window_bits, int max_rows) try {
     std::lock_guard<std::mutex> lk(g_mu);
-    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
-    if (!h || h->magic != 0x6768424au) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
+    BasesBase* h = bases_of(handle);
+    if (!h) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
     if (window_bits < 0 || window_bits == 1 || window_bits > 24) { g_err = "window must be 0 (auto) or in [2, 24]"; return GH_E_BAD_ARG; }
     if (max_rows < 0) { g_err = "max_rows must be 0 (no cap) or positive"; return GH_E_BAD_ARG; }
     const MsmOps* ops = ops_of(h->curve);
@@ -374,24 +372,24 @@ int gh_bases_precompute_rows(gh_bases_t handle, int window_bits, int max_rows) t
 } catch (...) { return gh_rt::api_exception(); }
 int gh_bases_precompute(gh_bases_t handle, int window_bits) { return gh_bases_precompute_rows(handle, window_bits, 0); }
 int gh_bases_table_rows(gh_bases_t handle) try {
-    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
-    return (h && h->magic == 0x6768424au && h->d_table) ? h->pre_W : 0;
+    const BasesBase* h = bases_of(handle);
+    return h && h->d_table ? h->pre_W : 0;
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_bases_precomputed_window(gh_bases_t handle) try {
-    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
-    return (h && h->magic == 0x6768424au && h->d_table) ? h->pre_c : 0;
+    const BasesBase* h = bases_of(handle);
+    return h && h->d_table ? h->pre_c : 0;
 } catch (...) { return gh_rt::api_exception(); }
 
 size_t gh_bases_len(gh_bases_t handle) try {
-    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
-    return (h && h->magic == 0x6768424au) ? h->n : 0;
+    const BasesBase* h = bases_of(handle);
+    return h ? h->n : 0;
 } catch (...) { (void)gh_rt::api_exception(); return 0; }
 
 int gh_msm_resident_dev(gh_bases_t handle, const void* d_scalars, size_t n_scalars, uint64_t* out_xyz) try {
     std::lock_guard<std::mutex> lk(g_mu);
-    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
-    if (!h || h->magic != 0x6768424au) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
+    BasesBase* h = bases_of(handle);
+    if (!h) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
     if (!out_xyz || (n_scalars && !d_scalars)) { g_err = "null argument"; return GH_E_BAD_ARG; }
     const MsmOps* ops = ops_of(h->curve);
     if (!ops) return GH_E_BAD_ARG;
@@ -407,11 +405,11 @@ int gh_msm_resident_dev_batch(const gh_bases_t* handles, const void* const* d_sc
     if (count == 0) return GH_OK;
     std::vector<BasesBase*> hs((size_t)count);
     for (int i = 0; i < count; i++) {
-        BasesBase* h = reinterpret_cast<BasesBase*>(handles[i]);
-        if (!h || h->magic != 0x6768424au) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
-        if (h->curve != reinterpret_cast<BasesBase*>(handles[0])->curve) { g_err = "a batch must stay on one curve"; return GH_E_BAD_ARG; }
-        if (n_scalars[i] && !d_scalars[i]) { g_err = "null argument"; return GH_E_BAD_ARG; }
+        BasesBase* h = bases_of(handles[i]);
+        if (!h) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
         hs[(size_t)i] = h;
+        if (h->curve != hs[0]->curve) { g_err = "a batch must stay on one curve"; return GH_E_BAD_ARG; }
+        if (n_scalars[i] && !d_scalars[i]) { g_err = "null argument"; return GH_E_BAD_ARG; }
     }
     const MsmOps* ops = ops_of(hs[0]->curve);
     if (!ops) return GH_E_BAD_ARG;
@@ -427,8 +425,8 @@ int gh_msm_resident_dev_batch(const gh_bases_t* handles, const void* const* d_sc
 int gh_msm_resident(gh_bases_t handle, const uint64_t* scalars, size_t n_scalars, uint64_t* out_xyz) try {
     // ONE critical section from staging the scalars to the result: the staging buffer is a shared pool slot
     std::lock_guard<std::mutex> lk(g_mu);
-    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
-    if (!h || h->magic != 0x6768424au) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
+    BasesBase* h = bases_of(handle);
+    if (!h) { g_err = "bad bases handle"; return GH_E_BAD_HANDLE; }
     if (!out_xyz || (n_scalars && !scalars)) { g_err = "null argument"; return GH_E_BAD_ARG; }
     const MsmOps* ops = ops_of(h->curve);
     if (!ops) return GH_E_BAD_ARG;
@@ -549,8 +547,7 @@ private:
 };
 
 KeyHash content_hash(gh_curve_t curve, const uint64_t* bases, const uint8_t* infinity, size_t n) {
-    const int deg = curve == GH_MNT4753_G2 ? 2 : (curve == GH_MNT6753_G2 ? 3 : 1);
-    const size_t words = n * (size_t)24 * deg;
+    const size_t words = n * (size_t)24 * curve_deg(curve);
     const HashSeeds& sd = hash_seeds();
     // chunks hashed in parallel, then the chunk hashes are hashed in order
     const size_t chunk = (size_t)1 << 16;
@@ -597,23 +594,11 @@ struct KeyCache {
 };
 KeyCache kc;
 size_t key_bytes(const BasesBase* h) {
-    const int deg = h->curve == GH_MNT4753_G2 ? 2 : (h->curve == GH_MNT6753_G2 ? 3 : 1);
-    const size_t pt = (size_t)208 * deg;
+    const size_t pt = (size_t)208 * curve_deg(h->curve);
     return h->n * pt + (h->d_inf ? h->n : 0) + (h->d_table ? (size_t)h->pre_W * h->n * pt : 0) + (size_t)4 * (h->n_dup_groups + 1 + h->n_dup_members);
 }
-void free_key(BasesBase* h) {
-    if (!h) return;
-    if (h->d_points) hipFree(h->d_points);
-    if (h->d_inf) hipFree(h->d_inf);
-    if (h->d_table) hipFree(h->d_table);
-    if (h->d_dup_starts) hipFree(h->d_dup_starts);
-    if (h->d_dup_members) hipFree(h->d_dup_members);
-    if (h->d_dup_chunks) hipFree(h->d_dup_chunks);
-    h->magic = 0;
-    delete h;
-}
 void cache_drop_all() {
-    for (auto& k : kc.e) free_key(k.key);
+    for (auto& k : kc.e) delete k.key;
     kc.e.clear();
     kc.st.entries = 0; kc.st.bytes = 0;
 }
@@ -629,7 +614,7 @@ void cache_fit(const BasesBase* keep) {
             if (kc.e[i].key != keep && (victim == kc.e.size() || kc.e[i].stamp < kc.e[victim].stamp)) victim = i;
         if (victim == kc.e.size()) return;           // only `keep` is left: a key larger than the budget stays for this call
         (void)sync_msm_streams();
-        free_key(kc.e[victim].key);
+        delete kc.e[victim].key;
         kc.e.erase(kc.e.begin() + (long)victim);
         kc.st.evictions++;
     }
@@ -797,7 +782,7 @@ int gh_msm_set_dedup(int on) try {
 } catch (...) { return gh_rt::api_exception(); }
 int gh_msm_get_window(gh_curve_t curve, size_t n) try {
     std::lock_guard<std::mutex> lk(g_mu);
-    return auto_window(n, curve == GH_MNT4753_G2 ? 2 : (curve == GH_MNT6753_G2 ? 3 : 1));
+    return auto_window(n, curve_deg(curve));
 } catch (...) { return gh_rt::api_exception(); }
 int gh_msm_batch_timing(int index, gh_msm_timing_t* out) try {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -862,21 +847,17 @@ int gh_witness_map_dev(gh_field_t field, void* d_a, void* d_b, void* d_c, uint32
 
 int gh_witness_map(gh_field_t field, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint32_t log_n,
                    const uint64_t* d1, const uint64_t* d2, const uint64_t* d3, uint64_t* h) try {
+    std::lock_guard<std::mutex> lk(g_mu);
     if (!a || !b || !c || !h || !d1 || !d2 || !d3) { g_err = "null argument"; return GH_E_BAD_ARG; }
     if (log_n >= 31) { g_err = "domain too large"; return GH_E_UNSUPPORTED; }
-    const size_t N = (size_t)1 << log_n, bytes = N * 96;
-    void *da = nullptr, *db = nullptr, *dc = nullptr, *dh = nullptr;
-    int rc = gh_dev_alloc(&da, bytes);
-    if (!rc) rc = gh_dev_alloc(&db, bytes);
-    if (!rc) rc = gh_dev_alloc(&dc, bytes);
-    if (!rc) rc = gh_dev_alloc(&dh, bytes + 96);
-    if (!rc) rc = gh_dev_upload(da, a, bytes);
-    if (!rc) rc = gh_dev_upload(db, b, bytes);
-    if (!rc) rc = gh_dev_upload(dc, c, bytes);
-    if (!rc) rc = gh_witness_map_dev(field, da, db, dc, log_n, d1, d2, d3, dh);
-    if (!rc) rc = gh_dev_download(h, dh, bytes + 96);
-    gh_dev_free(da); gh_dev_free(db); gh_dev_free(dc); gh_dev_free(dh);
-    return rc;
+    const size_t bytes = ((size_t)1 << log_n) * 96;
+    int rc = ensure_init();
+    if (rc) return rc;
+    DevMem da, db, dc, dh;
+    if ((rc = da.alloc(bytes)) || (rc = db.alloc(bytes)) || (rc = dc.alloc(bytes)) || (rc = dh.alloc(bytes + 96))) return rc;
+    if ((rc = to_device(da.get(), a, bytes)) || (rc = to_device(db.get(), b, bytes)) || (rc = to_device(dc.get(), c, bytes))) return rc;
+    if ((rc = witness_map(field, da.get(), db.get(), dc.get(), log_n, d1, d2, d3, dh.get()))) return rc;
+    return to_host_sync(h, dh.get(), bytes + 96);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_sap_witness_map_dev(gh_field_t field, void* d_a, void* d_c, uint32_t log_n, const uint64_t* d1, const uint64_t* d2, void* d_h) try {
@@ -888,19 +869,17 @@ int gh_sap_witness_map_dev(gh_field_t field, void* d_a, void* d_c, uint32_t log_
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_sap_witness_map(gh_field_t field, const uint64_t* a, const uint64_t* c, uint32_t log_n, const uint64_t* d1, const uint64_t* d2, uint64_t* h) try {
-    if (!a || !c || !h || !d1 || !d2) { std::lock_guard<std::mutex> lk(g_mu); g_err = "null argument"; return GH_E_BAD_ARG; }
-    if (log_n >= 31) { std::lock_guard<std::mutex> lk(g_mu); g_err = "domain too large"; return GH_E_UNSUPPORTED; }
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!a || !c || !h || !d1 || !d2) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (log_n >= 31) { g_err = "domain too large"; return GH_E_UNSUPPORTED; }
     const size_t bytes = ((size_t)1 << log_n) * 96;
-    void *da = nullptr, *dc = nullptr, *dh = nullptr;
-    int rc = gh_dev_alloc(&da, bytes);
-    if (!rc) rc = gh_dev_alloc(&dc, bytes);
-    if (!rc) rc = gh_dev_alloc(&dh, bytes + 96);
-    if (!rc) rc = gh_dev_upload(da, a, bytes);
-    if (!rc) rc = gh_dev_upload(dc, c, bytes);
-    if (!rc) rc = gh_sap_witness_map_dev(field, da, dc, log_n, d1, d2, dh);
-    if (!rc) rc = gh_dev_download(h, dh, bytes + 96);
-    gh_dev_free(da); gh_dev_free(dc); gh_dev_free(dh);
-    return rc;
+    int rc = ensure_init();
+    if (rc) return rc;
+    DevMem da, dc, dh;
+    if ((rc = da.alloc(bytes)) || (rc = dc.alloc(bytes)) || (rc = dh.alloc(bytes + 96))) return rc;
+    if ((rc = to_device(da.get(), a, bytes)) || (rc = to_device(dc.get(), c, bytes))) return rc;
+    if ((rc = sap_witness_map(field, da.get(), dc.get(), log_n, d1, d2, dh.get()))) return rc;
+    return to_host_sync(h, dh.get(), bytes + 96);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_batch_inverse_dev(gh_field_t field, void* d_a, size_t n) try {
@@ -913,14 +892,13 @@ int gh_batch_inverse_dev(gh_field_t field, void* d_a, size_t n) try {
 
 int gh_batch_inverse(gh_field_t field, uint64_t* a, size_t n) try {
     if (n == 0) return GH_OK;
-    if (!a) { std::lock_guard<std::mutex> lk(g_mu); g_err = "null argument"; return GH_E_BAD_ARG; }
-    void* da = nullptr;
-    int rc = gh_dev_alloc(&da, n * 96);
-    if (!rc) rc = gh_dev_upload(da, a, n * 96);
-    if (!rc) rc = gh_batch_inverse_dev(field, da, n);
-    if (!rc) rc = gh_dev_download(a, da, n * 96);
-    gh_dev_free(da);
-    return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!a) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    int rc = ensure_init();
+    if (rc) return rc;
+    DevMem da;
+    if ((rc = da.alloc(n * 96)) || (rc = to_device(da.get(), a, n * 96)) || (rc = batch_inverse(field, da.get(), n))) return rc;
+    return to_host_sync(a, da.get(), n * 96);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_lagrange_coefficients_dev(gh_field_t field, uint32_t log_n, const uint64_t* tau12, void* d_out) try {
@@ -933,15 +911,15 @@ int gh_lagrange_coefficients_dev(gh_field_t field, uint32_t log_n, const uint64_
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_lagrange_coefficients(gh_field_t field, uint32_t log_n, const uint64_t* tau12, uint64_t* out) try {
-    if (!tau12 || !out) { std::lock_guard<std::mutex> lk(g_mu); g_err = "null argument"; return GH_E_BAD_ARG; }
-    if (log_n >= 31) { std::lock_guard<std::mutex> lk(g_mu); g_err = "domain too large"; return GH_E_UNSUPPORTED; }
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!tau12 || !out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (log_n >= 31) { g_err = "domain too large"; return GH_E_UNSUPPORTED; }
     const size_t bytes = ((size_t)1 << log_n) * 96;
-    void* d = nullptr;
-    int rc = gh_dev_alloc(&d, bytes);
-    if (!rc) rc = gh_lagrange_coefficients_dev(field, log_n, tau12, d);
-    if (!rc) rc = gh_dev_download(out, d, bytes);
-    gh_dev_free(d);
-    return rc;
+    int rc = ensure_init();
+    if (rc) return rc;
+    DevMem d;
+    if ((rc = d.alloc(bytes)) || (rc = lagrange_coefficients(field, log_n, tau12, d.get()))) return rc;
+    return to_host_sync(out, d.get(), bytes);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_measure_fpmul_peak(double* products_per_s) try {
@@ -978,30 +956,25 @@ int gh_vec_scale_dev(gh_field_t field, void* d_a, const uint64_t* scalar12, size
 
 int gh_vec_mul(gh_field_t field, uint64_t* a, const uint64_t* b, size_t n) try {
     if (n == 0) return GH_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
     if (!a || !b) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    void *da = nullptr, *db = nullptr;
-    int rc;
-    if ((rc = gh_dev_alloc(&da, n * 96))) return rc;
-    if ((rc = gh_dev_alloc(&db, n * 96))) { gh_dev_free(da); return rc; }
-    rc = gh_dev_upload(da, a, n * 96);
-    if (!rc) rc = gh_dev_upload(db, b, n * 96);
-    if (!rc) rc = gh_vec_mul_dev(field, da, db, n);
-    if (!rc) rc = gh_dev_download(a, da, n * 96);
-    gh_dev_free(da);
-    gh_dev_free(db);
-    return rc;
+    int rc = ensure_init();
+    if (rc) return rc;
+    DevMem da, db;
+    if ((rc = da.alloc(n * 96)) || (rc = db.alloc(n * 96))) return rc;
+    if ((rc = to_device(da.get(), a, n * 96)) || (rc = to_device(db.get(), b, n * 96))) return rc;
+    if ((rc = vec_op(field, 0, da.get(), db.get(), nullptr, n))) return rc;
+    return to_host_sync(a, da.get(), n * 96);
 } catch (...) { return gh_rt::api_exception(); }
 int gh_vec_scale(gh_field_t field, uint64_t* a, const uint64_t* scalar12, size_t n) try {
     if (n == 0) return GH_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
     if (!a || !scalar12) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    void* da = nullptr;
-    int rc;
-    if ((rc = gh_dev_alloc(&da, n * 96))) return rc;
-    rc = gh_dev_upload(da, a, n * 96);
-    if (!rc) rc = gh_vec_scale_dev(field, da, scalar12, n);
-    if (!rc) rc = gh_dev_download(a, da, n * 96);
-    gh_dev_free(da);
-    return rc;
+    int rc = ensure_init();
+    if (rc) return rc;
+    DevMem da;
+    if ((rc = da.alloc(n * 96)) || (rc = to_device(da.get(), a, n * 96)) || (rc = vec_op(field, 2, da.get(), nullptr, scalar12, n))) return rc;
+    return to_host_sync(a, da.get(), n * 96);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_dev_alloc(void** d_ptr, size_t bytes) try {
@@ -1024,7 +997,7 @@ int gh_dev_upload(void* d_dst, const void* h_src, size_t bytes) try {
     if (!d_dst || !h_src) { g_err = "null argument"; return GH_E_BAD_ARG; }
     int rc = ensure_init();
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, g.stream));
+    if ((rc = to_device(d_dst, h_src, bytes))) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
@@ -1034,9 +1007,7 @@ int gh_dev_download(void* h_dst, const void* d_src, size_t bytes) try {
     if (!h_dst || !d_src) { g_err = "null argument"; return GH_E_BAD_ARG; }
     int rc = ensure_init();
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    return GH_OK;
+    return to_host_sync(h_dst, d_src, bytes);
 } catch (...) { return gh_rt::api_exception(); }
 int gh_dev_trim(void) try {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -1054,6 +1025,7 @@ int gh_dev_sync(void) try {
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_proj_add(gh_curve_t curve, uint64_t* acc_xyz, const uint64_t* p_xyz) try {
+    std::lock_guard<std::mutex> lk(g_mu);
     if (!acc_xyz || !p_xyz) { g_err = "null argument"; return GH_E_BAD_ARG; }
     const MsmOps* ops = ops_of(curve);
     if (!ops) return GH_E_BAD_ARG;
@@ -1061,6 +1033,7 @@ int gh_proj_add(gh_curve_t curve, uint64_t* acc_xyz, const uint64_t* p_xyz) try 
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_proj_mul(gh_curve_t curve, const uint64_t* p_xyz, const uint64_t* scalar12, uint64_t* out_xyz) try {
+    std::lock_guard<std::mutex> lk(g_mu);
     if (!p_xyz || !scalar12 || !out_xyz) { g_err = "null argument"; return GH_E_BAD_ARG; }
     const MsmOps* ops = ops_of(curve);
     if (!ops) return GH_E_BAD_ARG;
@@ -1068,6 +1041,7 @@ int gh_proj_mul(gh_curve_t curve, const uint64_t* p_xyz, const uint64_t* scalar1
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_proj_neg(gh_curve_t curve, uint64_t* xyz) try {
+    std::lock_guard<std::mutex> lk(g_mu);
     if (!xyz) { g_err = "null argument"; return GH_E_BAD_ARG; }
     const MsmOps* ops = ops_of(curve);
     if (!ops) return GH_E_BAD_ARG;
@@ -1075,6 +1049,7 @@ int gh_proj_neg(gh_curve_t curve, uint64_t* xyz) try {
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_proj_to_affine(gh_curve_t curve, const uint64_t* xyz, uint64_t* out_xy, uint8_t* is_infinity) try {
+    std::lock_guard<std::mutex> lk(g_mu);
     if (!xyz || !out_xy || !is_infinity) { g_err = "null argument"; return GH_E_BAD_ARG; }
     const MsmOps* ops = ops_of(curve);
     if (!ops) return GH_E_BAD_ARG;

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
+#include <memory>
 #include <type_traits>
 #include <vector>
 #include "runtime.h"
@@ -14,12 +15,6 @@
 
 namespace gh_rt {
 using namespace gh;
-
-template <class C> struct CurveId;
-template <> struct CurveId<Mnt4G1> { static constexpr gh_curve_t id = GH_MNT4753_G1; };
-template <> struct CurveId<Mnt4G2> { static constexpr gh_curve_t id = GH_MNT4753_G2; };
-template <> struct CurveId<Mnt6G1> { static constexpr gh_curve_t id = GH_MNT6753_G1; };
-template <> struct CurveId<Mnt6G2> { static constexpr gh_curve_t id = GH_MNT6753_G2; };
 
 template <class C> void proj_to_abi_host(uint64_t* out, const Proj<C>& p) {
     typedef typename C::F F;
@@ -90,30 +85,31 @@ template <class C> int device_salts(Aff<C>** out) {
 template <class C>
 int upload_bases(const uint64_t* bases, const uint8_t* infinity, size_t n, int canonical, BasesBase** out) {
     typedef typename C::F F;
-    BasesBase* h = new BasesBase();
+    std::unique_ptr<BasesBase> h(new BasesBase());     // an early return frees the key and what it holds by then
     h->curve = CurveId<C>::id;
     h->n = n;
     if (n > 0) {
         const size_t in_bytes = n * (size_t)(48 * F::DEG) * 4;
-        void* d_in = nullptr;
-        HIPCHK(hipMalloc(&h->d_points, n * sizeof(Aff<C>)));
-        HIPCHK(hipMalloc(&d_in, in_bytes));
-        HIPCHK(hipMemcpyAsync(d_in, bases, in_bytes, hipMemcpyHostToDevice, g.stream));
+        DevMem points, d_in, inf;
+        int rc;
+        if ((rc = points.alloc(n * sizeof(Aff<C>))) || (rc = d_in.alloc(in_bytes))) return rc;
+        h->d_points = points.release();
+        HIPCHK(hipMemcpyAsync(d_in.get(), bases, in_bytes, hipMemcpyHostToDevice, g.stream));
         GH_LAUNCH((msm_convert_bases_kernel<C>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream,
-                           (const uint32_t*)d_in, (Aff<C>*)h->d_points, n, canonical);
+                           d_in.as<const uint32_t>(), (Aff<C>*)h->d_points, n, canonical);
         HIPCHK(hipGetLastError());
         if (infinity) {
             bool any = false;
             for (size_t i = 0; i < n && !any; i++) any = infinity[i] != 0;
             if (any) {
-                HIPCHK(hipMalloc((void**)&h->d_inf, n));
+                if ((rc = inf.alloc(n))) return rc;
+                h->d_inf = (uint8_t*)inf.release();
                 HIPCHK(hipMemcpyAsync(h->d_inf, infinity, n, hipMemcpyHostToDevice, g.stream));
             }
         }
         HIPCHK(hipStreamSynchronize(g.stream));
-        HIPCHK(hipFree(d_in));
     }
-    *out = h;
+    *out = h.release();
     return GH_OK;
 }
 
@@ -143,13 +139,13 @@ inline int precompute_window(size_t n, int deg) {
 }
 
 // Groups of equal bases (msm_kernels.h "equal bases"): hashed on the device, grouped on the host, verified limb for limb on the
-// device.  Optional: any failure leaves the key without groups (every base its own).  Called when the shift table is built --
-// a key that gets a table is a key that is used again.  GH_DEDUP=0 switches it off (A/B).
+// device.  Optional: any failure leaves the key without groups (every base its own) and the caller ignores the status.  Called
+// when the shift table is built -- a key that gets a table is a key that is used again.  GH_DEDUP=0 switches it off (A/B).
 template <class C>
 int dedup_bases(BasesBase* h) {
-    if (h->d_dup_starts) { (void)hipFree(h->d_dup_starts); h->d_dup_starts = nullptr; }
-    if (h->d_dup_members) { (void)hipFree(h->d_dup_members); h->d_dup_members = nullptr; }
-    if (h->d_dup_chunks) { (void)hipFree(h->d_dup_chunks); h->d_dup_chunks = nullptr; }
+    dev_free(h->d_dup_starts);
+    dev_free(h->d_dup_members);
+    dev_free(h->d_dup_chunks);
     h->n_dup_groups = h->n_dup_members = h->n_dup_chunks = 0;
     static const bool off = env_int("GH_DEDUP", 1) == 0;
     const size_t n = h->n;
@@ -183,24 +179,21 @@ int dedup_bases(BasesBase* h) {
     }
     if (starts.empty()) return GH_OK;
     starts.push_back((uint32_t)members.size());
-    uint32_t *d_st = nullptr, *d_mem = nullptr;
+    DevMem d_st, d_mem, d_ch;          // become the key's lists at the very end; any return before that frees them
     uint8_t* d_flags = nullptr;
-    HIPCHK(hipMalloc((void**)&d_st, starts.size() * 4));
-    if (hipMalloc((void**)&d_mem, members.size() * 4) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_st); return GH_OK; }
-    if ((rc = pool_get("dedup_flags", members.size() + 16, (void**)&d_flags))) { (void)hipFree(d_st); (void)hipFree(d_mem); return GH_OK; }
+    if ((rc = d_st.alloc(starts.size() * 4)) || (rc = d_mem.alloc(members.size() * 4)) ||
+        (rc = pool_get("dedup_flags", members.size() + 16, (void**)&d_flags))) return rc;
     const uint32_t ng = (uint32_t)starts.size() - 1;
-    hipError_t e = hipMemcpyAsync(d_st, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_mem, members.data(), members.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, members.size(), st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((msm_dup_verify_kernel<C>), dim3(ng), dim3(256), 0, st, (const Aff<C>*)h->d_points, (const uint32_t*)d_st, ng, d_mem, d_flags);
-        e = hipGetLastError();
-    }
+    HIPCHK(hipMemcpyAsync(d_st.get(), starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_mem.get(), members.data(), members.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_flags, 0, members.size(), st));
+    hipLaunchKernelGGL((msm_dup_verify_kernel<C>), dim3(ng), dim3(256), 0, st, (const Aff<C>*)h->d_points, d_st.as<const uint32_t>(), ng,
+                       d_mem.as<uint32_t>(), d_flags);
+    HIPCHK(hipGetLastError());
     std::vector<uint8_t> flags(members.size());
-    if (e == hipSuccess) e = hipMemcpyAsync(flags.data(), d_flags, members.size(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(members.data(), d_mem, members.size() * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_st); (void)hipFree(d_mem); return GH_OK; }
+    HIPCHK(hipMemcpyAsync(flags.data(), d_flags, members.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(members.data(), d_mem.get(), members.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     bool collision = false;
     for (uint8_t f : flags) collision |= f != 0;
     if (collision) {      // equal 128-bit hashes over different abscissae: drop those members and rebuild the lists
@@ -210,13 +203,11 @@ int dedup_bases(BasesBase* h) {
             for (uint32_t j = starts[gi]; j < starts[gi + 1]; j++) if (!flags[j]) mem2.push_back(members[j]);
             if (mem2.size() - b0 >= 2) st2.push_back((uint32_t)b0); else mem2.resize(b0);
         }
-        (void)hipFree(d_st); (void)hipFree(d_mem);
         if (st2.empty()) return GH_OK;
         st2.push_back((uint32_t)mem2.size());
-        HIPCHK(hipMalloc((void**)&d_st, st2.size() * 4));
-        if (hipMalloc((void**)&d_mem, mem2.size() * 4) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_st); return GH_OK; }
-        HIPCHK(hipMemcpy(d_st, st2.data(), st2.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_mem, mem2.data(), mem2.size() * 4, hipMemcpyHostToDevice));
+        if ((rc = d_st.alloc(st2.size() * 4)) || (rc = d_mem.alloc(mem2.size() * 4))) return rc;
+        HIPCHK(hipMemcpy(d_st.get(), st2.data(), st2.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_mem.get(), mem2.data(), mem2.size() * 4, hipMemcpyHostToDevice));
         starts.swap(st2); members.swap(mem2);
     }
     // chunks of at most MSM_DUP_CHUNK members for the summation (msm_merge_scalars_kernel), then the chunk offsets per group
@@ -232,15 +223,11 @@ int dedup_bases(BasesBase* h) {
     goff[ngf] = (uint32_t)(ch.size() / 3);
     const uint32_t nch = goff[ngf];
     ch.insert(ch.end(), goff.begin(), goff.end());
-    uint32_t* d_ch = nullptr;
-    if (hipMalloc((void**)&d_ch, ch.size() * 4) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d_st); (void)hipFree(d_mem); return GH_OK; }
-    if (hipMemcpy(d_ch, ch.data(), ch.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFree(d_st); (void)hipFree(d_mem); (void)hipFree(d_ch);
-        return GH_OK;
-    }
-    h->d_dup_starts = d_st;
-    h->d_dup_members = d_mem;
-    h->d_dup_chunks = d_ch;
+    if ((rc = d_ch.alloc(ch.size() * 4))) return rc;
+    HIPCHK(hipMemcpy(d_ch.get(), ch.data(), ch.size() * 4, hipMemcpyHostToDevice));
+    h->d_dup_starts = (uint32_t*)d_st.release();
+    h->d_dup_members = (uint32_t*)d_mem.release();
+    h->d_dup_chunks = (uint32_t*)d_ch.release();
     h->n_dup_groups = ngf;
     h->n_dup_members = (uint32_t)members.size();
     h->n_dup_chunks = nch;
@@ -250,7 +237,9 @@ int dedup_bases(BasesBase* h) {
 template <class C>
 int precompute_bases(BasesBase* h, int c_req, int max_rows) {
     typedef typename C::FC::T FT;
-    if (h->d_table) { HIPCHK(hipFree(h->d_table)); h->d_table = nullptr; h->pre_c = h->pre_W = 0; h->pre_G = 1; }
+    dev_free(h->d_table);
+    h->pre_c = h->pre_W = 0;
+    h->pre_G = 1;
     const size_t n = h->n;
     if (n == 0) return GH_OK;
     // Partial table (max_rows > 0, or GH_TABLE_ROWS for every table of the process): at most that many rows, row j = 2^(c G j) P with
@@ -287,14 +276,15 @@ int precompute_bases(BasesBase* h, int c_req, int max_rows) {
         g_err = "not enough device memory for the precomputed table (GH_TEST_TABLE_NOMEM)";
         return GH_E_NOMEM;
     }
-    Aff<C>* table = nullptr;
+    DevMem table_mem;                 // becomes h->d_table once every row is built
     FT *zs = nullptr, *zp = nullptr;
     uint32_t* bad = nullptr;
     int rc;
-    HIPCHK(hipMalloc((void**)&table, (size_t)W * n * sizeof(Aff<C>)));
-    if ((rc = pool_get("pre_zs", (size_t)(W - 1) * slab * sizeof(FT) + 8, (void**)&zs)) ||
+    if ((rc = table_mem.alloc((size_t)W * n * sizeof(Aff<C>))) ||
+        (rc = pool_get("pre_zs", (size_t)(W - 1) * slab * sizeof(FT) + 8, (void**)&zs)) ||
         (rc = pool_get("pre_zp", (size_t)(W - 1) * slab * sizeof(FT) + 8, (void**)&zp)) ||
-        (rc = pool_get("pre_bad", 16, (void**)&bad))) { hipFree(table); return rc; }
+        (rc = pool_get("pre_bad", 16, (void**)&bad))) return rc;
+    Aff<C>* const table = table_mem.as<Aff<C>>();
     hipStream_t st = g.stream;
     hipError_t e = hipMemcpyAsync(table, h->d_points, n * sizeof(Aff<C>), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 4, st);
@@ -303,7 +293,7 @@ int precompute_bases(BasesBase* h, int c_req, int max_rows) {
         {   // the table builders carry 2-9 KB of stack per lane: no dispatch the card cannot back with scratch (runtime.h scratch_guard)
             const void* kfn = C::F::DEG == 1 ? (const void*)(msm_precompute_jac_kernel<C, typename C::F>)
                                              : (const void*)(msm_precompute_jac_kernel<C, typename C::FC>);
-            if (int grc = scratch_guard(kfn, (cnt + 255) / 256 * 256)) { hipFree(table); return grc; }
+            if (int grc = scratch_guard(kfn, (cnt + 255) / 256 * 256)) return grc;
         }
         if constexpr (C::F::DEG == 1)
             hipLaunchKernelGGL((msm_precompute_jac_kernel<C, typename C::F>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st,
@@ -316,17 +306,17 @@ int precompute_bases(BasesBase* h, int c_req, int max_rows) {
     uint32_t hbad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { hipFree(table); g_err = std::string("precompute failed: ") + hipGetErrorString(e); return GH_E_HIP; }
+    if (e != hipSuccess) { g_err = std::string("precompute failed: ") + hipGetErrorString(e); return GH_E_HIP; }
     if (hbad) {   // a base of 2-power order: 2^(c w) P hits infinity, which an affine table cannot hold
-        hipFree(table);
         g_err = "precompute: a base has 2-power order; the key stays on the per-window path";
         return GH_E_UNSUPPORTED;
     }
-    h->d_table = table;
+    h->d_table = table_mem.release();
     h->pre_c = c;
     h->pre_W = W;
     h->pre_G = G;
-    (void)dedup_bases<C>(h);      // equal bases of the key: their scalars are added up before every MSM (optional: failures leave none)
+    // equal bases of the key: their scalars are added up before every MSM (optional: a failure leaves none, and no pending HIP error)
+    if (dedup_bases<C>(h)) (void)hipGetLastError();
     return GH_OK;
 }
 
@@ -1222,22 +1212,17 @@ template <class C>
 int msm_host(const uint64_t* bases, const uint8_t* infinity, size_t n_bases, const uint64_t* scalars, size_t n_scalars,
              uint64_t* out_xyz) {
     size_t n = n_bases < n_scalars ? n_bases : n_scalars;
-    BasesBase* h = nullptr;
-    int rc = upload_bases<C>(bases, infinity, n, 0, &h);
+    BasesBase* uploaded = nullptr;
+    int rc = upload_bases<C>(bases, infinity, n, 0, &uploaded);
     if (rc) return rc;
+    const std::unique_ptr<BasesBase> h(uploaded);      // the key of this one call
     void* d_s = nullptr;
     if (n > 0) {
-        rc = pool_get("scalars", n * 96, &d_s);
-        if (!rc) {
-            hipError_t e = hipMemcpyAsync(d_s, scalars, n * 96, hipMemcpyHostToDevice, g.stream);
-            if (e != hipSuccess) { g_err = hipGetErrorString(e); rc = GH_E_HIP; }
-        }
+        if ((rc = pool_get("scalars", n * 96, &d_s))) return rc;
+        hipError_t e = hipMemcpyAsync(d_s, scalars, n * 96, hipMemcpyHostToDevice, g.stream);
+        if (e != hipSuccess) { g_err = hipGetErrorString(e); return GH_E_HIP; }
     }
-    if (!rc) rc = msm_run<C>(h, d_s, n, out_xyz);
-    if (h->d_points) hipFree(h->d_points);
-    if (h->d_inf) hipFree(h->d_inf);
-    delete h;
-    return rc;
+    return msm_run<C>(h.get(), d_s, n, out_xyz);
 }
 
 

@@ -34,14 +34,10 @@ template <class P> int build_pow_table(Fp* tab, int log_n, const Fp& first, Fp b
 // Tables are built into locals and committed to the Domain only after every allocation and launch has
 // succeeded: a failed build (e.g. out of memory next to a 100 GB shift table) leaves no half-initialised
 // entry behind for the next call to trip over.
-template <class P> int build_table_checked(Fp** slot, int log_n, const Fp& first, const Fp& base) {
-    const size_t N = (size_t)1 << log_n;
-    Fp* t = nullptr;
-    HIPCHK(hipMalloc((void**)&t, N * sizeof(Fp)));
-    int rc = build_pow_table<P>(t, log_n, first, base);
-    if (!rc && hipStreamSynchronize(g.stream) != hipSuccess) { g_err = "building a domain table failed"; rc = GH_E_HIP; }
-    if (rc) { hipFree(t); return rc; }
-    *slot = t;
+template <class P> int build_table_checked(DevMem& t, int log_n, const Fp& first, const Fp& base) {
+    int rc;
+    if ((rc = t.alloc(((size_t)1 << log_n) * sizeof(Fp))) || (rc = build_pow_table<P>(t.as<Fp>(), log_n, first, base))) return rc;
+    if (hipStreamSynchronize(g.stream) != hipSuccess) { g_err = "building a domain table failed"; return GH_E_HIP; }
     return GH_OK;
 }
 
@@ -58,29 +54,28 @@ template <class P> int get_domain(int fidx, int log_n, bool need_coset, bool nee
         Fp n_int = fp_one<P>();
         for (int i = 0; i < log_n; i++) n_int = fp_dbl<P>(n_int);
         d.size_inv = host_fp_inv<P>(n_int);
-        hipError_t e = hipMalloc((void**)&d.scratch, N * 96);
-        if (e != hipSuccess) { g_err = std::string("domain scratch: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? GH_E_NOMEM : GH_E_HIP; }
-        int rc = build_table_checked<P>(&d.tw, log_n, fp_one<P>(), w);
-        if (rc) { hipFree(d.scratch); return rc; }
-        if (hipMalloc((void**)&d.d_size_inv, 128) != hipSuccess ||
-            hipMemcpy(d.d_size_inv, &d.size_inv, sizeof(Fp), hipMemcpyHostToDevice) != hipSuccess) {
-            g_err = "domain constants: device allocation failed";
-            hipFree(d.scratch); hipFree(d.tw); if (d.d_size_inv) hipFree(d.d_size_inv);
-            return GH_E_NOMEM;
-        }
+        DevMem scratch, tw, size_inv;
+        int rc;
+        if ((rc = scratch.alloc(N * 96)) || (rc = build_table_checked<P>(tw, log_n, fp_one<P>(), w)) || (rc = size_inv.alloc(128))) return rc;
+        HIPCHK(hipMemcpy(size_inv.get(), &d.size_inv, sizeof(Fp), hipMemcpyHostToDevice));
+        d.scratch = (uint32_t*)scratch.release();
+        d.tw = (Fp*)tw.release();
+        d.d_size_inv = (Fp*)size_inv.release();
         it = g.domains[fidx].emplace(log_n, d).first;
     }
     Domain& d = it->second;
     if (need_coset && !d.coset) {
         Fp gen = fp_from_abi<P>(reinterpret_cast<const uint32_t*>(FieldConsts<P>::gen_m()));
-        int rc = build_table_checked<P>(&d.coset, log_n, fp_one<P>(), gen);
-        if (rc) return rc;
+        DevMem t;
+        if (int rc = build_table_checked<P>(t, log_n, fp_one<P>(), gen)) return rc;
+        d.coset = (Fp*)t.release();
     }
     if (need_coset_inv && !d.coset_inv) {
         Fp gen = fp_from_abi<P>(reinterpret_cast<const uint32_t*>(FieldConsts<P>::gen_m()));
         Fp gi = host_fp_inv<P>(gen);
-        int rc = build_table_checked<P>(&d.coset_inv, log_n, d.size_inv, gi);
-        if (rc) return rc;
+        DevMem t;
+        if (int rc = build_table_checked<P>(t, log_n, d.size_inv, gi)) return rc;
+        d.coset_inv = (Fp*)t.release();
     }
     *out = &d;
     return GH_OK;
@@ -114,11 +109,12 @@ template <class P> int fft_run(int fidx, void* d_data, uint32_t log_n, uint32_t 
     // Ping-pong: with an even number of passes the caller's vector and the domain's scratch alternate; with an odd number (2^24:
     // three) a second scratch vector lets the last pass write into the caller's vector instead of a 3.2 GB copy at the end.
     if (P_ >= 3 && (P_ & 1) && !d->scratch2 && !d->scratch2_failed) {
-        if (hipMalloc((void**)&d->scratch2, ((size_t)96) << log_n) != hipSuccess) {
+        DevMem s2;
+        if (s2.alloc(((size_t)96) << log_n)) {
             (void)hipGetLastError();
-            d->scratch2 = nullptr;
             d->scratch2_failed = true;
         }
+        d->scratch2 = (uint32_t*)s2.release();
     }
     const bool three = P_ >= 3 && (P_ & 1) && d->scratch2;
     uint32_t* bufs[2] = {(uint32_t*)d_data, d->scratch};
@@ -289,11 +285,11 @@ template <class P> int lagrange_t(int fidx, uint32_t log_n, const uint64_t* tau1
     const dim3 grid((unsigned)((N + 255) / 256)), blk(256);
     Fp one_tab = fp_one<P>();
     const Fp* tw = nullptr;
-    Fp* tw1 = nullptr;
+    DevMem tw1;
     if (log_n == 0) {                      // size-1 domain: w^0 = 1, no table
-        HIPCHK(hipMalloc((void**)&tw1, sizeof(Fp)));
-        HIPCHK(hipMemcpy(tw1, &one_tab, sizeof(Fp), hipMemcpyHostToDevice));
-        tw = tw1;
+        if (int rc = tw1.alloc(sizeof(Fp))) return rc;
+        HIPCHK(hipMemcpy(tw1.get(), &one_tab, sizeof(Fp), hipMemcpyHostToDevice));
+        tw = tw1.as<Fp>();
     } else {
         Domain* d;
         int rc = get_domain<P>(fidx, (int)log_n, false, false, &d);
@@ -313,7 +309,6 @@ template <class P> int lagrange_t(int fidx, uint32_t log_n, const uint64_t* tau1
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    if (tw1) (void)hipFree(tw1);
     if (!rc && e != hipSuccess) { g_err = std::string("lagrange coefficients: ") + hipGetErrorString(e); rc = GH_E_HIP; }
     return rc;
 }

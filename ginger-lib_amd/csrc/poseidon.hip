@@ -211,8 +211,10 @@ template <class P> Fp to_internal(const uint64_t* x) { return fp_from_abi<P>((co
 int prepare(gh_poseidon* h) {
     if (int rc = gh_rt::ensure_init()) return rc;
     if (!h->dev) {
-        HIPCHK(hipMalloc(&h->dev, h->host.size() * sizeof(Fp)));
-        HIPCHK(hipMemcpy(h->dev, h->host.data(), h->host.size() * sizeof(Fp), hipMemcpyHostToDevice));
+        gh_rt::DevMem dev;          // the handle's only once the constants are in it
+        if (int rc = dev.alloc(h->host.size() * sizeof(Fp))) return rc;
+        HIPCHK(hipMemcpy(dev.get(), h->host.data(), h->host.size() * sizeof(Fp), hipMemcpyHostToDevice));
+        h->dev = (Fp*)dev.release();
     }
     if (!h->have_empty) {
         uint64_t one[12];
@@ -281,7 +283,7 @@ int gh_poseidon_free(gh_poseidon_t h) try {
     std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
     if (!h) return GH_OK;
     if (!valid(h)) { g_err = "not a Poseidon handle"; return GH_E_BAD_HANDLE; }
-    if (h->dev) (void)hipFree(h->dev);
+    gh_rt::dev_free(h->dev);
     h->magic = 0;
     delete h;
     return GH_OK;

@@ -14,8 +14,15 @@
 #include "fp29.h"
 
 struct gh_poseidon;
+namespace gh { struct Mnt4G1; struct Mnt4G2; struct Mnt6G1; struct Mnt6G2; }   // the curve policies (ec29.h)
 
 namespace gh_rt {
+
+// hipFree of a device pointer held in a struct, which is left null.  hipFree waits for the device first.
+template <class T> void dev_free(T*& p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+}
 
 struct Domain {
     int log_n = 0;
@@ -27,6 +34,9 @@ struct Domain {
     uint32_t* scratch = nullptr;
     uint32_t* scratch2 = nullptr;  // second ping-pong vector: an odd number of passes ends in the caller's buffer without a copy
     bool scratch2_failed = false;
+    // A Domain lives inside the static context, so it holds raw pointers and is released by gh_shutdown, never by a destructor
+    // (which would run after the HIP runtime is gone).  Builders fill it from local DevMem owners on success only (ntt.hip).
+    void release() { dev_free(tw); dev_free(coset); dev_free(coset_inv); dev_free(d_size_inv); dev_free(scratch); dev_free(scratch2); }
 };
 
 struct DevBuf {
@@ -122,7 +132,50 @@ int scratch_guard(const void* kernel, size_t threads);
         }                                                                                    \
     } while (0)
 
+// Owner of one hipMalloc allocation: whatever way a function is left -- the early returns inside HIPCHK and GH_LAUNCH included
+// -- the destructor frees it.  hipFree waits for the device, so nothing that still runs can read freed memory.  For locals and
+// for members of heap handles only: an object with static storage duration would free after the HIP runtime is gone, so statics
+// keep raw pointers and a g.at_shutdown hook.  release() hands the pointer to a longer-lived struct once a build has succeeded.
+class DevMem {
+public:
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    DevMem(DevMem&& o) noexcept : p_(o.release()) {}
+    DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { reset(); p_ = o.release(); } return *this; }
+    ~DevMem() { reset(); }
+    int alloc(size_t bytes) {       // frees what it held; GH_E_NOMEM / GH_E_HIP with the message in g_err
+        reset();
+        HIPCHK(hipMalloc(&p_, bytes));
+        return GH_OK;
+    }
+    void* get() const { return p_; }
+    template <class T> T* as() const { return static_cast<T*>(p_); }
+    void* release() { void* p = p_; p_ = nullptr; return p; }
+    void reset() { dev_free(p_); }
+private:
+    void* p_ = nullptr;
+};
+
+// ---- curves: the facts every unit needs about a curve id
+inline int curve_deg(gh_curve_t c) { return c == GH_MNT4753_G2 ? 2 : (c == GH_MNT6753_G2 ? 3 : 1); }   // extension degree of the base field
+template <class C> struct CurveId;
+template <> struct CurveId<gh::Mnt4G1> { static constexpr gh_curve_t id = GH_MNT4753_G1; };
+template <> struct CurveId<gh::Mnt4G2> { static constexpr gh_curve_t id = GH_MNT4753_G2; };
+template <> struct CurveId<gh::Mnt6G1> { static constexpr gh_curve_t id = GH_MNT6753_G1; };
+template <> struct CurveId<gh::Mnt6G2> { static constexpr gh_curve_t id = GH_MNT6753_G2; };
+inline int unknown_curve() { g_err = "unknown curve id"; return GH_E_BAD_ARG; }
+// fn<C>(args) for the curve policy C of a curve id: the two G1 curves (Schnorr, EC-VRF: the caller has checked is_g1), or all four
+#define GH_G1_DISPATCH(curve, fn, ...) ((curve) == GH_MNT6753_G1 ? fn<gh::Mnt6G1>(__VA_ARGS__) : fn<gh::Mnt4G1>(__VA_ARGS__))
+#define GH_CURVE_DISPATCH(curve, fn, ...)                          \
+    ((curve) == GH_MNT4753_G1   ? fn<gh::Mnt4G1>(__VA_ARGS__)       \
+     : (curve) == GH_MNT4753_G2 ? fn<gh::Mnt4G2>(__VA_ARGS__)       \
+     : (curve) == GH_MNT6753_G1 ? fn<gh::Mnt6G1>(__VA_ARGS__)       \
+     : (curve) == GH_MNT6753_G2 ? fn<gh::Mnt6G2>(__VA_ARGS__)       \
+                                : gh_rt::unknown_curve())
+
 // ---- per-curve entry points (msm_<curve>.hip)
+// A resident key.  The destructor is the one place that knows which device arrays a key owns: `delete h` frees them all.
 struct BasesBase {
     gh_curve_t curve;
     size_t n = 0;
@@ -140,8 +193,22 @@ struct BasesBase {
     uint8_t aff_asm_off = 0;    // G2: an MSM over this key overflowed the exception list of the assembly rounds (a key with many equal
                                 // bases, e.g. a proving key's b_g2_query under an assignment with equal values: every pair of such bases
                                 // in a bucket is a doubling) -- later MSMs go straight to the C++ round kernel, which doubles inline
-    uint32_t magic = 0x6768424au;
+    static constexpr uint32_t MAGIC = 0x6768424au;
+    uint32_t magic = MAGIC;
+    BasesBase() = default;
+    BasesBase(const BasesBase&) = delete;
+    BasesBase& operator=(const BasesBase&) = delete;
+    ~BasesBase() {
+        dev_free(d_points); dev_free(d_inf); dev_free(d_table);
+        dev_free(d_dup_starts); dev_free(d_dup_members); dev_free(d_dup_chunks);
+        magic = 0;
+    }
 };
+// the checked cast of a handle of the C ABI: null for a null pointer or for memory that is not a live key
+inline BasesBase* bases_of(gh_bases_t handle) {
+    BasesBase* h = reinterpret_cast<BasesBase*>(handle);
+    return h && h->magic == BasesBase::MAGIC ? h : nullptr;
+}
 struct MsmOps {
     int (*upload)(const uint64_t* bases, const uint8_t* infinity, size_t n, int canonical, BasesBase** out);
     int (*run)(BasesBase* h, const void* d_scalars, size_t n_scalars, uint64_t* out_xyz);
@@ -160,6 +227,7 @@ const MsmOps* msm_ops_mnt4753_g1();
 const MsmOps* msm_ops_mnt4753_g2();
 const MsmOps* msm_ops_mnt6753_g1();
 const MsmOps* msm_ops_mnt6753_g2();
+const MsmOps* ops_of(gh_curve_t curve);            // null, with "unknown curve id" in g_err, for anything else
 
 // ---- transforms (ntt.hip)
 int fft_run(gh_field_t field, void* d_data, uint32_t log_n, uint32_t flags);
@@ -174,7 +242,7 @@ int lagrange_coefficients(gh_field_t field, uint32_t log_n, const uint64_t* tau1
 struct FixedTable;                                 // fixed_base.hip: a window table of one base
 int fixed_table_create(gh_curve_t curve, const uint64_t* g_xyz, size_t scalar_size, int window, FixedTable** out);
 int fixed_table_sums(const FixedTable* t, const void* d_scalars, size_t n, void* d_out_proj);   // on g.stream, internal Proj<C>
-void fixed_table_destroy(FixedTable* t);
+void fixed_table_destroy(FixedTable* t);          // null is fine
 int poseidon_field(const gh_poseidon* h, gh_field_t* out);                              // GH_E_BAD_HANDLE if h is none
 int poseidon_hash_dev_locked(gh_poseidon* h, const void* d_in, size_t n, size_t len, void* d_out);   // on g.stream, no sync
 void poseidon_trim_slab();                         // the release of a large slab every Poseidon entry point does on return

@@ -280,7 +280,6 @@ template <class C> struct Scheme;
 template <> struct Scheme<Mnt6G1> { typedef P6 PF; typedef P4 PS; static constexpr gh_field_t field = GH_MNT4753_FR; };
 template <> struct Scheme<Mnt4G1> { typedef P4 PF; typedef P6 PS; static constexpr gh_field_t field = GH_MNT6753_FR; };
 inline bool is_g1(gh_curve_t c) { return c == GH_MNT6753_G1 || c == GH_MNT4753_G1; }
-#define GH_G1_DISPATCH(curve, fn, ...) ((curve) == GH_MNT6753_G1 ? fn<Mnt6G1>(__VA_ARGS__) : fn<Mnt4G1>(__VA_ARGS__))
 template <class C> bool data_below(const uint64_t* x, size_t count) { return all_below<typename Scheme<C>::PF>(x, count); }
 template <class C> bool scalar_below(const uint64_t* x, size_t count) { return all_below<typename Scheme<C>::PS>(x, count); }
 
