@@ -32,11 +32,11 @@
 // row-major -- they are random rows -- and are fetched with 16-byte loads.
 #pragma once
 #include "ec29.h"
+#include "msm_plan.h"      // AFF_MAX_ROUNDS
 
 namespace gh {
 
 constexpr uint32_t AFF_MARK = 0xFFFFFFFFu;   // x.l[0] of the infinity marker
-constexpr int AFF_MAX_ROUNDS = 26;
 
 #ifndef GH_LD_ST_FP
 #define GH_LD_ST_FP

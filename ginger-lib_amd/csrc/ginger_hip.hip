@@ -195,26 +195,6 @@ int device_scan(const uint32_t* in, uint32_t* out, size_t n, const char* tmpname
     return GH_OK;
 }
 
-// Window size.  Measured on MI355X (profiles/r01_window_sweep.txt): besides the usual trade of
-// accumulate work (n * ceil(754/c) additions) against bucket-reduction work (2^(c-1) buckets per
-// window), what matters is how full the TOP window is -- c = 13 (58 * 13 = 754), 18 (42 * 18 = 756),
-// 19 and 21 leave no sparsely populated top window whose few buckets become over-long.
-int auto_window(size_t n, int deg) {
-    if (g.window_override > 0) return g.window_override;
-    int lg = 0;
-    while (((size_t)1 << (lg + 1)) <= n) lg++;
-    if (deg > 1) {   // G2: the host fold and the reduction weigh more per window -> fewer, larger windows
-        int c = lg - 4;
-        return c < 4 ? 4 : (c > 20 ? 20 : c);
-    }
-    if (lg >= 23) return 19;
-    if (lg >= 21) return 18;
-    if (lg >= 19) return 16;
-    if (lg >= 15) return 13;
-    int c = lg - 3;
-    return c < 4 ? 4 : c;
-}
-
 const MsmOps* ops_of(gh_curve_t curve) {
     switch (curve) {
         case GH_MNT4753_G1: return msm_ops_mnt4753_g1();

@@ -26,17 +26,16 @@
 //                            lane, then tree / suffix scan / tree across the 64 lanes through LDS:
 //                            the wavefront-wide bucket reduction); two launches.
 //   6. window fold           ~750 dependent doublings: latency-bound, done on the host
-//                            (msm_impl.h fold_windows) with the reduction's powers of two merged in.
+//                            (msm_fold.h fold_windows) with the reduction's powers of two merged in.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ec29.h"
 #include "aff_kernels.h"
+#include "msm_plan.h"
 
 namespace gh {
 
-constexpr int MSM_REDUCE_L = 16;         // buckets folded serially per lane in reduce level 1
-constexpr int MSM_MAX_HEAVY_THRESHOLD = 1024;  // upper bound of the run-time heavy threshold
-constexpr int MSM_SIZE_BINS = MSM_MAX_HEAVY_THRESHOLD + 2;
+// MSM_REDUCE_L, MSM_MAX_HEAVY_THRESHOLD, MSM_SIZE_BINS, MSM_PART_MAX_BINS, MSM_DUP_CHUNK: msm_plan.h (shared with the host's plans)
 
 // ---------------------------------------------------------------- generic point load / store
 template <class C> __device__ __forceinline__ Aff<C> ld_aff(const Aff<C>* p) {
@@ -262,7 +261,7 @@ static __device__ __forceinline__ uint32_t wave_agg_inc(uint32_t* base, uint32_t
 // shift tables, section 0 below: window w then reads its bases from table row w).  That merged set uses slot_shift 1:
 // slot = |d| - 1, exactly 2^(c-1) slots -- a power of two, so the bucket reduction's segments tile it without a
 // remainder (one straggling wave program on an already occupied SIMD doubled the whole launch); the weight of a slot
-// is then slot + 1 and the fold adds the plain sum of all buckets once (msm_impl.h fold_merged).
+// is then slot + 1 and the fold adds the plain sum of all buckets once (msm_fold.h fold_merged).
 //
 // (a) sign folding: s > r/2 is replaced by r - s with the base negated (s P = (r - s)(-P)), so the
 //     magnitude is below 2^752 and bit 752 never needs a window.
@@ -274,7 +273,7 @@ static __device__ __forceinline__ uint32_t wave_agg_inc(uint32_t* base, uint32_t
 //     entries.  Instead (top_unsigned) window W-2, the top real one, is taken UNSIGNED:
 //     v <= 0.885 * 2^c + 1 is filed under slot v of window W-2 if v <= 2^(c-1), else under slot
 //     v - 2^(c-1) of window W-1, which thereby is "region b" of window W-2 (same window weight,
-//     slot offset 2^(c-1): the host adds 2^(c-1) * sum(region b), msm_impl.h fold_windows).
+//     slot offset 2^(c-1): the host adds 2^(c-1) * sum(region b), msm_fold.h fold_windows).
 struct MsmModulus { uint32_t w[24]; };
 
 // ---- equal bases.  A proving key holds the SAME point for every variable with the same polynomial (the `Benchmark` circuit's
@@ -283,7 +282,7 @@ struct MsmModulus { uint32_t w[24]; };
 // (nothing in the reference does this; VariableBaseMSM::multi_scalar_mul's result is the same group element).  Without it every
 // pair of equal bases that meet in a bucket is a doubling / a cancellation (swp.rs:492) -- millions per MSM on such a key.
 // msm_base_hash_kernel: 128 bits over the abscissa's limbs per base (0, 0 for infinity); the host groups equal hashes
-// (msm_impl.h dedup_bases); msm_dup_verify_kernel compares every member with its group's first base limb for limb (a hash
+// (msm_key.h dedup_bases); msm_dup_verify_kernel compares every member with its group's first base limb for limb (a hash
 // collision drops out of the group) and records the sign; msm_merge_scalars_kernel does the sums at MSM time.
 template <class C>
 static __global__ void __launch_bounds__(256)
@@ -347,7 +346,6 @@ static __device__ __forceinline__ void scalar_add_mod(uint32_t* a, const uint32_
 // into chunks of at most MSM_DUP_CHUNK members (chunks[3 k] = first member, [3 k + 1] = end, [3 k + 2] = group); step 1 sums a
 // chunk's scalars into partial[k] and zeroes its non-canonical members in `out`, step 2 adds a group's partial sums into its
 // canonical base's scalar.
-constexpr uint32_t MSM_DUP_CHUNK = 4096;
 static __global__ void __launch_bounds__(256)
 msm_merge_scalars_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n, const uint32_t* __restrict__ starts,
                          const uint32_t* __restrict__ members, const uint32_t* __restrict__ chunks, uint32_t n_chunks,
@@ -489,7 +487,6 @@ msm_digits_kernel(const uint32_t* __restrict__ scalars, const uint8_t* __restric
 //   B  one block per bin: per-bucket counts in LDS, block scan -> counts[] / starts[], second sweep -> sorted[].
 // Result: the same counts / starts / sorted arrays as the atomic path (order inside a bucket is arbitrary in both).
 constexpr int MSM_PART_THREADS = 256;
-constexpr int MSM_PART_MAX_BINS = 2048;   // (1024 unless the buckets need more: msm_impl.h, launch_sort)
 struct MsmPartArgs {
     const int32_t* digits;
     size_t entries;        // W * n
@@ -1174,7 +1171,7 @@ msm_heavy_combine_kernel(const Proj<C>* __restrict__ partials, const uint32_t* _
 // addition; the whole wave then spends three extra steps on a detour through a salt point
 // (p + S) + q - S for the affected lanes.  Powers of two (64, 64 L) that weight the outputs are
 // NOT applied here: they are folded into the host's Horner loop over the windows, where the
-// doublings are needed anyway (msm_impl.h: fold_windows).
+// doublings are needed anyway (msm_fold.h: fold_windows).
 template <class C> struct WaveReduceIn {
     const Proj<C>* base;   // item (w, k) = base[(w * count + k) * stride + offset]
     uint32_t stride, offset, count, mode;

@@ -12,6 +12,7 @@
 #include <vector>
 #include "../../include/ginger_hip.h"
 #include "fp29.h"
+#include "msm_plan.h"
 
 struct gh_poseidon;
 namespace gh { struct Mnt4G1; struct Mnt4G2; struct Mnt6G1; struct Mnt6G2; }   // the curve policies (ec29.h)
@@ -51,7 +52,7 @@ struct Ctx {
     hipStream_t stream = nullptr;       // transforms, bucket sort
     hipStream_t stream_acc = nullptr;   // MSM accumulation (lowest priority: the filler of the pipeline)
     hipStream_t stream_red = nullptr;   // MSM bucket reduction (highest priority: short latency chains)
-    hipStream_t stream_acc2 = nullptr;  // second half of a split affine round (msm_impl.h launch_tree): same priority as stream_acc
+    hipStream_t stream_acc2 = nullptr;  // second half of a split affine round (msm_impl.h issue_round): same priority as stream_acc
     hipEvent_t tev[2] = {nullptr, nullptr};   // fork / join of a split round
     hipEvent_t ev[8];
     hipEvent_t pev[4][8];               // MSM stage events, one set per job in flight (job k of a batch uses set k & 3)
@@ -84,9 +85,7 @@ inline std::string slot_name(const char* name, int slot) { return std::string(na
 template <class T> int slot_buf(const char* name, int slot, size_t bytes, T** out) {
     return pool_get(slot_name(name, slot).c_str(), bytes, (void**)out);
 }
-// an integer / real knob from the environment: dflt when unset, atoi / atof of the value otherwise
-inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-inline double env_double(const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; }
+// (env_int / env_double, the readers of an environment knob: msm_plan.h)
 // Waits for every stream an MSM runs on, the second stream of a split affine round included: nothing may still read or write a
 // pooled buffer or a cached key when it is released.  Waits on all four even after an error; returns the first error.
 inline hipError_t sync_msm_streams() {
@@ -98,7 +97,7 @@ inline hipError_t sync_msm_streams() {
     return e;
 }
 int device_scan(const uint32_t* in, uint32_t* out, size_t n, const char* tmpname, hipStream_t stream = nullptr);   // nullptr: g.stream
-int auto_window(size_t n, int deg);
+inline int auto_window(size_t n, int deg) { return auto_window(n, deg, g.window_override); }   // msm_plan.h, under gh_msm_set_window
 void dist_teardown_locked();                      // dist.hip: gh_shutdown (API lock held) destroys the communicator with the context
 
 // No C++ exception leaves the library (include/ginger_hip.h: "nothing is thrown"; the reference's multi_scalar_mul is

@@ -630,7 +630,7 @@ def test_msm_affine_degenerate_inputs(gpu, no_dedup, curve):
 
 @pytest.mark.parametrize("curve", ["mnt4753_g1", "mnt4753_g2", "mnt6753_g2"])
 def test_msm_adds_up_the_scalars_of_equal_bases(gpu, curve):
-    """A key with a shift table knows its equal bases (msm_impl.h dedup_bases: hashed on the device, grouped on the host,
+    """A key with a shift table knows its equal bases (msm_key.h dedup_bases: hashed on the device, grouped on the host,
     verified limb for limb) and adds their scalars up before the MSM: sum s_i P = (sum s_i) P, opposite bases with the
     opposite sign.  One large group (every third base the same point, as a proving key's b_query has for the variables of a
     closing constraint), pairs of equal and of opposite bases, an infinity base, scalars 0 / 1 / r - 1 inside groups, fewer
@@ -839,7 +839,7 @@ def test_msm_cached_survives_forced_hash_collisions_and_a_failed_table_build(gpu
     """Two round-3 defects of gh_msm_cached, exercised by fault injection on every GPU run instead of by filling the card
     (the test that did that aborted the suite once and was deleted):
     (a) a shift-table build that runs out of memory drops every pooled scratch buffer -- GH_TEST_TABLE_NOMEM=1 makes every
-        build take exactly that path (msm_impl.h precompute_bases).  The scalars' PCIe copy is in flight at that moment; round 3
+        build take exactly that path (msm_key.h precompute_bases).  The scalars' PCIe copy is in flight at that moment; round 3
         copied into a pooled buffer that the builder freed under the copy (GPU fault at 2^22 MNT6 G2 pairs).  The call must
         succeed on the per-window path with the oracle's sum, `tables_built` unchanged;
     (b) a hit used to be decided by 128 hash bits alone.  gh_test_hooks(1) forces the selection lanes of every key to one
@@ -922,7 +922,7 @@ def test_msm_parity_again_with_the_lean_reduction_forced(gpu):
 
 
 def test_affine_rounds_parity_again_with_every_round_split(gpu):
-    """Large affine rounds go out as two halves on two streams (msm_impl.h launch_tree); sizes the oracle can referee stay below the
+    """Large affine rounds go out as two halves on two streams (msm_impl.h issue_round); sizes the oracle can referee stay below the
     threshold, so the affine-round parity tests of this file run once more in a child process with GH_AFF_SPLIT_B=1 (every round with
     more than one tile of outputs is split: ragged second halves, exception lists in both control blocks, duplicate bases that overflow
     them) -- against the oracle as before."""
