@@ -16,7 +16,7 @@ import struct
 import numpy as np
 
 # base-field bytes of one coordinate coefficient / degree of the G2 coordinate field / bytes of the target-field element
-# vk.alpha_g1_beta_g2 (Fq4 resp. Fq6: carried as opaque bytes -- pairings are out of scope, the prover never reads it)
+# vk.alpha_g1_beta_g2 (Fq4 resp. Fq6: carried as opaque bytes -- the prover never reads it; pairing.py computes it for MNT4-753)
 _FQ_BYTES = 96
 _G2_DEG = {"mnt4753": 2, "mnt6753": 3}
 _FQK_BYTES = {"mnt4753": 4 * 96, "mnt6753": 6 * 96}
@@ -133,8 +133,8 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, 
       * instance_map_with_evaluation (r1cs_to_qap.rs:14-69): host integers, as in the reference;
       * the five queries and gamma_abc_g1: FixedBaseMSM on the device with the reference's window rule (:233-311), followed
         by batch_normalization + into_affine (:318-335) -- gh_fixed_base_msm_affine, straight into the serialised form;
-      * vk.alpha_g1_beta_g2 is a pairing value (:313): pairings are out of scope, the prover never reads it -- filler bytes
-        unless the caller supplies them."""
+      * vk.alpha_g1_beta_g2 is a pairing value (:313) that the prover never reads -- filler bytes unless the caller supplies
+        them; pairing.parameters_with_pairing puts the real value into an MNT4-753 stream."""
     r = _MODULUS[pairing]
     field = "mnt4753_fr" if pairing == "mnt4753" else "mnt6753_fr"
     g1c, g2c = pairing + "_g1", pairing + "_g2"

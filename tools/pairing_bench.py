@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""MNT4-753 pairings and Groth16 verification on the device: pairings/s (gh_pairing_product, k = 1) and verifications/s
+(gh_groth16_verify, two public inputs) at 2^16 and 2^20 rows, warmed, best of 3, timed around the call (which synchronises
+the device before it returns), the phase split of every call, and the Miller and final-exponentiation kernels' products per
+row (counted from the formulas as written in csrc/pairing29.h, squarings as products) over their kernel time as a fraction of
+the product peak gh_measure_fpmul_peak measures in the same run.
+
+The rows are valid proofs of a key made from random scalars, so that (A, B, C) is known in the exponent:
+    a b = alpha beta + (k_0 + sum_j x_j k_j) gamma + c delta;
+4096 distinct rows are tiled to the batch size (no kernel looks at another row).  Every status must be 1.
+Prints one JSON document.  Usage: timeout -k 10 900 python tools/pairing_bench.py [--log2n 16 20] [--reps 3] > out.json"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from schnorr_bench import INV, MADD, ADD   # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+DISTINCT = 4096
+N_INPUTS = 2
+# products of the steps of csrc/pairing29.h (its header counts them)
+FQ4_MUL, FQ4_SQR, MUL_023, CYC_SQR = 9, 6, 8, 4
+DBL_STEP, ADD_STEP, PREPARED_LINE = 25 + 4, 28 + 8, 2
+
+
+def products(consts):
+    naf, w0 = consts["ate_naf"], consts["w0_naf"]
+    dig, nz = len(naf), sum(1 for d in naf if d)
+    variable = dig * (DBL_STEP + FQ4_MUL) + nz * (ADD_STEP + FQ4_MUL)
+    prepared = (dig + nz) * (PREPARED_LINE + MUL_023)
+    squarings = dig * FQ4_SQR
+    fq4_inv = 4 + (2 + INV + 2 + 2) + 6
+    final_exp = fq4_inv + 2 * FQ4_MUL + 3 * 2 + (len(w0) - 1) * CYC_SQR + (sum(1 for d in w0 if d) - 1) * FQ4_MUL + FQ4_MUL + 4
+    g_ic = N_INPUTS * (2 + -(-753 // 8) * MADD + ADD) + (1 + 3 + INV / 16 + 2)
+    return {"variable_pair": variable, "prepared_pair": prepared, "shared_squarings": squarings, "final_exponentiation": final_exp,
+            "pairing_miller": variable + squarings + 6, "groth16_miller": variable + 2 * prepared + squarings + 10,
+            "groth16_g_ic_and_checks": g_ic + 21,
+            "pairing_total": variable + squarings + 6 + final_exp,
+            "groth16_total": variable + 2 * prepared + squarings + 10 + final_exp + g_ic + 21}
+
+
+def _rows(vals):
+    return np.frombuffer(b"".join(int(v).to_bytes(96, "little") for v in vals), dtype=np.uint64).reshape(-1, 12)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log2n", type=int, nargs="*", default=[16, 20])
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    from __graft_entry__ import _load_pkg
+    gl = _load_pkg()
+    gl.init()
+    from ginger_lib_amd import groth16, pairing
+    peak = gl.measure_fpmul_peak()
+    C = json.load(open(os.path.join(GOLDEN, "constants.json")))
+    consts = json.load(open(os.path.join(GOLDEN, "pairing_constants.json")))
+    prod = products(consts)
+    p, r = int(C["fields"]["p4"]["p"], 16), int(C["fields"]["p6"]["p"], 16)
+    mont = lambda vals: groth16._mont_rows(vals, p).reshape(-1)
+    c1, c2 = C["curves"]["mnt4753_g1"], C["curves"]["mnt4753_g2"]
+    g1_xyz = mont([int(c1["gx"][0], 16), int(c1["gy"][0], 16), 1])
+    g2_xyz = mont([int(v, 16) for v in c2["gx"] + c2["gy"]] + [1, 0])
+    t1, t2 = gl.FixedBaseMSM("mnt4753_g1", g1_xyz, 753, 10), gl.FixedBaseMSM("mnt4753_g2", g2_xyz, 753, 8)
+    g1 = lambda ks: t1.multi_scalar_mul_affine(_rows(ks))
+    g2 = lambda ks: t2.multi_scalar_mul_affine(_rows(ks))
+    rng = random.Random(14)
+    alpha, beta, gamma, delta = (rng.randrange(1, r) for _ in range(4))
+    ks = [rng.randrange(1, r) for _ in range(N_INPUTS + 1)]
+    av = [rng.randrange(1, r) for _ in range(DISTINCT)]
+    bv = [rng.randrange(1, r) for _ in range(DISTINCT)]
+    xv = [[rng.randrange(r) for _ in range(N_INPUTS)] for _ in range(DISTINCT)]
+    di = pow(delta, -1, r)
+    cv = [(x * y - alpha * beta - (ks[0] + sum(u * k for u, k in zip(xs, ks[1:]))) * gamma) * di % r for x, y, xs in zip(av, bv, xv)]
+    A, B, Cc = g1(av), g2(bv), g1(cv)
+    vk2 = g2([gamma, delta, beta])
+    abc = g1(ks + [alpha])
+    gt = pairing.pairing_product((abc[0][-1:], abc[1][-1:]), (vk2[0][2:], vk2[1][2:]))
+    pvk = pairing.PreparedVerifyingKey(gt, vk2[0][0], vk2[0][1], abc[0][:-1])
+    X = groth16._mont_rows([u for xs in xv for u in xs], r).reshape(DISTINCT, N_INPUTS * 12)
+    t1.free()
+    t2.free()
+    doc = {"device": gl.device_name(), "fpmul_peak_per_s": peak, "public_inputs": N_INPUTS, "products_per_row": prod, "rows": {}}
+    for lg in a.log2n:
+        n = 1 << lg
+        tile = lambda arr: np.ascontiguousarray(np.tile(arr, (-(-n // DISTINCT),) + (1,) * (arr.ndim - 1))[:n])
+        pa, pb, pc, px = [(tile(q[0]), tile(q[1])) for q in (A, B, Cc)] + [tile(X)]
+        res = {"rows": n}
+        for name, call, ok, miller in (("pairing", lambda: pairing.pairing_product(pa, pb), None, prod["pairing_miller"]),
+                                       ("groth16_verify", lambda: pvk.verify(pa, pb, pc, px), 1, prod["groth16_miller"])):
+            out = call()                                        # warm: tables, pooled buffers
+            if ok is not None:
+                assert (out == ok).all(), "a valid proof did not verify"
+            best, phases = None, None
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                call()
+                dt = time.perf_counter() - t0
+                if best is None or dt < best:
+                    best, phases = dt, pairing.last_timing()
+            ms = phases[0]
+            res[name] = {"s": best, "per_s": n / best, "phases_ms": ms, "total_ms": phases[1],
+                         "miller_fraction_of_peak": miller * n / (ms["miller"] / 1e3) / peak,
+                         "final_exp_fraction_of_peak": prod["final_exponentiation"] * n / (ms["final_exp"] / 1e3) / peak}
+            print("%s 2^%d: %.0f /s, Miller %.1f ms (%.3f of peak), final exponentiation %.1f ms (%.3f of peak)" % (
+                name, lg, n / best, ms["miller"], res[name]["miller_fraction_of_peak"], ms["final_exp"],
+                res[name]["final_exp_fraction_of_peak"]), file=sys.stderr, flush=True)
+        doc["rows"][str(lg)] = res
+    pvk.close()
+    print(json.dumps(doc, indent=1))
+
+
+if __name__ == "__main__":
+    main()
