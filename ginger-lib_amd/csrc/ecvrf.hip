@@ -222,7 +222,7 @@ template <class C> int bh_launch(gh_bh* b, const uint8_t* d_in, size_t stride, s
 // out[i] = k1_i (+-) P1_i + k2_i (+-) P2_i, on g.stream
 template <class C> int vb_joint(const void* d_xy1, const uint8_t* d_inf1, int neg1, const uint32_t* d_k1, const void* d_xy2,
                                 const uint8_t* d_inf2, int neg2, const uint32_t* d_k2, size_t n, Proj<C>* d_out) {
-    const size_t chunk = vb_chunk<VB_W>(n, 2);
+    const size_t chunk = vb_chunk<VB_W>("vb_joint", n, 2);
     uint32_t *slab1 = nullptr, *slab2 = nullptr;
     if (int rc = gh_rt::pool_get("vb_slab", chunk * vb_row_bytes<VB_W>(), (void**)&slab1)) return rc;
     if (int rc = gh_rt::pool_get("vb_slab2", chunk * vb_row_bytes<VB_W>(), (void**)&slab2)) return rc;

@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(256) bcast_xy_kernel(const uint32_t* __restric
 template <class E, int KV, int KP>
 int launch_pairs(const PairIn& in, const uint8_t* d_status, const typename E::Coeff* tab, size_t n, uint64_t* d_val, Phases* ph) {
     constexpr size_t row_bytes = (size_t)(VAR_SLOTS * KV + PRE_SLOTS * KP) * NL * 4;
-    const size_t chunk = std::min(n, std::max<size_t>(BLOCK, (PAIR_SLAB_BYTES / row_bytes) / BLOCK * BLOCK));
+    const size_t chunk = slab_chunk_rows("launch_pairs", PAIR_SLAB_BYTES, row_bytes, n);
     uint32_t* slab;
     uint8_t* d_skip;
     typename E::GT* d_f;

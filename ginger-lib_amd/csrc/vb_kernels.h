@@ -383,15 +383,27 @@ struct Trim {
 // ---- the variable-base launches; large batches are cut into chunks whose slabs stay below VB_SLAB_BYTES together
 constexpr size_t VB_SLAB_BYTES = (size_t)1 << 30;
 template <int W> constexpr size_t vb_row_bytes() { return (size_t)VbWindow<W>::E * SLOTS_PER_ENTRY * NL * 4; }   // one row of one slab
-template <int W> size_t vb_chunk(size_t n, int slabs) {
-    return std::min(n, std::max<size_t>(BLOCK, (VB_SLAB_BYTES / (vb_row_bytes<W>() * slabs)) / BLOCK * BLOCK));
+// rows per chunk of a launch of n rows whose slabs take row_bytes per row and stay below `budget` together: a multiple of BLOCK,
+// at most n.  GH_TEST_SLAB_ROWS=R (test support, read on every call; R <= 0 or unset: nothing changes) caps a chunk at R rows
+// rounded up to a multiple of BLOCK, so that a test reaches the chunks after the first at a few hundred rows; while it is set,
+// every launch says on stderr how it was cut (`loop` names the caller).
+inline size_t slab_chunk_rows(const char* loop, size_t budget, size_t row_bytes, size_t n) {
+    size_t rows = std::max<size_t>(BLOCK, (budget / row_bytes) / BLOCK * BLOCK);
+    const int knob = gh_rt::env_int("GH_TEST_SLAB_ROWS", 0);
+    if (knob > 0) rows = std::min(rows, ((size_t)knob + BLOCK - 1) / BLOCK * BLOCK);
+    const size_t chunk = std::min(n, rows);
+    if (knob > 0) fprintf(stderr, "[gh] slab chunks: %s n=%zu rows=%zu chunks=%zu\n", loop, n, chunk, chunk ? (n + chunk - 1) / chunk : (size_t)0);
+    return chunk;
+}
+template <int W> size_t vb_chunk(const char* loop, size_t n, int slabs) {
+    return slab_chunk_rows(loop, VB_SLAB_BYTES, vb_row_bytes<W>() * slabs, n);
 }
 
 // one table of (+-) P per row, then d_out[j][i] = d_k[j]_i (+-) P_i for each of the `count` scalar vectors (n x 24 words,
 // canonical) as internal Proj<C>, on g.stream
 template <class C, int W>
 int vb_single(const void* d_xy, const uint8_t* d_inf, int negate, const uint32_t* const* d_k, Proj<C>* const* d_out, int count, size_t n) {
-    const size_t chunk = vb_chunk<W>(n, 1);
+    const size_t chunk = vb_chunk<W>("vb_single", n, 1);
     uint32_t* slab = nullptr;
     if (int rc = gh_rt::pool_get("vb_slab", chunk * vb_row_bytes<W>(), (void**)&slab)) return rc;
     for (size_t r0 = 0; r0 < n; r0 += chunk) {

@@ -368,3 +368,124 @@ def test_device_round_trip_2p18(setups, scheme):
         assert int(st2[i]) == code, i
         if code == ecvrf_ref.OK:
             assert V.from_fe(out2[i]) == o, i
+
+
+# ---------------------------------------------------------------- 7. the chunks after the first (tests/slab_chunks.py)
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_batch_double_mul_in_three_slab_chunks(gpu, scheme, monkeypatch, capfd):
+    """gh_batch_double_mul of 261 rows in chunks of 128, 128 and 5 rows: the chunk line of the joint launch, the same bits as
+    in one chunk, and the restatement's points at both sides of every chunk edge and in the special rows (later chunks only)"""
+    from ginger_lib_amd import ecvrf
+    import slab_chunks as K
+    curve = ecvrf_ref.SCHEMES[scheme][1]
+    V = ecvrf_ref.EcVrf(scheme, None)
+    C = V.C
+    rng = random.Random(261 + len(scheme))
+    P1, P2, H = ecvrf_ref.random_point(C, rng), ecvrf_ref.random_point(C, rng), mul(C, 3, V.G)
+    p1, p2 = [], []
+    for _ in range(K.N):                                        # P1 + i G and P2 + 3 i G: bases of its own in every row
+        p1.append(P1)
+        p2.append(P2)
+        P1, P2 = C.add(P1, V.G), C.add(P2, H)
+    k1 = [rng.getrandbits(753) for _ in range(K.N)]
+    k2 = [rng.getrandbits(753) for _ in range(K.N)]
+    K.assert_rows_differ(p1, p2, k1, k2)
+    top = (1 << 753) - 1
+    p1[131], p2[257] = None, None                               # rows 3 and 259 (1 and 129) are ordinary rows
+    k1[140], k2[150], k1[160], k2[258] = 0, 0, top, top
+    p2[170], k2[170] = C.neg(p1[170]), k1[170]                  # the two halves cancel
+    xy1, inf1 = pts_abi(V, p1)
+    xy2, inf2 = pts_abi(V, p2)
+    a1, a2 = limbs(k1), limbs(k2)
+    plain, cut, err = K.plain_and_cut(monkeypatch, capfd, lambda: ecvrf.batch_double_mul(curve, xy1, a1, xy2, a2, inf1, inf2))
+    assert K.chunk_lines(err, "vb_joint") == K.THREE, err
+    assert K.identical(plain, cut)
+    for i in K.SAMPLE + (131, 140, 150, 160, 170, 257, 258):
+        assert proj_to_aff(V, cut[i]) == C.add(mul(C, k1[i], p1[i]), mul(C, k2[i], p2[i])), i
+    assert proj_to_aff(V, cut[170]) is None
+
+
+_CHUNK_ROWS = {}
+
+
+def _chunk_rows(V, D, scheme):
+    """261 rows of (sk, pk, one message element), shared by the two tests below; sk = 0 (pk, gamma at infinity) in row 131"""
+    import slab_chunks as K
+    if scheme not in _CHUNK_ROWS:
+        rng = random.Random(522 + len(scheme))
+        sks = [rng.randrange(1, V.r) for _ in range(K.N)]
+        sks[131] = 0
+        msgs = [[rng.randrange(V.p)] for _ in range(K.N)]
+        K.assert_rows_differ(sks, [m[0] for m in msgs])
+        sk = limbs([V.R.to_mont(x) for x in sks])
+        pk = D.get_public_key(sk)
+        for i in (0, 131, 260):
+            assert V.pt_from_abi(pk[0][i], pk[1][i]) == V.pk(sks[i]), i
+        _CHUNK_ROWS[scheme] = (sks, sk, pk, msgs, msg_arr(V, msgs, 1))
+    return _CHUNK_ROWS[scheme]
+
+
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_prove_in_three_slab_chunks(setups, scheme, monkeypatch, capfd):
+    """EC-VRF prove of 261 rows at L = 1: its one table per row serves two scalar vectors (gamma = sk mh, b = k mh) in every chunk"""
+    import slab_chunks as K
+    V, D, _ = setups[scheme]
+    sks, sk, pk, msgs, ma = _chunk_rows(V, D, scheme)
+    rng = random.Random(7 + len(scheme))
+    nonces = [rng.randrange(1, V.r) for _ in range(K.N)]
+    K.assert_rows_differ(nonces)
+    nonces[140] = 0                                             # rejected, in the second chunk only
+    ka = limbs([V.R.to_mont(k) for k in nonces])
+    plain, cut, err = K.plain_and_cut(monkeypatch, capfd, lambda: D.prove(sk, pk, ma, ka))
+    assert K.chunk_lines(err, "vb_single") == K.THREE, err
+    assert K.identical(plain, cut)
+    (gxy, ginf), cs, st = cut
+    assert 0 < int(st.sum()) < K.N and st[140] == 0             # both verdicts occur
+    for i in K.SAMPLE + (131, 140):
+        want = V.prove_with(sks[i], V.pt_from_abi(pk[0][i], pk[1][i]), msgs[i], nonces[i])
+        assert V.pt_from_abi(gxy[i], ginf[i]) == (want[0] if want else V.gamma_of(sks[i], msgs[i])), i
+        assert int(st[i]) == (want is not None), i
+        if want is None:
+            assert not cs[i].any(), i
+        else:
+            assert (V.from_fe(cs[i][:12]), V.from_fe(cs[i][12:])) == want[1:], i
+    assert ginf[131] == 1
+
+
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_proof_to_hash_in_three_slab_chunks(setups, scheme, monkeypatch, capfd):
+    """EC-VRF proof_to_hash of 261 proofs of the device's prove, one spoilt row in each chunk: c (-pk) by the single launch
+    and s mh + c (-gamma) by the joint launch, both in three chunks"""
+    import slab_chunks as K
+    V, D, _ = setups[scheme]
+    sks, sk, pk, msgs, ma = _chunk_rows(V, D, scheme)
+    rs = np.random.default_rng(261 + len(scheme))
+    gxy, ginf, cs = np.zeros((K.N, 24), dtype=np.uint64), np.zeros(K.N, dtype=np.uint8), np.zeros((K.N, 24), dtype=np.uint64)
+    todo = np.arange(K.N)
+    for _ in range(64):                                         # about 32 % of the nonces pass both range checks
+        (g_, gi_), c_, st = D.prove(sk[todo], (pk[0][todo], pk[1][todo]), ma[todo], _random_elems(rs, len(todo), V.r))
+        ok = todo[st == 1]
+        gxy[ok], ginf[ok], cs[ok] = g_[st == 1], gi_[st == 1], c_[st == 1]
+        todo = todo[st != 1]
+        if not len(todo):
+            break
+    assert not len(todo)
+    K.assert_rows_differ([r.tobytes() for r in cs[:, :12]], [r.tobytes() for r in cs[:, 12:]], [r.tobytes() for r in gxy])
+    expect = [1] * K.N
+    cs[5, 12:] = V.fe((V.from_fe(cs[5, 12:]) + 1) % BOUND)      # s + 1
+    ma2 = ma.copy()
+    ma2[140, 0] = V.fe(msgs[140][0] + 1)                         # another message
+    cs[258, :12] = V.fe((V.from_fe(cs[258, :12]) + 1) % BOUND)  # c + 1
+    expect[5] = expect[140] = expect[258] = 0
+    plain, cut, err = K.plain_and_cut(monkeypatch, capfd, lambda: D.proof_to_hash(pk, ma2, (gxy, ginf), cs))
+    assert K.chunk_lines(err, "vb_single") == K.THREE and K.chunk_lines(err, "vb_joint") == K.THREE, err
+    assert K.identical(plain, cut)
+    out, st = cut
+    assert [int(x) for x in st] == expect
+    assert not out[[5, 140, 258]].any()
+    for i in K.SAMPLE + (5, 131, 140, 258):
+        proof = (V.pt_from_abi(gxy[i], ginf[i]), V.from_fe(cs[i][:12]), V.from_fe(cs[i][12:]))
+        code, o = V.proof_to_hash(V.pt_from_abi(pk[0][i], pk[1][i]), [V.from_fe(ma2[i, 0])], proof)
+        assert int(st[i]) == code, i
+        if code == ecvrf_ref.OK:
+            assert V.from_fe(out[i]) == o, i

@@ -195,3 +195,169 @@ def test_groth16_no_public_inputs(pairing, e0):
         assert _verify(pairing, pvk, cases) == [1, 0, 0, 0]
     finally:
         pvk.close()
+
+
+# ---- 8. the chunks of launch_pairs after the first (tests/slab_chunks.py)
+@pytest.mark.parametrize("k", [1, 3])
+def test_pairing_product_in_three_slab_chunks(pairing, e0, k, monkeypatch, capfd):
+    """gh_pairing_product of 261 rows in chunks of 128, 128 and 5 rows: pair t = i k + j of row i is ((a0 + t) G1, (b0 + 7 t) G2),
+    so no two rows share a point, and the row's value is e0^(sum_j a b): every row against the restatement, not a sample"""
+    import slab_chunks as K
+    rng = random.Random(261 + k)
+    a0, b0 = rng.randrange(1 << 19, 1 << 20), rng.randrange(1 << 19, 1 << 20)
+    m = K.N * k
+    P, Q, H2 = C1.mul(a0, C1.G), C2.mul(b0, C2.G), C2.mul(7, C2.G)
+    ps, qs = [], []
+    for _ in range(m):
+        ps.append(P)
+        qs.append(Q)
+        P, Q = C1.add(P, C1.G), C2.add(Q, H2)
+    assert len(set(ps)) == m and len(set(qs)) == m
+    assert ps[m - 1] == C1.mul(a0 + m - 1, C1.G) and qs[m - 1] == C2.mul(b0 + 7 * (m - 1), C2.G)
+    ab = [[(a0 + i * k + j, b0 + 7 * (i * k + j)) for j in range(k)] for i in range(K.N)]
+    ps[131 * k] = None                                                           # P at infinity: in the second chunk only
+    ab[131][0] = (0, 0)
+    qs[258 * k + k - 1] = None                                                   # Q at infinity: in the tail only
+    ab[258][k - 1] = (0, 0)
+    g1, g2 = g1_batch(ps), g2_batch(qs)
+    plain, cut, err = K.plain_and_cut(monkeypatch, capfd, lambda: pairing.pairing_product(g1, g2, k=k))
+    assert K.chunk_lines(err, "launch_pairs") == K.THREE, err
+    assert K.identical(plain, cut)
+    exp = [pr.fpow(e0, sum(a * b for a, b in row) % r) for row in ab]
+    if k == 1:
+        assert exp[131] == exp[258] == pr.ONE
+    bad = [i for i in range(K.N) if fq4_of(cut[i]) != exp[i]]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("tables", [None, "1"])
+def test_groth16_verify_in_three_slab_chunks(pairing, g16, tables, monkeypatch, capfd):
+    """test_groth16_batch's seeded shuffle of the seven cases at 261 rows, so that the rows of status 2 and the skipped pairs fall
+    into every chunk; with GH_GROTH16_TABLES=1 the second input's part of g_ic goes through vb_single across the chunks too"""
+    import slab_chunks as K
+    for seed in range(K.N, K.N + 100):                                           # the first shuffle that puts a skipped pair (case 5, A at
+        order = [i % 7 for i in range(K.N)]                                      # infinity) and a row of status 2 (case 6) into every chunk,
+        random.Random(seed).shuffle(order)                                       # the tail of 5 rows included
+        if all({5, 6} <= set(order[lo:hi]) for lo, hi in ((0, 128), (128, 256), (256, K.N))):
+            break
+    else:
+        raise AssertionError("no shuffle found")
+    cases = [g16["cases"][i] for i in order]
+    blob = pairing.parameters_with_pairing(g16["blob"])
+    if tables is None:
+        monkeypatch.delenv("GH_GROTH16_TABLES", raising=False)
+    else:
+        monkeypatch.setenv("GH_GROTH16_TABLES", tables)                          # read when a key is first used
+    pvk = pairing.PreparedVerifyingKey.from_parameters(blob)
+    try:
+        plain, cut, err = K.plain_and_cut(monkeypatch, capfd, lambda: _verify(pairing, pvk, cases))
+    finally:
+        pvk.close()
+    assert K.chunk_lines(err, "launch_pairs") == K.THREE, err
+    assert K.chunk_lines(err, "vb_single") == (K.THREE if tables else []), err
+    assert plain == cut
+    assert cut == [g16["expected"][i] for i in order]
+
+
+# ---- 9. g_ic and the proof points at their edges, on a key with known exponents
+@pytest.fixture(scope="module")
+def edge_key(e0):
+    """gamma_abc_g1 = [x0 G1 .. x3 G1], alpha_g1_beta_g2 = e0^(alpha beta), gamma_g2 = gamma G2, delta_g2 = delta G2: for
+    inputs s, g_ic = g G1 with g = x0 + s1 x1 + s2 x2 + s3 x3, and (a G1, b G2, c G1) is valid iff a b = alpha beta + g gamma + c delta.
+    The rows: every input row once with c solved (status 1) and once with one input increased by 1 (status 0), then the
+    proof-point rows."""
+    import schnorr_ref
+    assert pyref.P6.p == r
+    rng = random.Random(19)
+    g1 = lambda k: schnorr_ref.mul(C1, k % r, C1.G)
+    inv = lambda v: pow(v, -1, r)
+    alpha, beta, gamma, delta = (rng.randrange(1, r) for _ in range(4))
+    x = [rng.randrange(1, r) for _ in range(4)]
+    ab0 = alpha * beta % r
+    g_of = lambda s: (x[0] + sum(si * xi for si, xi in zip(s, x[1:]))) % r
+    rnd = lambda: rng.randrange(2, r - 1)
+    s4, s5, s7 = [x[0] * inv(x[1]) % r, rnd(), rnd()], [-x[0] * inv(x[1]) % r, rnd(), rnd()], [rnd(), rnd(), 0]
+    s7[2] = -(x[0] + s7[0] * x[1] + s7[1] * x[2]) * inv(x[3]) % r
+    s_rows = [[0, 0, 0], [1, r - 1, 0], [r - 1, r - 1, r - 1],
+              s4,                                                                # x0 G1 + s1 x1 G1: the first accumulation is a doubling
+              s5,                                                                # ... passes through the point at infinity
+              [rnd(), 0, rnd()],                                                 # a zero input between non-zero inputs
+              s7]                                                                # g_ic ends at the point at infinity
+    assert (x[0] + s4[0] * x[1]) % r == 2 * x[0] % r and (x[0] + s5[0] * x[1]) % r == 0 and g_of(s7) == 0
+    rows, expected = [], []                                                      # (A, B, C, inputs)
+
+    def proof(s, a=None, b=None, c=None):
+        """a valid proof for the inputs s; of a, b, c at most two given, the third solved"""
+        g = g_of(s)
+        a = rng.randrange(1, 1 << 64) if a is None else a
+        if c is None:
+            b = rng.randrange(1, 1 << 20) if b is None else b
+            c = (a * b - ab0 - g * gamma) * inv(delta) % r
+        elif b is None:
+            b = (ab0 + g * gamma + c * delta) * inv(a) % r
+        return a, b, c
+
+    for j, s in enumerate(s_rows):
+        a, b, c = proof(s)
+        A, B, C = g1(a), C2.mul(b, C2.G), g1(c)
+        rows.append((A, B, C, list(s)))
+        t = list(s)
+        t[j % 3] = (t[j % 3] + 1) % r
+        rows.append((A, B, C, t))
+        expected += [1, 0]
+    s = [rnd(), rnd(), rnd()]
+    g = g_of(s)
+    a, b, _ = proof(s, c=0)                                                      # C at infinity, b = (alpha beta + g gamma) / a
+    rows.append((g1(a), C2.mul(b, C2.G), None, s))
+    c = -(ab0 + g * gamma) * inv(delta) % r                                      # B at infinity: e(A, B) is one
+    rows.append((g1(rng.randrange(1, r)), None, g1(c), s))
+    a, b, c = proof(s)
+    A, B, C = g1(a), C2.mul(b, C2.G), g1(c)
+    B_off = (B[0], (B[1][0], (B[1][1] + 1) % pr.p))
+    C_off = (C[0], ((C[1][0] + 1) % pr.p,))
+    assert C2.on_curve(B) and not C2.on_curve(B_off) and C1.on_curve(C) and not C1.on_curve(C_off)
+    rows += [(A, B_off, C, s), (A, B, C_off, s), (A, B, C, s)]                   # the last row: A's infinity byte is set below
+    expected += [1, 1, 2, 2, 0]
+    n = len(rows)
+    a_xy, a_inf = g1_batch([row[0] for row in rows])
+    a_xy[n - 1] = np.array(pr.limbs(1) + pr.limbs(1), dtype=np.uint64)           # the point at infinity with coordinates (1, 1):
+    a_inf[n - 1] = 1                                                             # on the curve, so evaluated as A = infinity
+    inputs = np.array([[pyref.int_to_limbs(pyref.P6.to_mont(v)) for v in row[3]] for row in rows], dtype=np.uint64).reshape(n, 3, 12)
+    vk = {"alpha_g1_beta_g2": pr.fpow(e0, ab0), "gamma_g2": C2.mul(gamma, C2.G), "delta_g2": C2.mul(delta, C2.G),
+          "gamma_abc_g1": [g1(v) for v in x]}
+    return {"vk": vk, "rows": rows, "expected": expected, "a": (a_xy, a_inf), "b": g2_batch([row[1] for row in rows]),
+            "c": g1_batch([row[2] for row in rows]), "inputs": inputs}
+
+
+@pytest.mark.parametrize("tables", [None, "0", "1"])
+def test_groth16_g_ic_and_proof_point_edges(pairing, edge_key, tables, monkeypatch):
+    """inputs 0, 1 and r - 1, an accumulation that doubles, one that passes through infinity and one that ends there; B and C
+    off their curves, B, C and A at infinity.  A g_ic at infinity contributes one to the product: this pins the deviation that
+    include/ginger_hip_pairing.h documents.  A fresh key for each setting of GH_GROTH16_TABLES (unset: every input by a
+    fixed-base table; 0: every input by the variable-base kernels; 1: the first by a table, the others by variable base)."""
+    K = edge_key
+    vk = K["vk"]
+    if tables is None:
+        monkeypatch.delenv("GH_GROTH16_TABLES", raising=False)
+    else:
+        monkeypatch.setenv("GH_GROTH16_TABLES", tables)
+    pvk = pairing.PreparedVerifyingKey(fq4_row(vk["alpha_g1_beta_g2"]), pr.g2_row(vk["gamma_g2"]), pr.g2_row(vk["delta_g2"]),
+                                       np.stack([pr.g1_row(P) for P in vk["gamma_abc_g1"]]))
+    try:
+        assert pvk.num_inputs == 3
+        got = [int(v) for v in pvk.verify(K["a"], K["b"], K["c"], K["inputs"])]
+        assert got == K["expected"]
+        # the pooled buffers of the batch serve a shorter call on the same key
+        first = pvk.verify(tuple(v[:5] for v in K["a"]), tuple(v[:5] for v in K["b"]), tuple(v[:5] for v in K["c"]), K["inputs"][:5])
+        assert [int(v) for v in first] == K["expected"][:5]
+    finally:
+        pvk.close()
+
+
+def test_groth16_edge_rows_against_the_restatement(edge_key):
+    """two of the rows above through pairing_ref.groth16_verify: the valid proof whose g_ic is the point at infinity, and the
+    rejected twin of the row whose accumulation doubles"""
+    K = edge_key
+    for i in (12, 7):
+        A, B, C, s = K["rows"][i]
+        assert int(pr.groth16_verify(K["vk"], (A, B, C), s)) == K["expected"][i], i

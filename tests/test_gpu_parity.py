@@ -104,6 +104,14 @@ for log_n in (13, 17, 20):
         dom.fft_dev(buf, fl)
         out["%%d_%%d" %% (log_n, fl)] = zlib.crc32(buf.download().tobytes())
     buf.free()
+# inputs next to the modulus (p - 1 - i) at 2^13: where a lazy reduction of the pass would go wrong
+a = S.scalar_array([pyref.P6.p - 1 - i for i in range(1 << 13)])
+dom = gl.EvaluationDomain("mnt4753_fr", 1 << 13)
+buf = gl.DeviceBuffer(96 << 13).upload(a)
+for fl in (0, 2, 3, 1):
+    dom.fft_dev(buf, fl)
+    out["edge13_%%d" %% fl] = zlib.crc32(buf.download().tobytes())
+buf.free()
 print("CRC " + json.dumps(out, sort_keys=True))
 """ % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GH_NTT_ASM="0")
@@ -120,6 +128,13 @@ print("CRC " + json.dumps(out, sort_keys=True))
             dom.fft_dev(buf, fl)
             assert zlib.crc32(buf.download().tobytes()) == ref["%d_%d" % (log_n, fl)], (log_n, fl)
         buf.free()
+    a = S.scalar_array([pyref.P6.p - 1 - i for i in range(1 << 13)])
+    dom = gpu.EvaluationDomain("mnt4753_fr", 1 << 13)
+    buf = gpu.DeviceBuffer(96 << 13).upload(a)
+    for fl in (0, 2, 3, 1):
+        dom.fft_dev(buf, fl)
+        assert zlib.crc32(buf.download().tobytes()) == ref["edge13_%d" % fl], ("edge13", fl)
+    buf.free()
 
 
 def test_vec_ops(gpu):
@@ -140,6 +155,78 @@ def test_vec_ops(gpu):
     exp = a.copy()
     S.oracle().oracle_vec_mul(0, S.ptr(exp), S.ptr(bb), n)
     assert (got == exp).all()
+
+
+# ---- the device build of fp29.h at the extremes (tests/test_fp29_host.py has the host build of the same header there)
+def edge_values(p):
+    """raw limb values below p at which a carry, a conditional subtraction or a lazily reduced sum goes wrong first: around 0 and
+    p, around p / 2, the Montgomery radix, the top bit, every 29-bit limb saturated alone, and every run of saturated low limbs"""
+    v = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, (1 << 768) % p, 1 << 752, (1 << 752) - 1]
+    v += [((1 << 29) - 1) << (29 * j) for j in range(26)]
+    v += [(1 << k) - 1 for k in range(29, 726, 29)] + [(1 << 752) - 1]
+    out = []
+    for x in v:
+        if x < p and x not in out:
+            out.append(x)
+    return out
+
+
+@pytest.mark.parametrize("field", ["mnt4753_fr", "mnt6753_fr"])
+def test_vec_ops_at_the_extremes(gpu, field):
+    """gh_vec_mul, gh_vec_sub_dev and gh_vec_scale on every ordered pair of edge_values, against Python integers: the ABI's words
+    are Montgomery residues, so a product of the raw values a, b is a b 2^-768 mod p and a difference is (a - b) mod p.  Then the
+    block edges n = 1, 255, 257 on a prefix of the same vectors (a block of the kernel is 256 rows)."""
+    p = S.FIELD_OF[field].p
+    V = edge_values(p)
+    assert len(V) >= 55 and len(set(V)) == len(V) and max(V) == p - 1
+    rinv = pow(1 << 768, -1, p)
+    av = [a for a in V for _ in V]
+    bv = [b for _ in V for b in V]
+    n = len(av)
+    assert n == len(V) ** 2 and 3000 < n < 5000 and set(bv[:255]) == set(V) and p - 1 in av[:255]
+    a, b = S.scalar_array(av), S.scalar_array(bv)
+    lib = gpu.load_library()
+    dom = gpu.EvaluationDomain(field, 1)
+
+    def sub_dev(x, y):
+        m = len(x)
+        dx, dy = gpu.DeviceBuffer(m * 96).upload(x), gpu.DeviceBuffer(m * 96).upload(y)
+        try:
+            gpu._check(lib.gh_vec_sub_dev(gpu.FIELDS[field], dx.ptr, dy.ptr, m))
+            return dx.download().reshape(m, 12)
+        finally:
+            dx.free()
+            dy.free()
+
+    def rows(arr):
+        return [S.to_int(r) for r in np.asarray(arr).reshape(-1, 12)]
+
+    scalars = [0, 1, p - 1, (1 << 768) % p]
+    for m in (n, 1, 255, 257):
+        got = rows(dom.mul_polynomials_in_evaluation_domain(a[:m], b[:m]))
+        assert got == [x * y * rinv % p for x, y in zip(av[:m], bv[:m])], ("mul", m)
+        got = rows(sub_dev(a[:m], b[:m]))
+        assert got == [(x - y) % p for x, y in zip(av[:m], bv[:m])], ("sub", m)
+        for s in scalars:
+            got = rows(gpu.vec_scale(field, b[:m], S.u64(s)))
+            assert got == [y * s * rinv % p for y in bv[:m]], ("scale", m, s)
+
+
+def edge_vectors(p, n):
+    return {"all p-1": [p - 1] * n, "0, p-1 alternating": [(p - 1) * (i & 1) for i in range(n)], "p-1-i": [p - 1 - i for i in range(n)]}
+
+
+@pytest.mark.parametrize("field,log_n", [("mnt4753_fr", l) for l in (4, 10, 13)] + [("mnt6753_fr", l) for l in (6, 12)])
+def test_ntt_at_the_extremes_vs_oracle(gpu, field, log_n):
+    """the four transforms on inputs next to the modulus, where a lazily reduced butterfly overflows first: below, across and
+    above the 2^9 tile and a transform of two passes (mnt4753_fr), one and two passes (mnt6753_fr)"""
+    n = 1 << log_n
+    dom = gpu.EvaluationDomain(field, n)
+    for name, vals in edge_vectors(S.FIELD_OF[field].p, n).items():
+        a = S.scalar_array(vals)
+        for nm, flags in FLAGS:
+            got = getattr(dom, nm)(a).reshape(-1, 12)
+            assert (got == S.oracle_fft(field, a, log_n, flags, 16)).all(), (field, log_n, name, nm)
 
 
 @pytest.mark.parametrize("field,log_n", [("mnt4753_fr", 0), ("mnt4753_fr", 1), ("mnt4753_fr", 10), ("mnt4753_fr", 15), ("mnt6753_fr", 9)])

@@ -361,3 +361,76 @@ def test_generator_table_follows_the_batch_size(gpu, refs):
     finally:
         D.close()
         prm.close()
+
+
+# ---------------------------------------------------------------- the chunks after the first (tests/slab_chunks.py)
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_batch_mul_in_three_slab_chunks(gpu, refs, scheme, monkeypatch, capfd):
+    """gh_batch_mul of 261 rows in chunks of 128, 128 and 5 rows: the chunk line, the same bits as in one chunk, and the
+    restatement's points at both sides of every chunk edge and in the special rows, which sit in the later chunks only"""
+    from ginger_lib_amd import schnorr
+    import slab_chunks as K
+    S = refs[scheme]
+    C, curve = S.C, schnorr_ref.SCHEMES[scheme][1]
+    rng = random.Random(261 + len(scheme))
+    P = schnorr_ref.mul(C, rng.randrange(1, S.r), S.G)
+    pts = []
+    for _ in range(K.N):                                      # P + i G: a base of its own in every row
+        pts.append(P)
+        P = C.add(P, S.G)
+    ks = [rng.getrandbits(753) for _ in range(K.N)]
+    K.assert_rows_differ(pts, ks)
+    top = (1 << 753) - 1
+    pts[131] = None                                           # rows 3 and 259, 12 and 268, ... are ordinary rows
+    ks[140], ks[150], ks[258] = 0, top, 0
+    xy, inf = _pk_arrays(S, pts)
+    k = limbs(ks)
+    plain, cut, err = K.plain_and_cut(monkeypatch, capfd, lambda: schnorr.batch_mul(curve, xy, k, inf))
+    assert K.chunk_lines(err, "vb_single") == K.THREE, err
+    assert K.identical(plain, cut)
+    for i in K.SAMPLE + (131, 140, 150, 258):
+        want = schnorr_ref.mul(C, ks[i], pts[i])
+        X, Y, Z = (S.from_fe(cut[i][12 * c:12 * c + 12]) for c in range(3))
+        if want is None:
+            assert Z == 0 and i in (131, 140, 258), i
+        else:
+            zi = pow(Z, -1, S.p)
+            assert (X * zi % S.p, Y * zi % S.p) == (want[0][0], want[1][0]), i
+
+
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_verify_in_three_slab_chunks(schemes, refs, scheme, monkeypatch, capfd):
+    """Schnorr verify of the restatement's 261 signatures (tests/golden/schnorr_chunk_rows.json, written by
+    tests/golden/gen_schnorr_chunk_rows.py) with one spoilt row in each chunk"""
+    import json
+    import os
+    import slab_chunks as K
+    S, D = refs[scheme], schemes[scheme]
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "schnorr_chunk_rows.json")) as f:
+        rows = json.load(f)[scheme]
+    sk0, m0, m_step = (int(rows[x], 16) for x in ("sk0", "m0", "m_step"))
+    sigs = [(int(e, 16), int(s, 16)) for e, s in rows["sigs"]]
+    nonces = [int(x, 16) for x in rows["nonces"]]
+    msgs = [[(m0 + i * m_step) % S.p] for i in range(K.N)]
+    pk, pks = S.pk(sk0), []
+    for _ in range(K.N):
+        pks.append(pk)
+        pk = S.C.add(pk, S.G)
+    assert pks[260] == S.pk(sk0 + 260)
+    K.assert_rows_differ(pks, [m[0] for m in msgs], [e for e, _ in sigs], [s for _, s in sigs], nonces)
+    for i in (0, 260):                                        # the file holds what the restatement signs
+        assert S.sign_with(sk0 + i, pks[i], msgs[i], nonces[i]) == sigs[i], i
+    expect = [1] * K.N
+    e, s = sigs[5]
+    sigs[5] = (e, (s + 1) % BOUND)
+    msgs[140] = [(msgs[140][0] + 1) % S.p]
+    e, s = sigs[258]
+    sigs[258] = ((e + 1) % BOUND, s)
+    expect[5] = expect[140] = expect[258] = 0
+    pka, ma, sg = _pk_arrays(S, pks), _msg_arr(S, msgs, 1), _sig_arr(S, sigs)
+    plain, cut, err = K.plain_and_cut(monkeypatch, capfd, lambda: D.verify(pka, ma, sg))
+    assert K.chunk_lines(err, "vb_single") == K.THREE, err
+    assert K.identical(plain, cut)
+    assert [int(x) for x in cut] == expect
+    for i in K.SAMPLE + (5, 140, 258):
+        assert {True: 1, False: 0, None: 2}[S.verify(pks[i], msgs[i], sigs[i])] == int(cut[i]), i
