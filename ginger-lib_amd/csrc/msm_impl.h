@@ -597,7 +597,7 @@ struct MsmJob {
         return GH_OK;
     }
 
-    // one level of the bucket reduction: `grid` wave programs (msm_kernels.h 5 / 5b) over up to three inputs.  G1: the 512-register
+    // one level of the bucket reduction: `grid` wave programs (msm_reduce_kernels.h) over up to three inputs.  G1: the 512-register
     // build of the program (one_wave) or the 256-register one; G2: the lane-group program.
     int reduce_level(unsigned grid, const WaveReduceIn<C>& i0, const WaveReduceIn<C>& i1, const WaveReduceIn<C>& i2, uint32_t per_input,
                      uint32_t n_inputs, uint32_t segs, int L, Proj<C>* out, uint32_t* slabs, bool one_wave, hipStream_t st) {
@@ -621,10 +621,10 @@ struct MsmJob {
         const uint32_t RW = (uint32_t)p.RW, segs = p.segs_per_window, all = 0xFFFFFFFFu;
         const unsigned nb1 = RW * segs, nb2 = 3 * RW;
         const WaveReduceIn<C> none{nullptr, 0, 0, 0, 0, 0};
-        // the programs' accumulators live in a slab of global memory each (msm_kernels.h, ReduceSlab / P3Slab)
+        // the programs' accumulators live in a slab of global memory each (msm_reduce_kernels.h, WaveSlab)
         uint32_t* slabs = nullptr;
         size_t slab_words;
-        if constexpr (DEG >= 2) slab_words = P3Slab::WORDS; else slab_words = ReduceSlab<C>::WORDS;
+        if constexpr (DEG >= 2) slab_words = WaveSlab<P3>::WORDS; else slab_words = WaveSlab<Proj<C>>::WORDS;
         if ((rc = slot_buf("reduce_slabs", slot, (size_t)(nb1 > nb2 ? nb1 : nb2) * slab_words * 4, &slabs))) return rc;
         // A stand-alone G1 MSM has the chip to itself: the 512-register build of the program (one wave per SIMD, 88 B of spills
         // per lane instead of 680) -- inside a batch the reduction must fit beside the accumulation's waves (256 registers).

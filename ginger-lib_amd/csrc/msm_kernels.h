@@ -24,7 +24,7 @@
 //                            and without doublings: "wave programs" whose every step is one
 //                            projective addition from a single inlined call site (serial sums per
 //                            lane, then tree / suffix scan / tree across the 64 lanes through LDS:
-//                            the wavefront-wide bucket reduction); two launches.
+//                            the wavefront-wide bucket reduction); two launches.  In msm_reduce_kernels.h.
 //   6. window fold           ~750 dependent doublings: latency-bound, done on the host
 //                            (msm_fold.h fold_windows) with the reduction's powers of two merged in.
 #pragma once
@@ -32,6 +32,7 @@
 #include "ec29.h"
 #include "aff_kernels.h"
 #include "msm_plan.h"
+#include "msm_schedule.h"
 
 namespace gh {
 
@@ -76,6 +77,14 @@ __device__ __forceinline__ void st_fp(Fp* p, const Fp& a) {
     for (int i = 0; i < NL / 2; i++) q[i] = make_uint2(a.l[2 * i], a.l[2 * i + 1]);
 }
 #endif
+// Lane groups (4b, and the lane-group reduction of msm_reduce_kernels.h): a lane holds coefficient `comp` of a field element of LANES coefficients.
+// Coordinate e of an Aff / Proj in memory is {c0, .., c_(LANES-1)}, so this lane's part is Fp number LANES e + comp of the point.
+template <int LANES> __device__ __forceinline__ Fp ld_coeff(const void* pt, int e, int comp) {
+    return ld_fp(reinterpret_cast<const Fp*>(pt) + LANES * e + comp);
+}
+template <int LANES> __device__ __forceinline__ void st_coeff(void* pt, int e, int comp, const Fp& v) {
+    st_fp(reinterpret_cast<Fp*>(pt) + LANES * e + comp, v);
+}
 
 // ---------------------------------------------------------------- bases: ABI -> internal layout
 // in: n x (2 * DEG * 24) words, x || y, either Montgomery 2^768 (the in-memory form, fp_768.rs:24-30) or --
@@ -685,7 +694,8 @@ msm_scatter_kernel(const int32_t* __restrict__ digits, size_t n, int num_windows
 // ---------------------------------------------------------------- 4. bucket accumulation
 // order[] lists bucket ids by descending size: [0, n_heavy) are heavy (msm_heavy_*_kernel), whose lists are cut into
 // chunks; the task list is [0, n_chunks) chunks of the heavy buckets (the longest tasks, scheduled first), then the buckets
-// order[n_heavy ..], one task per thread (G1) or lane group (G2, 4b); empty buckets store infinity.
+// order[n_heavy ..], one task per thread (G1) or lane group (G2, 4b); empty buckets store infinity.  Every kernel of this
+// section gets its task's (beg, cnt, destination) from ONE decode, msm_schedule.h acc_task_decode.
 //
 // The reference's `P == Q -> double` branch (swp.rs:492-495) is reached when a bucket's running sum equals the incoming
 // base (duplicate bases); instead of a doubling formula the thread then takes a three-step detour through a fixed "salt"
@@ -696,7 +706,7 @@ msm_scatter_kernel(const int32_t* __restrict__ digits, size_t n, int num_windows
 // [starts[g] - list_base, + counts[g]) of `bases` directly (no index list, no signs) and infinity markers are skipped.
 
 // ---------------------------------------------------------------- 4-asm. task table of the assembly accumulation kernel
-// The task decode of msm_accumulate_xyzz_kernel (chunks of the heavy buckets first, then every other
+// The task decode of section 4 (acc_task_decode: chunks of the heavy buckets first, then every other
 // bucket by descending size) as a table, so that the assembly kernel (asmgen/g1_xyzz.py) starts from (beg, cnt, dst).
 struct AccTaskRec {
     uint32_t beg, cnt;
@@ -709,20 +719,10 @@ msm_acc_tasks_kernel(const uint32_t* __restrict__ starts, const uint32_t* __rest
                      uint32_t n_chunks, uint32_t chunk, Proj<C>* __restrict__ partials, AccTaskRec* __restrict__ out) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_chunks + (total - n_heavy)) return;
+    const auto k = acc_task_decode<false>(t, starts, counts, order, buckets, chunk_start, n_heavy, n_chunks, chunk, partials, 0, 0);
     AccTaskRec r;
-    if (t >= n_chunks) {
-        const uint32_t g = order[n_heavy + (t - n_chunks)];
-        r.beg = starts[g]; r.cnt = counts[g];
-        r.dst = (uint64_t)(uintptr_t)(buckets + g);
-    } else {
-        uint32_t lo = 0, hi = n_heavy;   // largest h with chunk_start[h] <= t
-        while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (chunk_start[mid] <= t) lo = mid; else hi = mid; }
-        const uint32_t g = order[lo], j = t - chunk_start[lo];
-        r.beg = starts[g] + j * chunk;
-        uint32_t cnt = counts[g] - j * chunk;
-        r.cnt = cnt > chunk ? chunk : cnt;
-        r.dst = (uint64_t)(uintptr_t)(partials + t);
-    }
+    r.beg = k.beg; r.cnt = k.cnt;
+    r.dst = (uint64_t)(uintptr_t)k.dst;
     out[t] = r;
 }
 
@@ -745,25 +745,9 @@ msm_accumulate_xyzz_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __r
     static_assert(C::F::DEG == 1, "XYZZ accumulation kernel: prime-field curves");
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_chunks + (total - n_heavy)) return;
-    uint32_t beg, cnt;
-    Proj<C>* dst;
-    if constexpr (AFFIN) {
-        const uint32_t g = g_first + t;
-        beg = starts[g] - list_base; cnt = counts[g];
-        dst = buckets + g;
-    } else if (t >= n_chunks) {
-        const uint32_t g = order[n_heavy + (t - n_chunks)];
-        beg = starts[g]; cnt = counts[g];
-        dst = buckets + g;
-    } else {
-        uint32_t lo = 0, hi = n_heavy;   // largest h with chunk_start[h] <= t
-        while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (chunk_start[mid] <= t) lo = mid; else hi = mid; }
-        const uint32_t g = order[lo], j = t - chunk_start[lo];
-        beg = starts[g] + j * chunk;
-        cnt = counts[g] - j * chunk;
-        if (cnt > chunk) cnt = chunk;
-        dst = partials + t;
-    }
+    const auto tk = acc_task_decode<AFFIN>(t, starts, counts, order, buckets, chunk_start, n_heavy, n_chunks, chunk, partials, g_first, list_base);
+    const uint32_t beg = tk.beg, cnt = tk.cnt;
+    Proj<C>* dst = tk.dst;
     __shared__ uint32_t park[2][NL][256];     // [0]: X, [1]: Y of this thread's running sum
     auto put = [&](int s, const Fp& v) {
 #pragma unroll
@@ -865,7 +849,7 @@ template <class P, int NR> struct F2S {
     typedef Fp T;
     static constexpr int DEG = 1;   // per-lane footprint
     static constexpr int LANES = 2;
-    static constexpr int WAVES = 1;
+    static constexpr int WAVES = 1;   // measured (twice): accumulation 119 ms at 1 wave / SIMD vs 135 ms at 2 (1.5 KB of spills), 2^20 pairs
     static __device__ __forceinline__ bool odd() { return (threadIdx.x & 1u) != 0; }
     static __device__ __forceinline__ T swap(const T& a) {
         T r;
@@ -1001,9 +985,6 @@ template <class P, int NR> struct F3S {
 
 // Same task list, salt detour and addition (madd-1998-cmo) as section 4, LANES lanes per task (2: Fq2 pairs, 3: Fq3
 // triples; a wave carries 64 / LANES tasks, the remaining lane of a triple wave idles).
-#ifndef GH_SPLIT_WAVES
-#define GH_SPLIT_WAVES 1   // measured on Fq2 (twice): 119 ms at 1 wave/SIMD (512 registers) vs 135 ms at 2 (1.5 KB of spills), 2^20 pairs
-#endif
 // AFFIN: as in section 4 -- the input is the T64 output list of the affine rounds.
 template <class C, class F, int LANES, bool AFFIN = false>
 __global__ void __launch_bounds__(256, F::WAVES)
@@ -1022,27 +1003,10 @@ msm_accumulate_split_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __
     uint32_t beg = 0, cnt = 0;
     Proj<C>* dst = buckets;
     if (live) {
-        if constexpr (AFFIN) {
-            const uint32_t g = g_first + t;
-            beg = starts[g] - list_base; cnt = counts[g];
-            dst = buckets + g;
-        } else if (t >= n_chunks) {
-            const uint32_t g = order[n_heavy + (t - n_chunks)];
-            beg = starts[g]; cnt = counts[g];
-            dst = buckets + g;
-        } else {
-            uint32_t lo = 0, hi = n_heavy;
-            while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (chunk_start[mid] <= t) lo = mid; else hi = mid; }
-            const uint32_t g = order[lo], j = t - chunk_start[lo];
-            beg = starts[g] + j * chunk;
-            cnt = counts[g] - j * chunk;
-            if (cnt > chunk) cnt = chunk;
-            dst = partials + t;
-        }
+        const auto tk = acc_task_decode<AFFIN>(t, starts, counts, order, buckets, chunk_start, n_heavy, n_chunks, chunk, partials, g_first, list_base);
+        beg = tk.beg; cnt = tk.cnt; dst = tk.dst;
     }
     __shared__ uint32_t park[NL][256];
-    // this lane's coefficient: element e of an Aff / Proj is {c0, .., c_(LANES-1)} -> Fp index LANES e + comp
-    auto ld_comp = [&](const void* base, int e) { return ld_fp(reinterpret_cast<const Fp*>(base) + LANES * e + comp); };
     Fp ax = fp_zero(), ay = F::one(), az = fp_zero();   // (0, 1, 0)
     uint32_t k = 0;
     int phase = 0, salt_id = 0;
@@ -1052,8 +1016,8 @@ msm_accumulate_split_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __
         guard++;
         Fp qx, qy;
         if (phase == 1 || phase == 3) {
-            qx = ld_comp(salts + salt_id, 0);
-            qy = ld_comp(salts + salt_id, 1);
+            qx = ld_coeff<LANES>(salts + salt_id, 0, comp);
+            qy = ld_coeff<LANES>(salts + salt_id, 1, comp);
             if (phase == 3) qy = F::neg(qy);
         } else if constexpr (AFFIN) {
             const uint32_t e = beg + k;
@@ -1065,8 +1029,8 @@ msm_accumulate_split_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __
         } else {
             const uint32_t e = sorted[beg + k];
             const Aff<C>* b = bases + (e & 0x7FFFFFFFu);
-            qx = ld_comp(b, 0);
-            qy = ld_comp(b, 1);
+            qx = ld_coeff<LANES>(b, 0, comp);
+            qy = ld_coeff<LANES>(b, 1, comp);
             if (e >> 31) qy = F::neg(qy);
         }
         if (F::is_zero(az)) {
@@ -1075,7 +1039,7 @@ msm_accumulate_split_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __
             Fp v = F::mul(qx, az);
             Fp u = F::mul(qy, az);
             if (phase == 0 && F::eq(u, ay) && F::eq(v, ax)) {
-                salt_id = F::eq(qx, ld_comp(salts, 0)) ? 1 : 0;
+                salt_id = F::eq(qx, ld_coeff<LANES>(salts, 0, comp)) ? 1 : 0;
                 phase = 1;
                 continue;
             }
@@ -1108,10 +1072,9 @@ msm_accumulate_split_kernel(const Aff<C>* __restrict__ bases, const uint32_t* __
         if (phase == 0 || phase == 3) { k++; phase = 0; } else phase++;
     }
     if (live) {
-        Fp* o = reinterpret_cast<Fp*>(dst);
-        st_fp(o + 0 * LANES + comp, ax);
-        st_fp(o + 1 * LANES + comp, ay);
-        st_fp(o + 2 * LANES + comp, az);
+        st_coeff<LANES>(dst, 0, comp, ax);
+        st_coeff<LANES>(dst, 1, comp, ay);
+        st_coeff<LANES>(dst, 2, comp, az);
     }
 }
 
@@ -1147,488 +1110,7 @@ msm_heavy_combine_kernel(const Proj<C>* __restrict__ partials, const uint32_t* _
     if (lane == 0) st_proj<C>(buckets + order[h], acc);
 }
 
-// ---------------------------------------------------------------- 5. bucket reduction
-// sum_b b * B_b per window, without the reference's per-window inversion (variable_base.rs:60-66)
-// and without any doubling or function call on the device.
-//
-// msm_wave_reduce_kernel is a "wave program": one wave per segment of 64 * L consecutive items of
-// one window; lane l owns items l, l + 64, l + 128, ... (stride 64).  Every step of the program is
-// one projective addition issued from a SINGLE inlined call site (operands are selected per
-// step; the earlier call-based version moved ~7 KB of scratch per addition and was
-// scratch-bandwidth bound).  The program's accumulators are parked in a global slab between steps
-// (ReduceSlab below):
-//   steps 0 .. 2L-2   serial:  run += item_i  (i = L-1 .. 0),  wacc += run      -> run_l = sum_i x,
-//                                                                                   wacc_l = sum_i i * x
-//   6 steps           tree over lanes of wacc                    -> A  = sum_l wacc_l
-//   6 steps           suffix scan over lanes of run              -> S_l = sum_{m >= l} run_m;  runW = S_0
-//   6 steps           tree over lanes l >= 1 of S                -> Bv = sum_l l * run_l
-// With item index = l + 64 i:   sum_items index * x = 64 * A + Bv,  sum_items x = runW.
-// mode 1 (plain sum) stops after the serial part and a tree over run.
-// mode 2 ("lean" level 1, msm_impl.h) stops after the serial part and stores every lane's (run_l, wacc_l) -- out[(program * 64
-// + l) * 2 + {0, 1}] -- for a second level that works on LANES instead of segments: the 18 cross-lane steps, in which most
-// lanes idle, are then issued once per window instead of once per segment.
-// Equal operands (acc == x as points, the reference's doubling branch) are detected in the
-// addition; the whole wave then spends three extra steps on a detour through a salt point
-// (p + S) + q - S for the affected lanes.  Powers of two (64, 64 L) that weight the outputs are
-// NOT applied here: they are folded into the host's Horner loop over the windows, where the
-// doublings are needed anyway (msm_fold.h: fold_windows).
-template <class C> struct WaveReduceIn {
-    const Proj<C>* base;   // item (w, k) = base[(w * count + k) * stride + offset]
-    uint32_t stride, offset, count, mode;
-    uint32_t valid;        // items with flat index w * count + k >= valid are padding (infinity)
-};
-
-// branch-free projective addition with selects for the infinity cases; same = (p == q as points)
-template <class C> struct ReduceField { typedef typename C::F type; };          // G1: inlined products
-template <> struct ReduceField<Mnt4G2> { typedef Mnt4G2::FC type; };                 // towers: out of line (code size)
-template <> struct ReduceField<Mnt6G2> { typedef Mnt6G2::FC type; };
-template <class C> __device__ __forceinline__ Proj<C> proj_add_sel(const Proj<C>& p, const Proj<C>& q, bool& same) {
-    typedef typename ReduceField<C>::type F;
-    const bool pz = F::is_zero(p.z), qz = F::is_zero(q.z);
-    typename F::T y1z2 = F::mul(p.y, q.z);
-    typename F::T x1z2 = F::mul(p.x, q.z);
-    typename F::T z1z2 = F::mul(p.z, q.z);
-    typename F::T u = F::sub(F::mul(p.z, q.y), y1z2);
-    typename F::T v = F::sub(F::mul(p.z, q.x), x1z2);
-    same = !pz && !qz && F::is_zero(u) && F::is_zero(v);
-    typename F::T uu = F::sqr(u);
-    typename F::T vv = F::sqr(v);
-    typename F::T vvv = F::mul(v, vv);
-    typename F::T r = F::mul(vv, x1z2);
-    typename F::T a = F::sub(F::sub(F::mul(uu, z1z2), vvv), F::dbl(r));
-    Proj<C> o;
-    o.x = F::mul(v, a);
-    o.y = F::mul_sub_mul(F::sub(r, a), u, vvv, y1z2);
-    o.z = F::mul(vvv, z1z2);
-    uint32_t* ow = reinterpret_cast<uint32_t*>(&o);
-    const uint32_t* pw = reinterpret_cast<const uint32_t*>(&p);
-    const uint32_t* qw = reinterpret_cast<const uint32_t*>(&q);
-#pragma unroll
-    for (int k = 0; k < (int)(sizeof(Proj<C>) / 4); k++) ow[k] = pz ? qw[k] : (qz ? pw[k] : ow[k]);
-    return o;
-}
-
-// A block may carry blockDim.x / 64 INDEPENDENT waves (each its own program and LDS region, so the
-// exchanges need wave-level ordering only, no s_barrier).  Measured at 2^20 buckets: 1, 2, 3 or 4
-// waves per block, with or without a block barrier per step, all take the same time for level 1
-// -- the default is 1.
-#define GH_WAVE_SYNC()                                           \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
-        __builtin_amdgcn_wave_barrier();                         \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
-    } while (0)
-// The same addition WITHOUT the final selects: p and q are dead after the first five products, which is what lets the step
-// fit the register budget; the caller patches the lanes with an infinite operand (pz / qz) from re-loaded operands.
-template <class C> __device__ __forceinline__ Proj<C> proj_add_raw(const Proj<C>& p, const Proj<C>& q, bool& same, bool& pz, bool& qz) {
-    typedef typename ReduceField<C>::type F;
-#define GH_RFENCE() __builtin_amdgcn_sched_barrier(0)      // keep the written order: at most eight field elements live
-    pz = F::is_zero(p.z); qz = F::is_zero(q.z);
-    typename F::T y1z2 = F::mul(p.y, q.z);
-    GH_RFENCE();
-    typename F::T u = F::sub(F::mul(p.z, q.y), y1z2);
-    GH_RFENCE();
-    typename F::T x1z2 = F::mul(p.x, q.z);
-    GH_RFENCE();
-    typename F::T v = F::sub(F::mul(p.z, q.x), x1z2);
-    GH_RFENCE();
-    typename F::T z1z2 = F::mul(p.z, q.z);                 // p, q dead
-    GH_RFENCE();
-    same = !pz && !qz && F::is_zero(u) && F::is_zero(v);
-    typename F::T vv = F::sqr(v);
-    GH_RFENCE();
-    typename F::T r = F::mul(vv, x1z2);                    // x1z2 dead
-    GH_RFENCE();
-    typename F::T vvv = F::mul(v, vv);                     // vv dead
-    GH_RFENCE();
-    typename F::T uu = F::sqr(u);
-    GH_RFENCE();
-    typename F::T a = F::sub(F::sub(F::mul(uu, z1z2), vvv), F::dbl(r));   // uu dead
-    GH_RFENCE();
-    Proj<C> o;
-    o.x = F::mul(v, a);                                    // v dead
-    GH_RFENCE();
-    o.z = F::mul(vvv, z1z2);                               // z1z2 dead
-    GH_RFENCE();
-    // Y3 = (r - a) u - vvv y1z2 as ONE dual product on a single accumulator chain (fp_mul2s, as in the XYZZ accumulation: one
-    // Montgomery reduction of fourteen saved; the kernel's scratch frame is unchanged by it: 736 -> 640 B per lane in the
-    // 512-register build, 1760 -> 1792 B in the 256-register one).  The towers keep two products.
-    o.y = F::mul_sub_mul1(F::sub(r, a), u, vvv, y1z2);
-#undef GH_RFENCE
-    return o;
-}
-
-// The three accumulators of a program (run, wacc, and tmp of the salt detour) live in a per-program slab of global memory,
-// word-major (slab[(slot * NW + word) * 64 + lane]: one 256-byte row per wave instruction), and only the operand of the
-// current step is in registers: with all three held in registers next to the operands of the addition the compiler
-// spilled 2.4 KB per lane -- 848 scratch instructions per step against the 156-234 explicit ones now.
-template <class C> struct ReduceSlab {
-    static constexpr int NW = (int)(sizeof(Proj<C>) / 4);
-    static constexpr size_t WORDS = (size_t)3 * NW * 64;      // per program
-    static __device__ __forceinline__ Proj<C> ld(const uint32_t* slab, int slot, int lane) {
-        Proj<C> v;
-        uint32_t* w = reinterpret_cast<uint32_t*>(&v);
-        const uint32_t* p = slab + (size_t)slot * NW * 64 + lane;
-#pragma unroll
-        for (int k = 0; k < NW; k++) w[k] = p[(size_t)k * 64];
-        return v;
-    }
-    static __device__ __forceinline__ void st(uint32_t* slab, int slot, int lane, const Proj<C>& v) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(&v);
-        uint32_t* p = slab + (size_t)slot * NW * 64 + lane;
-#pragma unroll
-        for (int k = 0; k < NW; k++) p[(size_t)k * 64] = w[k];
-    }
-};
-template <class C, int WAVES = 2>
-__global__ void __launch_bounds__(256, WAVES)
-msm_wave_reduce_kernel(WaveReduceIn<C> in0, WaveReduceIn<C> in1, WaveReduceIn<C> in2, uint32_t blocks_per_input,
-                       uint32_t n_inputs, uint32_t segs_per_window, int L, const Aff<C>* __restrict__ salts,
-                       Proj<C>* __restrict__ out, uint32_t* __restrict__ slabs) {
-    typedef typename C::F F;
-    typedef ReduceSlab<C> SL;
-    enum { RUN = 0, WACC = 1, TMP = 2 };
-    extern __shared__ uint32_t lds_raw[];
-    const int lane = threadIdx.x & 63;
-    Proj<C>* sh = reinterpret_cast<Proj<C>*>(lds_raw) + 64 * (threadIdx.x >> 6);
-    const uint32_t gb = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // one program per wave
-    if (gb >= n_inputs * blocks_per_input) return;
-    const uint32_t which = gb / blocks_per_input, blk = gb % blocks_per_input;
-    const WaveReduceIn<C> in = which == 0 ? in0 : (which == 1 ? in1 : in2);
-    const uint32_t w = blk / segs_per_window, seg = blk % segs_per_window;
-    const uint32_t item0 = seg * 64u * (uint32_t)L;
-    if ((size_t)w * in.count + item0 >= (size_t)in.valid) {   // segment of padding slots only: all sums are infinity
-        if (in.mode == 2) {
-            const Proj<C> z = proj_zero<C>();
-            st_proj<C>(out + ((size_t)blk * 64 + lane) * 2, z); st_proj<C>(out + ((size_t)blk * 64 + lane) * 2 + 1, z);
-        } else if (lane == 0) {
-            Proj<C>* oz = out + ((size_t)which * blocks_per_input + blk) * 3;
-            const Proj<C> z = proj_zero<C>();
-            st_proj<C>(oz, z); st_proj<C>(oz + 1, z); st_proj<C>(oz + 2, z);
-        }
-        return;
-    }
-    const int NS1 = in.mode == 1 ? L : 2 * L - 1;
-    const int NST = in.mode == 1 ? L + 6 : (in.mode == 2 ? NS1 : NS1 + 18);
-    uint32_t* slab = slabs + (size_t)gb * SL::WORDS;
-    {
-        const Proj<C> z = proj_zero<C>();
-        SL::st(slab, RUN, lane, z); SL::st(slab, WACC, lane, z); SL::st(slab, TMP, lane, z);
-    }
-    int step = 0, det = 0, salt_id = 0;
-    bool mydet = false, mid_done = false;
-    Proj<C>* o = out + ((size_t)which * blocks_per_input + blk) * 3;
-    while (step < NST) {
-        int kind, off = 0, i = 0;
-        if (step < NS1) {
-            if (in.mode == 1) { kind = 0; i = L - 1 - step; }
-            else { kind = (step & 1) ? 1 : 0; i = L - 1 - (step >> 1); }
-        } else if (in.mode == 1) { kind = 4; off = 32 >> (step - NS1); }
-        else if (step < NS1 + 6) { kind = 2; off = 32 >> (step - NS1); }
-        else if (step < NS1 + 12) { kind = 3; off = 1 << (step - NS1 - 6); }
-        else {
-            kind = 4; off = 32 >> (step - NS1 - 12);
-            if (!mid_done) {   // between scan and the last tree: publish runW = S_0, drop lane 0 from the tree
-                if (lane == 0) { st_proj<C>(o, SL::ld(slab, RUN, lane)); SL::st(slab, RUN, lane, proj_zero<C>()); }
-                mid_done = true;
-            }
-        }
-        const bool exch = kind >= 2;
-        if (exch && det == 0) st_proj<C>(sh + lane, SL::ld(slab, kind == 2 ? WACC : RUN, lane));
-        if (exch) GH_WAVE_SYNC();
-        const bool to_wacc = kind == 1 || kind == 2;
-        const int dst = to_wacc ? WACC : RUN;
-        bool active;
-        if (kind == 0) active = item0 + (uint32_t)lane + 64u * (uint32_t)i < in.count;
-        else if (kind == 1) active = true;
-        else active = kind == 3 ? lane + off < 64 : lane < off;
-        if (det > 0) active = mydet;
-        // the step's second operand (re-loadable: it is read again below for the lanes whose sum is one of the operands)
-        auto load_q = [&]() -> Proj<C> {
-            Proj<C> q = proj_zero<C>();
-            if (det == 1 || det == 3) {
-                const Aff<C> sp = ld_aff<C>(salts + salt_id);
-                q.x = sp.x; q.y = det == 3 ? F::neg(sp.y) : sp.y; q.z = F::one();
-            } else if (kind == 0) {
-                const uint32_t k = item0 + (uint32_t)lane + 64u * (uint32_t)i;
-                if (k < in.count) q = ld_proj<C>(in.base + ((size_t)w * in.count + k) * in.stride + in.offset);
-            } else if (kind == 1) {
-                q = SL::ld(slab, RUN, lane);
-            } else {
-                const int partner = lane + off;
-                if (kind == 3 ? partner < 64 : lane < off) q = ld_proj<C>(sh + partner);
-            }
-            return q;
-        };
-        const int src = det >= 2 ? TMP : dst;
-        bool same, pz, qz;
-        Proj<C> r;
-        {
-            const Proj<C> q = load_q();
-            const Proj<C> p = SL::ld(slab, src, lane);
-            r = proj_add_raw<C>(p, q, same, pz, qz);
-        }
-        if (__any((pz || qz) && active)) {   // p + infinity = p, infinity + q = q: patch those lanes from the operands, read again
-            const Proj<C> q = load_q();
-            const Proj<C> p = SL::ld(slab, src, lane);
-            uint32_t* rw = reinterpret_cast<uint32_t*>(&r);
-            const uint32_t* pw = reinterpret_cast<const uint32_t*>(&p);
-            const uint32_t* qw = reinterpret_cast<const uint32_t*>(&q);
-#pragma unroll
-            for (int k = 0; k < SL::NW; k++) rw[k] = pz ? qw[k] : (qz ? pw[k] : rw[k]);
-        }
-        if (exch) GH_WAVE_SYNC();
-        same = same && active;
-        if (det == 0) {
-            const bool any_same = __any(same) != 0;
-            if (active && !same) SL::st(slab, dst, lane, r);
-            if (any_same) {
-                mydet = same;
-                if (same) {   // salt with x != p.x / p.z  (rare path: out-of-line product)
-                    const Proj<C> p = SL::ld(slab, src, lane);
-                    Aff<C> s0 = ld_aff<C>(salts);
-                    salt_id = C::FC::eq(C::FC::mul(s0.x, p.z), p.x) ? 1 : 0;
-                }
-                det = 1;
-            } else {
-                step++;
-            }
-        } else {
-            if (mydet) SL::st(slab, det < 3 ? TMP : dst, lane, r);
-            if (det == 3) { det = 0; mydet = false; step++; } else det++;
-        }
-    }
-    if (in.mode == 2) {
-        st_proj<C>(out + ((size_t)blk * 64 + lane) * 2, SL::ld(slab, RUN, lane));
-        st_proj<C>(out + ((size_t)blk * 64 + lane) * 2 + 1, SL::ld(slab, WACC, lane));
-    } else if (lane == 0) {
-        if (in.mode == 1) {
-            st_proj<C>(o, SL::ld(slab, RUN, lane));
-        } else {
-            st_proj<C>(o + 1, SL::ld(slab, WACC, lane));
-            st_proj<C>(o + 2, SL::ld(slab, RUN, lane));
-        }
-    }
-}
-
-// ---------------------------------------------------------------- 5b. bucket reduction for G2: lane groups
-// The same wave program over the split field policies of section 4b: a point of the program lives in a
-// lane pair (Fq2) or triple (Fq3), one coefficient per lane, so a wave carries TPW = 32 / 16 items (Fq3:
-// lanes 48..63 idle) and every addition runs on inlined Fp products in registers -- the tower version of
-// msm_wave_reduce_kernel has to call out-of-line products whose operands travel through scratch.
-// Item index = g + TPW * i (g = group, i = slot of the group), so  sum index * x = TPW * A + Bv.
-struct P3 { Fp x, y, z; };
-template <class FS> __device__ __forceinline__ P3 p3_zero() { return P3{fp_zero(), FS::one(), fp_zero()}; }
-template <class FS> __device__ __forceinline__ P3 p3_add_sel(const P3& p, const P3& q, bool& same) {
-    const bool pz = FS::is_zero(p.z), qz = FS::is_zero(q.z);
-    Fp y1z2 = FS::mul(p.y, q.z);
-    Fp x1z2 = FS::mul(p.x, q.z);
-    Fp z1z2 = FS::mul(p.z, q.z);
-    Fp u = FS::sub(FS::mul(p.z, q.y), y1z2);
-    Fp v = FS::sub(FS::mul(p.z, q.x), x1z2);
-    same = !pz && !qz && FS::is_zero(u) && FS::is_zero(v);
-    Fp uu = FS::sqr(u);
-    Fp vv = FS::sqr(v);
-    Fp vvv = FS::mul(v, vv);
-    Fp r = FS::mul(vv, x1z2);
-    Fp a = FS::sub(FS::sub(FS::mul(uu, z1z2), vvv), FS::dbl(r));
-    P3 o;
-    o.x = FS::mul(v, a);
-    o.y = FS::sub(FS::mul(FS::sub(r, a), u), FS::mul(vvv, y1z2));
-    o.z = FS::mul(vvv, z1z2);
-#pragma unroll
-    for (int k = 0; k < NL; k++) {
-        o.x.l[k] = pz ? q.x.l[k] : (qz ? p.x.l[k] : o.x.l[k]);
-        o.y.l[k] = pz ? q.y.l[k] : (qz ? p.y.l[k] : o.y.l[k]);
-        o.z.l[k] = pz ? q.z.l[k] : (qz ? p.z.l[k] : o.z.l[k]);
-    }
-    return o;
-}
-
-// without the final operand selects (see proj_add_raw): the caller patches lanes with an infinite operand
-template <class FS> __device__ __forceinline__ P3 p3_add_raw(const P3& p, const P3& q, bool& same, bool& pz, bool& qz) {
-    pz = FS::is_zero(p.z); qz = FS::is_zero(q.z);
-    Fp y1z2 = FS::mul(p.y, q.z);
-    Fp u = FS::sub(FS::mul(p.z, q.y), y1z2);
-    Fp x1z2 = FS::mul(p.x, q.z);
-    Fp v = FS::sub(FS::mul(p.z, q.x), x1z2);
-    Fp z1z2 = FS::mul(p.z, q.z);
-    same = !pz && !qz && FS::is_zero(u) && FS::is_zero(v);
-    Fp vv = FS::sqr(v);
-    Fp r = FS::mul(vv, x1z2);
-    Fp vvv = FS::mul(v, vv);
-    Fp uu = FS::sqr(u);
-    Fp a = FS::sub(FS::sub(FS::mul(uu, z1z2), vvv), FS::dbl(r));
-    P3 o;
-    o.x = FS::mul(v, a);
-    o.z = FS::mul(vvv, z1z2);
-    o.y = FS::sub(FS::mul(FS::sub(r, a), u), FS::mul(vvv, y1z2));
-    return o;
-}
-struct P3Slab {   // run / wacc / tmp of a program, word-major per lane (see ReduceSlab)
-    static constexpr int NW = 3 * NL;
-    static constexpr size_t WORDS = (size_t)3 * NW * 64;
-    static __device__ __forceinline__ P3 ld(const uint32_t* slab, int slot, int lane) {
-        P3 v;
-        uint32_t* w = reinterpret_cast<uint32_t*>(&v);
-        const uint32_t* p = slab + (size_t)slot * NW * 64 + lane;
-#pragma unroll
-        for (int k = 0; k < NW; k++) w[k] = p[(size_t)k * 64];
-        return v;
-    }
-    static __device__ __forceinline__ void st(uint32_t* slab, int slot, int lane, const P3& v) {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(&v);
-        uint32_t* p = slab + (size_t)slot * NW * 64 + lane;
-#pragma unroll
-        for (int k = 0; k < NW; k++) p[(size_t)k * 64] = w[k];
-    }
-};
-
-// (A 256-register build of this kernel -- two waves per SIMD, so that inside a batch a program would share its SIMD with a wave of
-// the next MSM's round kernels -- was measured at the end of round 4: 2.4 KB of scratch per lane on Fq3, batches 2-3 % SLOWER.)
-template <class C, class FS, int LANES, int TPW>
-__global__ void __launch_bounds__(64, 1)
-msm_wave_reduce_split_kernel(WaveReduceIn<C> in0, WaveReduceIn<C> in1, WaveReduceIn<C> in2, uint32_t blocks_per_input,
-                             uint32_t n_inputs, uint32_t segs_per_window, int L, const Aff<C>* __restrict__ salts,
-                             Proj<C>* __restrict__ out, uint32_t* __restrict__ slabs) {
-    typedef P3Slab SL;
-    enum { RUN = 0, WACC = 1, TMP = 2 };
-    constexpr int LT = TPW == 32 ? 5 : (TPW == 16 ? 4 : 6);
-    static_assert((1 << LT) == TPW && TPW * LANES <= 64, "groups per wave");
-    extern __shared__ uint32_t lds_raw[];
-    P3* sh = reinterpret_cast<P3*>(lds_raw);
-    const int lane = threadIdx.x & 63;
-    const bool live = lane < TPW * LANES;
-    const int g = live ? lane / LANES : TPW, comp = lane % LANES;
-    const uint32_t gb = blockIdx.x;
-    if (gb >= n_inputs * blocks_per_input) return;
-    const uint32_t which = gb / blocks_per_input, blk = gb % blocks_per_input;
-    const WaveReduceIn<C> in = which == 0 ? in0 : (which == 1 ? in1 : in2);
-    const uint32_t w = blk / segs_per_window, seg = blk % segs_per_window;
-    const uint32_t item0 = seg * (uint32_t)TPW * (uint32_t)L;
-    // coefficient `comp` of coordinate e of a projective / affine point in memory
-    auto ld_c = [&](const void* pt, int e) { return ld_fp(reinterpret_cast<const Fp*>(pt) + LANES * e + comp); };
-    auto st_c = [&](void* pt, int e, const Fp& v) { st_fp(reinterpret_cast<Fp*>(pt) + LANES * e + comp, v); };
-    auto st_p3 = [&](Proj<C>* pt, const P3& v) { st_c(pt, 0, v.x); st_c(pt, 1, v.y); st_c(pt, 2, v.z); };
-    Proj<C>* o = out + ((size_t)which * blocks_per_input + blk) * 3;
-    if ((size_t)w * in.count + item0 >= (size_t)in.valid) {   // segment of padding slots only
-        if (g == 0) { const P3 z = p3_zero<FS>(); st_p3(o, z); st_p3(o + 1, z); st_p3(o + 2, z); }
-        return;
-    }
-    const int NS1 = in.mode == 1 ? L : 2 * L - 1;
-    const int NST = in.mode == 1 ? L + LT : NS1 + 3 * LT;
-    uint32_t* slab = slabs + (size_t)gb * SL::WORDS;
-    {
-        const P3 z = p3_zero<FS>();
-        SL::st(slab, RUN, lane, z); SL::st(slab, WACC, lane, z); SL::st(slab, TMP, lane, z);
-    }
-    int step = 0, det = 0, salt_id = 0;
-    bool mydet = false, mid_done = false;
-    auto sh_store = [&](const P3& v) {
-        uint2* d = reinterpret_cast<uint2*>(sh + lane);
-        const uint2* sv = reinterpret_cast<const uint2*>(&v);
-#pragma unroll
-        for (int k = 0; k < (int)(sizeof(P3) / 8); k++) d[k] = sv[k];
-    };
-    auto sh_load = [&](int src_lane) {
-        P3 v;
-        const uint2* sv = reinterpret_cast<const uint2*>(sh + src_lane);
-        uint2* d = reinterpret_cast<uint2*>(&v);
-#pragma unroll
-        for (int k = 0; k < (int)(sizeof(P3) / 8); k++) d[k] = sv[k];
-        return v;
-    };
-    while (step < NST) {
-        int kind, off = 0, i = 0;
-        if (step < NS1) {
-            if (in.mode == 1) { kind = 0; i = L - 1 - step; }
-            else { kind = (step & 1) ? 1 : 0; i = L - 1 - (step >> 1); }
-        } else if (in.mode == 1) { kind = 4; off = (TPW / 2) >> (step - NS1); }
-        else if (step < NS1 + LT) { kind = 2; off = (TPW / 2) >> (step - NS1); }
-        else if (step < NS1 + 2 * LT) { kind = 3; off = 1 << (step - NS1 - LT); }
-        else {
-            kind = 4; off = (TPW / 2) >> (step - NS1 - 2 * LT);
-            if (!mid_done) {   // between scan and the last tree: publish runW = S_0, drop group 0 from the tree
-                if (g == 0) { st_p3(o, SL::ld(slab, RUN, lane)); SL::st(slab, RUN, lane, p3_zero<FS>()); }
-                mid_done = true;
-            }
-        }
-        const bool exch = kind >= 2;
-        if (exch && det == 0) sh_store(SL::ld(slab, kind == 2 ? WACC : RUN, lane));
-        if (exch) GH_WAVE_SYNC();
-        const bool to_wacc = kind == 1 || kind == 2;
-        const int dst = to_wacc ? WACC : RUN;
-        bool active;
-        if (kind == 0) active = live && item0 + (uint32_t)g + (uint32_t)TPW * (uint32_t)i < in.count;
-        else if (kind == 1) active = live;
-        else active = live && (kind == 3 ? g + off < TPW : g < off);
-        if (det > 0) active = mydet;
-        auto load_q = [&]() -> P3 {   // the step's second operand; read again below for the lanes whose sum is one of the operands
-            P3 q = p3_zero<FS>();
-            if (det == 1 || det == 3) {
-                q.x = ld_c(salts + salt_id, 0);
-                q.y = ld_c(salts + salt_id, 1);
-                if (det == 3) q.y = FS::neg(q.y);
-                q.z = FS::one();
-            } else if (kind == 0) {
-                const uint32_t k = item0 + (uint32_t)g + (uint32_t)TPW * (uint32_t)i;
-                if (live && k < in.count) {
-                    const Proj<C>* pt = in.base + ((size_t)w * in.count + k) * in.stride + in.offset;
-                    q.x = ld_c(pt, 0); q.y = ld_c(pt, 1); q.z = ld_c(pt, 2);
-                }
-            } else if (kind == 1) {
-                q = SL::ld(slab, RUN, lane);
-            } else {
-                if (live && (kind == 3 ? g + off < TPW : g < off)) q = sh_load(lane + off * LANES);
-            }
-            return q;
-        };
-        const int src = det >= 2 ? TMP : dst;
-        bool same, pz, qz;
-        P3 r;
-        {
-            const P3 q = load_q();
-            const P3 p = SL::ld(slab, src, lane);
-            r = p3_add_raw<FS>(p, q, same, pz, qz);
-        }
-        if (__any((pz || qz) && active)) {   // p + infinity = p, infinity + q = q
-            const P3 q = load_q();
-            const P3 p = SL::ld(slab, src, lane);
-            uint32_t* rw = reinterpret_cast<uint32_t*>(&r);
-            const uint32_t* pw = reinterpret_cast<const uint32_t*>(&p);
-            const uint32_t* qw = reinterpret_cast<const uint32_t*>(&q);
-#pragma unroll
-            for (int k = 0; k < SL::NW; k++) rw[k] = pz ? qw[k] : (qz ? pw[k] : rw[k]);
-        }
-        if (exch) GH_WAVE_SYNC();
-        same = same && active;
-        if (det == 0) {
-            const bool any_same = __any(same) != 0;
-            if (active && !same) SL::st(slab, dst, lane, r);
-            if (any_same) {
-                mydet = same;
-                // salt with x != p.x / p.z (all lanes run the product: the group shuffles need their partners)
-                const P3 p = SL::ld(slab, src, lane);
-                const bool s0_hits = FS::eq(FS::mul(ld_c(salts, 0), p.z), p.x);
-                if (same) salt_id = s0_hits ? 1 : 0;
-                det = 1;
-            } else {
-                step++;
-            }
-        } else {
-            if (mydet) SL::st(slab, det < 3 ? TMP : dst, lane, r);
-            if (det == 3) { det = 0; mydet = false; step++; } else det++;
-        }
-    }
-    if (g == 0) {
-        if (in.mode == 1) {
-            st_p3(o, SL::ld(slab, RUN, lane));
-        } else {
-            st_p3(o + 1, SL::ld(slab, WACC, lane));
-            st_p3(o + 2, SL::ld(slab, RUN, lane));
-        }
-    }
-}
-
-
 }  // namespace gh
+
+// ---------------------------------------------------------------- 5. bucket reduction: msm_reduce_kernels.h
+#include "msm_reduce_kernels.h"

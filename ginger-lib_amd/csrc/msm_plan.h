@@ -184,7 +184,7 @@ inline MsmPlan plan_msm(size_t n, int deg, bool has_table, int pre_c, int pre_G,
     // (measured at 2^20 + 1 buckets: L1 = 16 -> 6.2 ms, 8 -> 6.8, 4 -> 8.2, 32 -> 7.9 -- the one bucket beyond the power of two
     //  added a 1025th / 2049th / 4097th wave program, which ran beside or after another one on its SIMD and doubled the
     //  launch; with the merged set at exactly 2^(c-1) slots level 1 takes 4.3 ms (L1 = 16), level 2 1.1 ms).
-    p.tpw = deg == 2 ? 32 : (deg == 3 ? 16 : 64);   // lane pairs / lane triples (48 lanes busy) on G2 (msm_kernels.h 5b)
+    p.tpw = deg == 2 ? 32 : (deg == 3 ? 16 : 64);   // lane pairs / lane triples (48 lanes busy) on G2 (msm_reduce_kernels.h)
     p.sw = p.tpw == 64 ? 6 : (p.tpw == 32 ? 5 : 4);
     auto programs = [&](int l1) { return (size_t)p.RW * ((p.Q + (uint32_t)p.tpw * l1 - 1) / ((uint32_t)p.tpw * l1)); };
     p.L1 = MSM_REDUCE_L;
@@ -195,7 +195,7 @@ inline MsmPlan plan_msm(size_t n, int deg, bool has_table, int pre_c, int pre_G,
     if (p.L1 == MSM_REDUCE_L && programs(p.L1) > 1024) p.L1 = 2 * MSM_REDUCE_L;
     if (k.reduce_l >= 4 && k.reduce_l <= 128 && (k.reduce_l & (k.reduce_l - 1)) == 0) p.L1 = k.reduce_l;
     // Lean reduction (G1, inside a batch): level 1 stops after its serial part and hands every LANE's two sums to level 2
-    // (msm_kernels.h, mode 2) -- 2 L1 - 1 steps per segment instead of 2 L1 + 17, a third fewer wave instructions for
+    // (msm_reduce_kernels.h, mode 2) -- 2 L1 - 1 steps per segment instead of 2 L1 + 17, a third fewer wave instructions for
     // the reduction, which inside a batch cost the accumulation beside it 3.2 of its 23.4 ms per MSM at 2^20 (measured by
     // leaving the reduction out).  The chain is longer (level 2 then folds 64 x as many items per window: 6.5 + 8.3 ms inside
     // a batch at 2^20 against 8.8 + 3.0), so an MSM that runs alone and the last one of a batch keep the segment form, and

@@ -1,4 +1,5 @@
-// Host build (g++) of the MSM's HIP-free host code -- the plans of msm_plan.h and the window folds of msm_fold.h -- exported for
+// Host build (g++) of the MSM's HIP-free code -- the plans of msm_plan.h, the window folds of msm_fold.h and the accumulation's
+// task decode, msm_schedule.h -- exported for
 // ctypes so that tests/test_msm_host.py can check them without a GPU.  Test infrastructure only; not part of the product library.
 // Points go in and out as ABI Montgomery limbs (3 x DEG x 12 u64 per projective point), which is the host curve's own form.
 // The plans are made with the knobs' defaults (MsmKnobs{}), whatever the environment holds.
@@ -6,6 +7,7 @@
 #include <vector>
 #include "../../ginger-lib_amd/csrc/msm_plan.h"
 #include "../../ginger-lib_amd/csrc/msm_fold.h"
+#include "../../ginger-lib_amd/csrc/msm_schedule.h"
 
 using namespace gh;
 using namespace gh_rt;
@@ -74,5 +76,26 @@ void t_tree_piece(uint32_t n_piece, uint32_t o0, uint32_t tpw, uint32_t max_wave
     const PieceGeom g = tp.piece(n_piece, o0);
     const RoundSplit s = tp.split(n_piece, aff_asm != 0);
     out[0] = g.t0; out[1] = g.waves; out[2] = g.aw; out[3] = g.Bq; out[4] = s.nA; out[5] = s.split;
+}
+
+// the accumulation's task decode (msm_schedule.h) with numbers for pointers: bucket g is g, the sum of chunk t is 2^32 + t.
+// out[4]: beg, cnt, index, 1 for a chunk sum
+void t_acc_task(int affin, uint32_t t, const uint32_t* starts, const uint32_t* counts, const uint32_t* order, const uint32_t* chunk_start,
+                uint32_t n_heavy, uint32_t n_chunks, uint32_t chunk, uint32_t g_first, uint32_t list_base, uint32_t* out) {
+    const uint64_t buckets = 0, partials = 1ull << 32;
+    const AccTaskSpan<uint64_t> k =
+        affin ? acc_task_decode<true>(t, starts, counts, order, buckets, chunk_start, n_heavy, n_chunks, chunk, partials, g_first, list_base)
+              : acc_task_decode<false>(t, starts, counts, order, buckets, chunk_start, n_heavy, n_chunks, chunk, partials, g_first, list_base);
+    out[0] = k.beg; out[1] = k.cnt; out[2] = (uint32_t)k.dst; out[3] = (uint32_t)(k.dst >> 32);
+}
+
+// the reduction's step schedule (msm_schedule.h).  out[6]: serial steps, total steps; kind, off, i, publish of `step`
+void t_wave_step(uint32_t mode, int L, int LT, int step, int* out) {
+    const WaveStep s = wave_step(mode, L, LT, step);
+    out[0] = wave_serial_steps(mode, L); out[1] = wave_total_steps(mode, L, LT);
+    out[2] = s.kind; out[3] = s.off; out[4] = s.i; out[5] = s.publish ? 1 : 0;
+}
+int t_wave_step_active(int kind, int off, int g, int tpw, int has_item) {
+    return wave_step_active(WaveStep{kind, off, 0, false}, g, tpw, has_item != 0) ? 1 : 0;
 }
 }

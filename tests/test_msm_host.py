@@ -1,6 +1,8 @@
 """The MSM's HIP-free host code compiled with g++ (tests/host_shim/msm_host_shim.cpp): the window folds of
-ginger-lib_amd/csrc/msm_fold.h against their definition, computed from Python integers, and the plans of msm_plan.h (one MSM,
-its bucket sort, its affine rounds) against the invariants the launch sequence relies on and the values the project documents.
+ginger-lib_amd/csrc/msm_fold.h against their definition, computed from Python integers, the plans of msm_plan.h (one MSM,
+its bucket sort, its affine rounds) against the invariants the launch sequence relies on and the values the project documents,
+the bucket accumulation's task decode (msm_schedule.h) against an enumeration, and the bucket reduction's step schedule
+(msm_schedule.h) run over integers against the sums the wave program promises.
 Nothing here is a recording of the code's own output."""
 import ctypes
 import os
@@ -20,7 +22,7 @@ CURVE_NAMES = ("mnt4753_g1", "mnt4753_g2", "mnt6753_g1", "mnt6753_g2")
 @pytest.fixture(scope="module")
 def shim():
     src = os.path.join(ROOT, "tests", "host_shim", "msm_host_shim.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("msm_plan.h", "msm_fold.h", "host_math.h", "ec29.h", "fp29.h")]
+    deps = [src] + [os.path.join(CSRC, f) for f in ("msm_plan.h", "msm_fold.h", "msm_schedule.h", "host_math.h", "ec29.h", "fp29.h")]
     os.makedirs(os.path.dirname(SHIM), exist_ok=True)
     if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
@@ -31,6 +33,10 @@ def shim():
     lib.t_plan_sort.argtypes = [U64, U64, U64, ctypes.POINTER(ctypes.c_uint32)]
     lib.t_tree_plan.argtypes = [ctypes.c_uint32, U64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, U64, U64, ctypes.POINTER(U64)]
     lib.t_tree_piece.argtypes = [ctypes.c_uint32] * 5 + [ctypes.c_int, ctypes.POINTER(U64)]
+    lib.t_acc_task.argtypes = ([ctypes.c_int, ctypes.c_uint32] + [ctypes.POINTER(ctypes.c_uint32)] * 4 + [ctypes.c_uint32] * 5
+                               + [ctypes.POINTER(ctypes.c_uint32)])
+    lib.t_wave_step.argtypes = [ctypes.c_uint32] + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)]
+    lib.t_wave_step_active.argtypes = [ctypes.c_int] * 5
     return lib
 
 
@@ -367,3 +373,102 @@ def test_tree_plan(shim):
                         assert aff_asm and 0 < nA < n_piece and n_piece > 31 * asm_max * tpw
                     else:
                         assert not aff_asm or nA >= n_piece or n_piece <= 31 * asm_max * tpw
+
+
+# ------------------------------------------------------------------------------------------------ the accumulation's task decode
+
+def u32_array(values):
+    return (ctypes.c_uint32 * max(len(values), 1))(*values)
+
+
+def test_acc_task_decode_against_enumeration(shim):
+    out = (ctypes.c_uint32 * 4)()
+    # (bucket sizes, heavy threshold = chunk): no heavy bucket; one whose last chunk is short; exact multiples of the chunk; all heavy
+    cases = [([3, 0, 7, 1, 5], 8), ([3, 21, 0, 2], 8), ([16, 1, 8, 24, 0, 9], 8), ([5, 4, 1], 4), ([9, 10, 17], 4), ([1], 1), ([2], 1)]
+    for sizes_, chunk in cases:
+        total = len(sizes_)
+        starts = [sum(sizes_[:g]) for g in range(total)]
+        order = sorted(range(total), key=lambda g: (-min(sizes_[g], chunk + 1), g))     # by descending size bin: the heavy ones first
+        n_heavy = sum(1 for c in sizes_ if c > chunk)
+        chunk_start, expect = [], []
+        for h in range(n_heavy):                                                        # the enumeration: chunk after chunk
+            g = order[h]
+            chunk_start.append(len(expect))
+            for b in range(0, sizes_[g], chunk):
+                expect.append((starts[g] + b, min(chunk, sizes_[g] - b), len(expect), 1))
+        chunk_start.append(len(expect))
+        n_chunks = len(expect)
+        expect += [(starts[g], sizes_[g], g, 0) for g in order[n_heavy:]]
+        assert len(expect) == n_chunks + total - n_heavy
+        a = [u32_array(v) for v in (starts, sizes_, order, chunk_start)]
+        for t, want in enumerate(expect):
+            shim.t_acc_task(0, t, a[0], a[1], a[2], a[3], n_heavy, n_chunks, chunk, 0, 0, out)
+            assert tuple(int(v) for v in out) == want, (sizes_, chunk, t)
+        assert sorted(e for b, c, _, _ in expect for e in range(b, b + c)) == list(range(sum(sizes_)))   # every list entry once
+        # the affine rounds' output list: task t is bucket g_first + t, its records start at starts[g] - list_base
+        for g_first in range(total):
+            for t in range(total - g_first):
+                g = g_first + t
+                shim.t_acc_task(1, t, a[0], a[1], a[2], a[3], n_heavy, n_chunks, chunk, g_first, starts[g_first], out)
+                assert tuple(int(v) for v in out) == (starts[g] - starts[g_first], sizes_[g], g, 0)
+
+
+# ------------------------------------------------------------------------------------------------ the reduction's step schedule
+
+def run_wave_schedule(shim, mode, L, TPW, items):
+    """The decoded schedule over integers for points: every group has run and wacc, the exchange is a list, group g owns the
+    segment's items g, g + TPW, ...; items past the end are padding.  Returns (run, wacc, the published runW)."""
+    LT = TPW.bit_length() - 1
+    out = (ctypes.c_int * 6)()
+    shim.t_wave_step(mode, L, LT, 0, out)
+    ns1, nst = out[0], out[1]
+    assert ns1 == (L if mode == 1 else 2 * L - 1) and nst == ns1 + (LT if mode == 1 else (0 if mode == 2 else 3 * LT))
+    run, wacc, published = [0] * TPW, [0] * TPW, []
+    for step in range(nst):
+        shim.t_wave_step(mode, L, LT, step, out)
+        kind, off, i, publish = out[2], out[3], out[4], out[5]
+        if publish:                                  # runW leaves the program, group 0 leaves the last tree
+            published.append(run[0])
+            run[0] = 0
+        exch = list(wacc if kind == 2 else run)      # what the groups put into the exchange before the step
+        for g in range(TPW):
+            k = g + TPW * i
+            if not shim.t_wave_step_active(kind, off, g, TPW, int(k < len(items))):
+                continue
+            if kind == 0:
+                run[g] += items[k]
+            elif kind == 1:
+                wacc[g] += run[g]
+            elif kind == 2:
+                wacc[g] += exch[g + off]
+            else:
+                assert kind in (3, 4)
+                run[g] += exch[g + off]
+    assert len(published) == (1 if mode == 0 else 0)
+    return run, wacc, (published[0] if published else None)
+
+
+def test_wave_schedule_over_integers(shim):
+    rng = pyref.Rng(0x5C4ED)
+    for TPW in (64, 32, 16):
+        for mode in ((0, 1, 2) if TPW == 64 else (0, 1)):
+            for L in (1, 2, 4, 16, 32):
+                seg_items = TPW * L
+                # a window of 2 full segments, a ragged third and a fourth of padding only; and one shorter than a segment
+                for count, n_segs in ((2 * seg_items + max(1, seg_items // 3), 4), (max(1, seg_items - 1), 2), (1, 1)):
+                    window = [1 + int(rng.next_u64() % 1000) for _ in range(count)]
+                    for seg in range(n_segs):
+                        items = window[seg * seg_items:(seg + 1) * seg_items]
+                        run, wacc, runW = run_wave_schedule(shim, mode, L, TPW, items)
+                        total = sum(items)
+                        weighted = sum(k * x for k, x in enumerate(items))
+                        where = (TPW, mode, L, count, seg)
+                        if mode == 0:       # out[0] = runW, out[1] = A = wacc of group 0, out[2] = Bv = run of group 0
+                            assert runW == total, where
+                            assert TPW * wacc[0] + run[0] == weighted, where
+                        elif mode == 1:
+                            assert run[0] == total, where
+                        else:               # every lane's (sum_i x, sum_i i x) over its own items g + TPW i
+                            for g in range(TPW):
+                                own = items[g::TPW]
+                                assert (run[g], wacc[g]) == (sum(own), sum(i * x for i, x in enumerate(own))), where + (g,)
