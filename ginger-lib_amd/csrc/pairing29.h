@@ -23,8 +23,8 @@
 //   products) costs 69 per doubling and 66 per addition, so 376 x 69 + 123 x 66 = 34.1 K products per variable pair against
 //   376 x 38 + 123 x 45 = 19.8 K for the Jacobian form, which is the one built.  (Squarings counted as products.)
 //
-// An MNT6 engine would add an Fq6 tower over F3 with the same interface as Fq4 below and its own step functions; the kernels
-// of pairing.hip are templates over the engine.
+// The MNT6-753 engine (pairing29_mnt6.h) is an Fq6 tower over F3 with the interface of Mnt4Pairing below and its own step
+// functions; the kernels of pairing_impl.h are templates over the engine and take every width from it.
 #pragma once
 #include "ec29.h"
 #include "pairing_constants_gen.h"
@@ -42,6 +42,7 @@ struct Mnt4Pairing {
     static constexpr int ATE_DIGITS = GH_MNT4_ATE_DIGITS;
     static constexpr int W0_DIGITS = GH_MNT4_W0_DIGITS;
     static constexpr int TABLE_STEPS = GH_MNT4_ATE_DIGITS + GH_MNT4_ATE_NONZERO;    // 499 entries of 3 Fq2
+    static constexpr int BDEG = 2;                   // Fq coefficients of a tower coordinate (of G2, of half a GT)
 
     static GH_HD Fp mul13(const Fp& a) { return fp_mul_small<P4, 13>(a); }
     // times X, the generator of Fq2: the non-residue of Fq4 over Fq2 and the twist       (fp4.rs:64-68)
@@ -75,12 +76,16 @@ struct Mnt4Pairing {
         const Fp2T s = B::mul(B::add(a.c0, a.c1), Fp2T{fp_add<P4>(b0, b1.c0), b1.c1});
         return Fq4T{B::add(v0, mul_x(v1)), B::sub(B::sub(s, v0), v1)};
     }
+    // times a prepared step's line (c0: [b0, 0], c1: b1), the name every engine has
+    static GH_HD Fq4T mul_by_line(const Fq4T& a, const Fp& b0, const Fp2T& b1) { return mul_by_023(a, b0, b1); }
     // zero gives zero                                                                   (fp4.rs:201-217)
     static GH_HD Fq4T inverse(const Fq4T& a) {
         const Fp2T t = inv2(B::sub(B::sqr(a.c0), mul_x(B::sqr(a.c1))));
         return Fq4T{B::mul(a.c0, t), B::neg(B::mul(a.c1, t))};
     }
     static GH_HD Fq4T unitary_inverse(const Fq4T& a) { return Fq4T{a.c0, B::neg(a.c1)}; }         // fp4.rs:70-72
+    // what follows the Miller loop: the trace is negative                               (mod.rs:219-221)
+    static GH_HD Fq4T miller_end(const Fq4T& f) { return unitary_inverse(f); }
     static GH_HD Fp frob4_coeff(int k) {
         switch (k & 3) {
             case 1: { const uint32_t c[NL] = GH_MNT4_FROB4_C1_1_I29; return fp_const<P4>(c); }
@@ -108,6 +113,8 @@ struct Mnt4Pairing {
     // ------------------------------------------------------------------------------------------------ Miller steps
     // what a pair brings to every step: x_P, 13 y_P
     struct G1Pre { Fp px, py13; };
+    static GH_HD G1Pre g1_pre(const Fp& x, const Fp& y) { return G1Pre{x, mul13(y)}; }
+    static GH_HD const Fp& line_c0(const G1Pre& P) { return P.py13; }
     // the running point of a variable Q: Jacobian, t = z^2
     struct G2Run { Fp2T x, y, z, t; };
     // one entry of a prepared table: the reference's G2PreparedCoefficients, r_y being -+y_Q in an addition step
@@ -202,8 +209,8 @@ struct Mnt4Pairing {
 template <class E> GH_HD_NOINLINE typename E::GT gt_mul_call(const typename E::GT& a, const typename E::GT& b) { return E::mul(a, b); }
 template <class E> GH_HD_NOINLINE typename E::GT gt_sqr_call(const typename E::GT& a) { return E::sqr(a); }
 template <class E> GH_HD_NOINLINE typename E::GT gt_cyclo_sqr_call(const typename E::GT& a) { return E::cyclotomic_square(a); }
-template <class E> GH_HD_NOINLINE typename E::GT gt_mul_by_023_call(const typename E::GT& a, const Fp& b0, const typename E::B::T& b1) {
-    return E::mul_by_023(a, b0, b1);
+template <class E> GH_HD_NOINLINE typename E::GT gt_mul_by_line_call(const typename E::GT& a, const Fp& b0, const typename E::B::T& b1) {
+    return E::mul_by_line(a, b0, b1);
 }
 template <class E> GH_HD_NOINLINE typename E::GT dbl_step_call(typename E::G2Run& R, const typename E::G1Pre& P) { return E::dbl_step(R, P); }
 template <class E>
@@ -236,21 +243,25 @@ GH_HD Fq4T Mnt4Pairing::final_exponentiation(const Fq4T& f, const int8_t* w0naf)
 
 // final_exp(prod_j miller(P_j, Q_j)) over k variable pairs of one row, on the host or in one thread: what the kernels of
 // pairing.hip compute with the running points in a slab.  skip[j]: the pair contributes one (a point at infinity).
-GH_HD Fq4T mnt4_miller_variable(const Mnt4Pairing::G1Pre* P, const Fp2T* qx, const Fp2T* qy, const bool* skip, int k, const int8_t* naf) {
-    typedef Mnt4Pairing E;
-    E::G2Run R[3];
-    for (int j = 0; j < k; j++) R[j] = E::G2Run{qx[j], qy[j], E::B::one(), E::B::one()};
-    Fq4T f = E::one();
+template <class E>
+GH_HD typename E::GT miller_variable(const typename E::G1Pre* P, const typename E::B::T* qx, const typename E::B::T* qy, const bool* skip, int k,
+                                     const int8_t* naf) {
+    typename E::G2Run R[3];
+    for (int j = 0; j < k; j++) R[j] = typename E::G2Run{qx[j], qy[j], E::B::one(), E::B::one()};
+    typename E::GT f = E::one();
     for (int i = 0; i < E::ATE_DIGITS; i++) {
-        f = gt_sqr_call<Mnt4Pairing>(f);
+        f = gt_sqr_call<E>(f);
         for (int j = 0; j < k; j++)
-            if (!skip[j]) f = gt_mul_call<Mnt4Pairing>(f, dbl_step_call<Mnt4Pairing>(R[j], P[j]));
+            if (!skip[j]) f = gt_mul_call<E>(f, dbl_step_call<E>(R[j], P[j]));
         const int n = naf[i];
         if (n != 0)
             for (int j = 0; j < k; j++)
-                if (!skip[j]) f = gt_mul_call<Mnt4Pairing>(f, add_step_call<Mnt4Pairing>(R[j], qx[j], n > 0 ? qy[j] : E::B::neg(qy[j]), P[j]));
+                if (!skip[j]) f = gt_mul_call<E>(f, add_step_call<E>(R[j], qx[j], n > 0 ? qy[j] : E::B::neg(qy[j]), P[j]));
     }
-    return E::unitary_inverse(f);                                // the trace is negative (mod.rs:219-221)
+    return E::miller_end(f);
+}
+GH_HD Fq4T mnt4_miller_variable(const Mnt4Pairing::G1Pre* P, const Fp2T* qx, const Fp2T* qy, const bool* skip, int k, const int8_t* naf) {
+    return miller_variable<Mnt4Pairing>(P, qx, qy, skip, k, naf);
 }
 
 }  // namespace gh

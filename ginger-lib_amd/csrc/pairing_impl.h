@@ -1,0 +1,599 @@
+// pairing_impl.h -- batched reduced ate pairings, one row per lane, and the Groth16 verifier built on them
+// (proof-systems/src/groth16/verifier.rs), as templates over the engine policy E: Mnt4Pairing (pairing29.h, instantiated by
+// pairing.hip) or Mnt6Pairing (pairing29_mnt6.h, pairing_mnt6753.hip).  Each unit ends with GH_DEFINE_PAIRING_OPS, and the C ABI
+// of pairing.hip reaches an engine through its PairingOps, as the MSM reaches a curve through msm_impl.h.  DESIGN.md section 14.
+//
+// Everything that counts Fq words comes from the engine: D = E::BDEG is the degree of the tower's base over Fq (2 or 3), a G2
+// coordinate and half a GT element are D Fq, a G2 point and a GT element 24 D ABI words.  A row's Miller value f (2 D Fq)
+// lives in registers; the running G2 points of its variable pairs (Jacobian X, Y, Z, T: 4 D Fq each) and what a pair brings to
+// every step (x_Q, y_Q, x_P and the line's Fq factor: 13 y_P on MNT4, y_P on MNT6) live in a per-row global slab, limb-major
+// with the row index fastest like the slabs of vb_kernels.h, so a wave reads 256 consecutive bytes per limb.  A prepared Q
+// (the verifying key's -gamma and -delta) is a table of 499 line coefficients in global memory that every lane reads at the
+// same step.
+//   pair_setup_kernel    ABI points -> the row's slab, the pair's skip flag (a point at infinity, or a row of status 2)
+//   miller_kernel        KV variable + KP prepared pairs with one shared f: f is squared once per digit and multiplied by every
+//                        pair's line.  The loop over the 376 signed digits is wave-uniform; only skipped pairs diverge.
+//   final_exp_kernel     the reference's split final exponentiation, out in ABI form
+//   g2_prepare_kernel    the two tables of a verifying key, one thread each, once per handle
+#pragma once
+#include <memory>
+#include "vb_kernels.h"
+#include "pairing29_mnt6.h"
+#include "../../include/ginger_hip_pairing.h"
+
+struct gh_groth16_vk {
+    static constexpr uint32_t MAGIC = 0x67684756u;
+    uint32_t magic = MAGIC;
+    int engine = GH_PAIRING_MNT4753;               // GH_PAIRING_*: which PairingOps verify with this key
+    size_t n_abc = 0;
+    std::vector<uint64_t> gt;                      // alpha_g1_beta_g2: 24 D words
+    std::vector<uint64_t> g2_neg;                  // -gamma_g2, -delta_g2: 2 x 24 D words
+    std::vector<uint64_t> abc;                     // gamma_abc_g1: n_abc x 24 words
+    gh_rt::DevMem d_tab;                           // 2 x TABLE_STEPS line coefficients, built on first use
+    gh_rt::DevMem d_gt;                            // alpha_g1_beta_g2 on the device
+    gh_rt::DevMem d_abc;                           // gamma_abc_g1 on the device (the variable-base rows)
+    std::vector<gh_rt::FixedTable*> tables;        // the fixed-base table of gamma_abc_g1[j + 1], for the first n_tables inputs
+    bool built = false;
+    ~gh_groth16_vk() {
+        for (auto* t : tables) gh_rt::fixed_table_destroy(t);
+        magic = 0;
+    }
+};
+
+// what the C ABI calls for a key's or a call's engine: the bodies of the entry points after the lock and the engine check
+namespace gh_rt {
+struct PairingOps {
+    int (*product)(const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy, const uint8_t* g2_inf, size_t n, size_t k, uint64_t* out_gt);
+    int (*vk_create)(int engine, const uint64_t* alpha_g1_beta_g2, const uint64_t* gamma_g2_xy, const uint64_t* delta_g2_xy,
+                     const uint64_t* gamma_abc_g1_xy, size_t n_abc, gh_groth16_vk** out);
+    int (*verify)(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                  const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status);
+    int (*last_timing)(float* phase_ms, int max_phases, float* total_ms);
+};
+const PairingOps* pairing_ops_mnt4753();
+const PairingOps* pairing_ops_mnt6753();
+}  // namespace gh_rt
+
+namespace {
+
+Timing g_tm{6};                                    // upload, g_ic, Miller loop, final exponentiation, compare, download
+
+// the signed digits of an engine's loop count and of its w0, most significant first
+__constant__ int8_t c_ate_naf4[GH_MNT4_ATE_DIGITS] = GH_MNT4_ATE_NAF;
+__constant__ int8_t c_w0_naf4[GH_MNT4_W0_DIGITS] = GH_MNT4_W0_NAF;
+__constant__ int8_t c_ate_naf6[GH_MNT6_ATE_DIGITS] = GH_MNT6_ATE_NAF;
+__constant__ int8_t c_w0_naf6[GH_MNT6_W0_DIGITS] = GH_MNT6_W0_NAF;
+template <class E> __device__ __forceinline__ const int8_t* ate_naf();
+template <class E> __device__ __forceinline__ const int8_t* w0_naf();
+template <> __device__ __forceinline__ const int8_t* ate_naf<Mnt4Pairing>() { return c_ate_naf4; }
+template <> __device__ __forceinline__ const int8_t* w0_naf<Mnt4Pairing>() { return c_w0_naf4; }
+template <> __device__ __forceinline__ const int8_t* ate_naf<Mnt6Pairing>() { return c_ate_naf6; }
+template <> __device__ __forceinline__ const int8_t* w0_naf<Mnt6Pairing>() { return c_w0_naf6; }
+
+// the host's side of an engine: PS the scalar field of the public inputs, the G1 curve of the g_ic tables, the name under which
+// launch_pairs reports its chunks (GH_TEST_SLAB_ROWS), one in Montgomery form, and the twist's b
+template <class E> struct EngineHost;
+template <> struct EngineHost<Mnt4Pairing> {
+    typedef P6 PS;
+    static constexpr gh_curve_t g1_curve = GH_MNT4753_G1;
+    static constexpr const char* pairs_loop = "launch_pairs";
+    static const uint64_t* one() { static const uint64_t v[12] = GH_P4_R_64; return v; }
+    static Fp2T g2_b() {
+        static const uint64_t b2w[12] = GH_MNT4753_G2_B1_M_64;
+        return Fp2T{fp_zero(), fp_from_abi<P4>((const uint32_t*)b2w)};
+    }
+};
+template <> struct EngineHost<Mnt6Pairing> {
+    typedef P4 PS;
+    static constexpr gh_curve_t g1_curve = GH_MNT6753_G1;
+    static constexpr const char* pairs_loop = "launch_pairs_mnt6";
+    static const uint64_t* one() { static const uint64_t v[12] = GH_P6_R_64; return v; }
+    static Fp3T g2_b() {
+        static const uint64_t b0[12] = GH_MNT6753_G2_B0_M_64, b1[12] = GH_MNT6753_G2_B1_M_64, b2[12] = GH_MNT6753_G2_B2_M_64;
+        return Fp3T{fp_from_abi<P6>((const uint32_t*)b0), fp_from_abi<P6>((const uint32_t*)b1), fp_from_abi<P6>((const uint32_t*)b2)};
+    }
+};
+
+// slab slots of a row (one Fq each): variable pair j at var_slots j, prepared pair j at var_slots KV + PRE_SLOTS j.  A variable
+// pair: X, Y, Z, T, x_Q, y_Q (D each) at 0, D .. 5 D, then x_P and the line's Fq factor: 14 slots on MNT4, 20 on MNT6
+template <class E> constexpr int var_slots() { return 6 * E::BDEG + 2; }
+constexpr int PRE_SLOTS = 2;                       // x_P, the line's Fq factor
+// ABI words (u32) of a G2 point and of a GT element; a G2 coordinate and half a GT element are half of it
+template <class E> constexpr int tower_words() { return 48 * E::BDEG; }
+constexpr int MAX_PAIRS = 3;
+constexpr size_t PAIR_SLAB_BYTES = (size_t)1 << 30;
+// fixed-base tables of gamma_abc_g1: window 8 (95 rows of 256 affine points, 5 MB per input) for as many inputs as fit this
+// bound; the inputs beyond it go through the variable-base kernels of vb_kernels.h
+constexpr int ABC_WINDOW = 8;
+constexpr size_t ABC_TABLE_BYTES = (size_t)1 << 30;
+constexpr size_t ABC_TABLE_EACH = (size_t)((753 + ABC_WINDOW - 1) / ABC_WINDOW) * ((size_t)1 << ABC_WINDOW) * sizeof(Aff<Mnt4G1>);
+static_assert(sizeof(Aff<Mnt6G1>) == sizeof(Aff<Mnt4G1>), "one table size for both G1");
+
+// where the pairs of a launch come from: ABI words, row i of pair j at base[j] + i * stride[j]
+struct PairIn {
+    const uint32_t* g1[MAX_PAIRS];
+    const uint8_t* g1_inf[MAX_PAIRS];
+    size_t g1_stride[MAX_PAIRS], g1_inf_stride[MAX_PAIRS];
+    const uint32_t* g2[MAX_PAIRS];                 // the variable pairs only
+    const uint8_t* g2_inf[MAX_PAIRS];
+    size_t g2_stride[MAX_PAIRS], g2_inf_stride[MAX_PAIRS];
+};
+
+// a tower coordinate in D consecutive slots
+template <class T> __device__ __forceinline__ T ld_t(const RowSlab& s, int slot);
+template <> __device__ __forceinline__ Fp2T ld_t<Fp2T>(const RowSlab& s, int slot) { return Fp2T{s.ld(slot), s.ld(slot + 1)}; }
+template <> __device__ __forceinline__ Fp3T ld_t<Fp3T>(const RowSlab& s, int slot) { return Fp3T{s.ld(slot), s.ld(slot + 1), s.ld(slot + 2)}; }
+__device__ __forceinline__ void st_t(const RowSlab& s, int slot, const Fp2T& v) {
+    s.st(slot, v.c0);
+    s.st(slot + 1, v.c1);
+}
+__device__ __forceinline__ void st_t(const RowSlab& s, int slot, const Fp3T& v) {
+    s.st(slot, v.c0);
+    s.st(slot + 1, v.c1);
+    s.st(slot + 2, v.c2);
+}
+
+template <class E, int KV, int KP>
+__global__ void __launch_bounds__(BLOCK)
+pair_setup_kernel(PairIn in, const uint8_t* __restrict__ status, size_t row0, size_t cnt, uint32_t* __restrict__ slab,
+                  uint8_t* __restrict__ skip) {
+    typedef typename E::PF PF;
+    typedef typename E::B B;
+    constexpr int D = E::BDEG, VS = var_slots<E>();
+    const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= cnt) return;
+    const size_t i = row0 + t;
+    const RowSlab s{slab + t, cnt};
+    const bool dead = status && status[i] == 2;
+#pragma unroll
+    for (int j = 0; j < KV + KP; j++) {
+        bool sk = dead || in.g1_inf[j][i * in.g1_inf_stride[j]] != 0;
+        if (j < KV) sk = sk || in.g2_inf[j][i * in.g2_inf_stride[j]] != 0;
+        skip[i * (KV + KP) + j] = sk;
+        if (sk) continue;
+        const uint32_t* p = in.g1[j] + i * in.g1_stride[j];
+        const int base = j < KV ? VS * j + 6 * D : VS * KV + PRE_SLOTS * (j - KV);
+        const typename E::G1Pre pre = E::g1_pre(fp_from_abi<PF>(p), fp_from_abi<PF>(p + 24));
+        s.st(base, pre.px);
+        s.st(base + 1, E::line_c0(pre));
+        if (j < KV) {
+            const uint32_t* q = in.g2[j] + i * in.g2_stride[j];
+            const typename B::T qx = B::from_abi(q), qy = B::from_abi(q + tower_words<E>() / 2);
+            st_t(s, VS * j, qx);
+            st_t(s, VS * j + D, qy);
+            st_t(s, VS * j + 2 * D, B::one());
+            st_t(s, VS * j + 3 * D, B::one());
+            st_t(s, VS * j + 4 * D, qx);
+            st_t(s, VS * j + 5 * D, qy);
+        }
+    }
+}
+
+template <class E, int KV, int KP>
+__global__ void __launch_bounds__(BLOCK)
+miller_kernel(uint32_t* __restrict__ slab, const uint8_t* __restrict__ skip, const typename E::Coeff* __restrict__ tab, size_t row0,
+              size_t cnt, typename E::GT* __restrict__ out) {
+    typedef typename E::B B;
+    typedef typename B::T BT;
+    typedef typename E::GT GT;
+    constexpr int D = E::BDEG, VS = var_slots<E>();
+    const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= cnt) return;
+    const size_t i = row0 + t;
+    const RowSlab s{slab + t, cnt};
+    bool sk[KV + KP];
+#pragma unroll
+    for (int j = 0; j < KV + KP; j++) sk[j] = skip[i * (KV + KP) + j] != 0;
+    GT f = E::one();
+    // one step of every pair: add == 0 a doubling, +-1 an addition of +-Q; idx the step's entry of the prepared tables
+    auto step = [&](int add, int idx) {
+#pragma unroll
+        for (int j = 0; j < KV; j++) {
+            if (sk[j]) continue;
+            const int b = VS * j;
+            typename E::G2Run R{ld_t<BT>(s, b), ld_t<BT>(s, b + D), ld_t<BT>(s, b + 2 * D), ld_t<BT>(s, b + 3 * D)};
+            const typename E::G1Pre P{s.ld(b + 6 * D), s.ld(b + 6 * D + 1)};
+            GT l;
+            if (add == 0) {
+                l = dbl_step_call<E>(R, P);
+            } else {
+                BT qy = ld_t<BT>(s, b + 5 * D);
+                if (add < 0) qy = B::neg(qy);
+                l = add_step_call<E>(R, ld_t<BT>(s, b + 4 * D), qy, P);
+            }
+            st_t(s, b, R.x);
+            st_t(s, b + D, R.y);
+            st_t(s, b + 2 * D, R.z);
+            st_t(s, b + 3 * D, R.t);
+            f = gt_mul_call<E>(f, l);
+        }
+#pragma unroll
+        for (int j = 0; j < KP; j++) {
+            if (sk[KV + j]) continue;
+            const int b = VS * KV + PRE_SLOTS * j;
+            const typename E::G1Pre P{s.ld(b), s.ld(b + 1)};
+            const typename E::Coeff c = ld_words(tab + (size_t)j * E::TABLE_STEPS + idx);
+            f = gt_mul_by_line_call<E>(f, E::line_c0(P), E::prepared_line(c, P));
+        }
+    };
+    int idx = 0;
+#pragma unroll 1
+    for (int d = 0; d < E::ATE_DIGITS; d++) {
+        f = gt_sqr_call<E>(f);
+        const int n = ate_naf<E>()[d];
+#pragma unroll 1
+        for (int h = 0; h < (n != 0 ? 2 : 1); h++) step(h ? n : 0, idx++);      // one inlined body for both kinds of step
+    }
+    st_words(out + i, E::miller_end(f));           // MNT4: the trace is negative (mnt4/mod.rs:219-221)
+}
+
+template <class E>
+__global__ void __launch_bounds__(BLOCK) final_exp_kernel(const typename E::GT* __restrict__ f, size_t n, uint32_t* __restrict__ out) {
+    typedef typename E::B B;
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const typename E::GT r = E::final_exponentiation(ld_words(f + i), w0_naf<E>());
+    uint32_t* o = out + i * tower_words<E>();
+    B::to_abi(o, r.c0);
+    B::to_abi(o + tower_words<E>() / 2, r.c1);
+}
+
+// the two tables of a verifying key: thread t prepares the point at g2 + 48 D t (ABI words)
+template <class E>
+__global__ void __launch_bounds__(BLOCK) g2_prepare_kernel(const uint32_t* __restrict__ g2, int count, typename E::Coeff* __restrict__ tab) {
+    typedef typename E::B B;
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= count) return;
+    constexpr int W = tower_words<E>();
+    E::prepare_g2(B::from_abi(g2 + W * t), B::from_abi(g2 + W * t + W / 2), ate_naf<E>(), tab + (size_t)t * E::TABLE_STEPS);
+}
+
+// status 2 for a row with a proof point off its curve (the point at infinity is on it), else 0
+template <class E>
+__global__ void __launch_bounds__(BLOCK)
+proof_check_kernel(const uint32_t* __restrict__ a, const uint8_t* __restrict__ a_inf, const uint32_t* __restrict__ b,
+                   const uint8_t* __restrict__ b_inf, const uint32_t* __restrict__ c, const uint8_t* __restrict__ c_inf, size_t n, Fp b1,
+                   typename E::B::T b2, uint8_t* __restrict__ status) {
+    typedef typename E::PF PF;
+    typedef typename E::B B;
+    typedef typename E::G1::FC F;
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    auto g1_ok = [&](const uint32_t* xy) {
+        const Fp x = fp_from_abi<PF>(xy), y = fp_from_abi<PF>(xy + 24);
+        return F::eq(F::sqr(y), F::add(F::add(F::mul(F::sqr(x), x), E::G1::mul_by_a(x)), b1));
+    };
+    bool ok = a_inf[i] || g1_ok(a + i * 48);
+    ok = ok && (c_inf[i] || g1_ok(c + i * 48));
+    if (ok && !b_inf[i]) {
+        constexpr int W = tower_words<E>();
+        const typename B::T x = B::from_abi(b + i * W), y = B::from_abi(b + i * W + W / 2);
+        ok = B::eq(B::sqr(y), B::add(B::add(B::mul(B::sqr(x), x), E::G2::mul_by_a(x)), b2));
+    }
+    status[i] = ok ? 0 : 2;
+}
+
+// 1 if the row's value (W u64 words) is the key's alpha_g1_beta_g2, 0 if not; rows of status 2 keep it
+template <int W>
+__global__ void __launch_bounds__(256) gt_compare_kernel(const uint64_t* __restrict__ val, const uint64_t* __restrict__ gt, size_t n,
+                                                         uint8_t* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (status[i] == 2) return;
+    bool eq = true;
+    for (int w = 0; w < W; w++) eq &= val[i * W + w] == gt[w];
+    status[i] = eq;
+}
+
+// ---- g_ic
+// public inputs (scalar-field Montgomery, row-major) -> canonical integers, input-major: out[j][i]
+template <class PS>
+__global__ void __launch_bounds__(256) inputs_to_int_kernel(const uint32_t* __restrict__ in, size_t n, size_t n_inputs, uint32_t* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * n_inputs) return;
+    const size_t i = t / n_inputs, j = t % n_inputs;
+    fp_to_int<PS>(out + (j * n + i) * 24, fp_from_abi<PS>(in + t * 24));
+}
+template <class C> __global__ void __launch_bounds__(256) fill_proj_kernel(Proj<C>* __restrict__ acc, size_t n, const uint32_t* __restrict__ xy) {
+    typedef typename C::PF PF;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    st_words(acc + i, Proj<C>{fp_from_abi<PF>(xy), fp_from_abi<PF>(xy + 24), C::FC::one()});
+}
+template <class C> __global__ void __launch_bounds__(BLOCK) proj_acc_kernel(Proj<C>* __restrict__ acc, const Proj<C>* __restrict__ b, size_t n) {
+    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    st_words(acc + i, proj_add_call<C>(ld_words(acc + i), ld_words(b + i)));
+}
+__global__ void __launch_bounds__(256) bcast_xy_kernel(const uint32_t* __restrict__ xy, size_t n, uint32_t* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * 48) return;
+    out[t] = xy[t % 48];
+}
+
+// ---------------------------------------------------------------------------------------------------- host side
+// setup, Miller loop and final exponentiation of n rows on g.stream: d_val[i] = the row's value in ABI form (24 D u64).  tab: the
+// KP prepared tables.  The slab is cut into chunks below PAIR_SLAB_BYTES.
+template <class E, int KV, int KP>
+int launch_pairs(const PairIn& in, const uint8_t* d_status, const typename E::Coeff* tab, size_t n, uint64_t* d_val, Phases* ph) {
+    constexpr size_t row_bytes = (size_t)(var_slots<E>() * KV + PRE_SLOTS * KP) * NL * 4;
+    const size_t chunk = slab_chunk_rows(EngineHost<E>::pairs_loop, PAIR_SLAB_BYTES, row_bytes, n);
+    uint32_t* slab;
+    uint8_t* d_skip;
+    typename E::GT* d_f;
+    int rc = gh_rt::pool_get("vb_pair_slab", chunk * row_bytes, (void**)&slab);
+    if (!rc) rc = dbuf("vb_pair_skip", n * (KV + KP), &d_skip);
+    if (!rc) rc = dbuf("vb_pair_f", n, &d_f);
+    if (rc) return rc;
+    for (size_t r0 = 0; r0 < n; r0 += chunk) {
+        const size_t cnt = std::min(chunk, n - r0);
+        GH_LAUNCH((pair_setup_kernel<E, KV, KP>), dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, g.stream, in, d_status, r0, cnt, slab, d_skip);
+        GH_LAUNCH((miller_kernel<E, KV, KP>), dim3(blocks(cnt, BLOCK)), dim3(BLOCK), 0, g.stream, slab, (const uint8_t*)d_skip, tab, r0, cnt, d_f);
+    }
+    HIPCHK(hipGetLastError());
+    if (ph && (rc = ph->mark())) return rc;
+    GH_LAUNCH((final_exp_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const typename E::GT*)d_f, n, (uint32_t*)d_val);
+    HIPCHK(hipGetLastError());
+    if (ph && (rc = ph->mark())) return rc;
+    return GH_OK;
+}
+
+template <class E>
+int run_product(const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy, const uint8_t* g2_inf, size_t n, size_t k, uint64_t* out_gt) {
+    constexpr size_t TW = tower_words<E>() / 2;    // u64 words of a G2 point and of a GT element
+    const size_t m = n * k;
+    uint64_t *d_g1, *d_g2, *d_val;
+    uint8_t *d_i1, *d_i2;
+    int rc = dbuf("vb_pair_g1", m * 24, &d_g1);
+    if (!rc) rc = dbuf("vb_pair_g2", m * TW, &d_g2);
+    if (!rc) rc = dbuf("vb_pair_i1", m, &d_i1);
+    if (!rc) rc = dbuf("vb_pair_i2", m, &d_i2);
+    if (!rc) rc = dbuf("vb_pair_val", n * TW, &d_val);
+    if (rc) return rc;
+    Phases ph{g_tm};
+    if ((rc = ph.mark())) return rc;
+    if ((rc = up(d_g1, g1_xy, m * 24)) || (rc = up(d_g2, g2_xy, m * TW)) || (rc = up(d_i1, g1_inf, m)) || (rc = up(d_i2, g2_inf, m)) ||
+        (rc = ph.mark()) || (rc = ph.mark()))                                                                    // no g_ic phase
+        return rc;
+    PairIn in{};
+    for (size_t j = 0; j < k; j++) {
+        in.g1[j] = (const uint32_t*)d_g1 + 48 * j;
+        in.g1_inf[j] = d_i1 + j;
+        in.g1_stride[j] = 48 * k;
+        in.g1_inf_stride[j] = k;
+        in.g2[j] = (const uint32_t*)d_g2 + 2 * TW * j;
+        in.g2_inf[j] = d_i2 + j;
+        in.g2_stride[j] = 2 * TW * k;
+        in.g2_inf_stride[j] = k;
+    }
+    switch (k) {
+        case 1: rc = launch_pairs<E, 1, 0>(in, nullptr, nullptr, n, d_val, &ph); break;
+        case 2: rc = launch_pairs<E, 2, 0>(in, nullptr, nullptr, n, d_val, &ph); break;
+        default: rc = launch_pairs<E, 3, 0>(in, nullptr, nullptr, n, d_val, &ph); break;
+    }
+    if (rc || (rc = ph.mark())) return rc;                                                                        // no compare phase
+    HIPCHK(hipMemcpyAsync(out_gt, d_val, n * TW * 8, hipMemcpyDeviceToHost, g.stream));
+    if ((rc = ph.mark())) return rc;
+    HIPCHK(hipStreamSynchronize(g.stream));
+    if ((rc = ph.finish())) return rc;
+    g_tm.ms[1] = g_tm.ms[4] = 0;                                                                                  // phases this call does not have
+    return GH_OK;
+}
+
+// how many of a key's inputs get a fixed-base table (GH_GROTH16_TABLES: a measurement and test knob, read when a key is first used)
+size_t abc_table_count(size_t n_inputs) {
+    const int knob = gh_rt::env_int("GH_GROTH16_TABLES", -1);
+    const size_t fit = ABC_TABLE_BYTES / ABC_TABLE_EACH;
+    return std::min(n_inputs, knob >= 0 ? (size_t)knob : fit);
+}
+
+// the device side of a key: the two prepared tables, alpha_g1_beta_g2, gamma_abc_g1 and its fixed-base tables
+template <class E> int vk_ensure(gh_groth16_vk* h) {
+    if (h->built) return GH_OK;
+    constexpr size_t TB = tower_words<E>() * 4;    // bytes of a G2 point and of a GT element
+    gh_rt::DevMem d_g2, d_tab, d_gt, d_abc;
+    int rc;
+    if ((rc = d_g2.alloc(2 * TB)) || (rc = d_tab.alloc(2 * E::TABLE_STEPS * sizeof(typename E::Coeff))) || (rc = d_gt.alloc(TB)) ||
+        (rc = d_abc.alloc(h->n_abc * 192)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(d_g2.get(), h->g2_neg.data(), 2 * TB, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(d_gt.get(), h->gt.data(), TB, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(d_abc.get(), h->abc.data(), h->n_abc * 192, hipMemcpyHostToDevice, g.stream));
+    GH_LAUNCH((g2_prepare_kernel<E>), dim3(1), dim3(BLOCK), 0, g.stream, d_g2.as<const uint32_t>(), 2, d_tab.as<typename E::Coeff>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(g.stream));
+    const size_t nt = abc_table_count(h->n_abc - 1);
+    while (h->tables.size() < nt) {
+        uint64_t xyz[36];
+        memcpy(xyz, h->abc.data() + 24 * (h->tables.size() + 1), 192);
+        memcpy(xyz + 24, EngineHost<E>::one(), 96);
+        gh_rt::FixedTable* t = nullptr;
+        if ((rc = gh_rt::fixed_table_create(EngineHost<E>::g1_curve, xyz, VB_BITS, ABC_WINDOW, &t))) return rc;   // a later call resumes here
+        h->tables.push_back(t);
+    }
+    h->d_tab = std::move(d_tab);
+    h->d_gt = std::move(d_gt);
+    h->d_abc = std::move(d_abc);
+    h->built = true;
+    return GH_OK;
+}
+
+// d_acc[i] = gamma_abc_g1[0] + sum_j inputs[i][j] gamma_abc_g1[j + 1], then affine in ABI form at d_xy / d_inf
+template <class E> int launch_g_ic(gh_groth16_vk* h, const uint64_t* d_inputs, size_t n, size_t n_inputs, uint64_t* d_xy, uint8_t* d_inf) {
+    typedef typename E::G1 C;
+    Proj<C>*d_acc, *d_tmp;
+    Fp* d_zp;
+    uint32_t* d_k = nullptr;
+    uint64_t* d_base = nullptr;
+    int rc = dbuf("vb_p", n, &d_acc);
+    if (!rc) rc = dbuf("vb_p2", n, &d_tmp);
+    if (!rc) rc = dbuf("vb_zp", n, &d_zp);
+    if (!rc && n_inputs) rc = dbuf("vb_pair_k", n * n_inputs * 24, &d_k);
+    if (!rc && h->tables.size() < n_inputs) rc = dbuf("vb_pk", n * 24, &d_base);
+    if (rc) return rc;
+    const uint32_t* abc = h->d_abc.as<const uint32_t>();
+    GH_LAUNCH((fill_proj_kernel<C>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, d_acc, n, abc);
+    if (n_inputs)
+        GH_LAUNCH((inputs_to_int_kernel<typename EngineHost<E>::PS>), dim3(blocks(n * n_inputs, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_inputs, n, n_inputs, d_k);
+    for (size_t j = 0; j < n_inputs; j++) {
+        const uint32_t* kj = d_k + j * n * 24;
+        if (j < h->tables.size()) {
+            if ((rc = gh_rt::fixed_table_sums(h->tables[j], kj, n, d_tmp))) return rc;
+        } else {
+            GH_LAUNCH(bcast_xy_kernel, dim3(blocks(n * 48, 256)), dim3(256), 0, g.stream, abc + 48 * (j + 1), n, (uint32_t*)d_base);
+            if ((rc = vb_single<C, 4>(d_base, nullptr, 0, &kj, &d_tmp, 1, n))) return rc;
+        }
+        GH_LAUNCH((proj_acc_kernel<C>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, d_acc, (const Proj<C>*)d_tmp, n);
+    }
+    if ((rc = launch_normalize<C>(d_acc, nullptr, n, d_zp, d_xy, 48, 0, d_inf))) return rc;
+    HIPCHK(hipGetLastError());
+    return GH_OK;
+}
+
+template <class E>
+int run_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+               const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
+    constexpr size_t TW = tower_words<E>() / 2;    // u64 words of a G2 point and of a GT element
+    if (int rc = vk_ensure<E>(h)) return rc;
+    uint64_t *d_a, *d_b, *d_c, *d_in = nullptr, *d_gic, *d_val;
+    uint8_t *d_ai, *d_bi, *d_ci, *d_gi, *d_st;
+    int rc = dbuf("vb_pair_g1", n * 24, &d_a);
+    if (!rc) rc = dbuf("vb_pair_g2", n * TW, &d_b);
+    if (!rc) rc = dbuf("vb_pair_c", n * 24, &d_c);
+    if (!rc) rc = dbuf("vb_pair_i1", n, &d_ai);
+    if (!rc) rc = dbuf("vb_pair_i2", n, &d_bi);
+    if (!rc) rc = dbuf("vb_pair_i3", n, &d_ci);
+    if (!rc && n_inputs) rc = dbuf("vb_pair_in", n * n_inputs * 12, &d_in);
+    if (!rc) rc = dbuf("vb_xy", n * 24, &d_gic);
+    if (!rc) rc = dbuf("vb_inf", n, &d_gi);
+    if (!rc) rc = dbuf("vb_pair_val", n * TW, &d_val);
+    if (!rc) rc = dbuf("vb_st", n, &d_st);
+    if (rc) return rc;
+    Phases ph{g_tm};
+    if ((rc = ph.mark())) return rc;
+    if ((rc = up(d_a, a_xy, n * 24)) || (rc = up(d_b, b_xy, n * TW)) || (rc = up(d_c, c_xy, n * 24)) || (rc = up(d_ai, a_inf, n)) ||
+        (rc = up(d_bi, b_inf, n)) || (rc = up(d_ci, c_inf, n)) || (n_inputs && (rc = up(d_in, inputs, n * n_inputs * 12))) || (rc = ph.mark()))
+        return rc;
+    GH_LAUNCH((proof_check_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_a, (const uint8_t*)d_ai,
+              (const uint32_t*)d_b, (const uint8_t*)d_bi, (const uint32_t*)d_c, (const uint8_t*)d_ci, n, curve_b<typename E::G1>(),
+              EngineHost<E>::g2_b(), d_st);
+    if ((rc = launch_g_ic<E>(h, d_in, n, n_inputs, d_gic, d_gi)) || (rc = ph.mark())) return rc;
+    PairIn in{};
+    const uint64_t* g1s[3] = {d_a, d_gic, d_c};
+    const uint8_t* infs[3] = {d_ai, d_gi, d_ci};
+    for (int j = 0; j < 3; j++) {
+        in.g1[j] = (const uint32_t*)g1s[j];
+        in.g1_inf[j] = infs[j];
+        in.g1_stride[j] = 48;
+        in.g1_inf_stride[j] = 1;
+    }
+    in.g2[0] = (const uint32_t*)d_b;
+    in.g2_inf[0] = d_bi;
+    in.g2_stride[0] = 2 * TW;
+    in.g2_inf_stride[0] = 1;
+    if ((rc = launch_pairs<E, 1, 2>(in, d_st, h->d_tab.as<const typename E::Coeff>(), n, d_val, &ph))) return rc;
+    GH_LAUNCH((gt_compare_kernel<(int)TW>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)d_val, h->d_gt.as<const uint64_t>(), n, d_st);
+    HIPCHK(hipGetLastError());
+    if ((rc = ph.mark())) return rc;
+    HIPCHK(hipMemcpyAsync(out_status, d_st, n, hipMemcpyDeviceToHost, g.stream));
+    if ((rc = ph.mark())) return rc;
+    HIPCHK(hipStreamSynchronize(g.stream));
+    return ph.finish();
+}
+
+// ---- host checks of a key's points (the same GH_HD arithmetic, on the host)
+template <class E> bool g1_on_curve(const uint64_t* xy) {
+    typedef typename E::G1 C;
+    typedef typename C::FC F;
+    const Fp x = fp_from_abi<typename E::PF>((const uint32_t*)xy), y = fp_from_abi<typename E::PF>((const uint32_t*)(xy + 12));
+    return F::eq(F::sqr(y), F::add(F::add(F::mul(F::sqr(x), x), C::mul_by_a(x)), curve_b<C>()));
+}
+template <class E> bool g2_on_curve(const uint64_t* xy) {
+    typedef typename E::B B;
+    constexpr int H = tower_words<E>() / 4;        // u64 words of a coordinate
+    const typename B::T x = B::from_abi((const uint32_t*)xy), y = B::from_abi((const uint32_t*)(xy + H));
+    return B::eq(B::sqr(y), B::add(B::add(B::mul(B::sqr(x), x), E::G2::mul_by_a(x)), EngineHost<E>::g2_b()));
+}
+template <class E> void g2_negate(uint64_t* out, const uint64_t* xy) {
+    typedef typename E::B B;
+    constexpr int H = tower_words<E>() / 4;
+    memcpy(out, xy, H * 8);
+    B::to_abi((uint32_t*)(out + H), B::neg(B::from_abi((const uint32_t*)(xy + H))));
+}
+
+// ---- the bodies of the entry points for one engine, under the caller's lock
+template <class E>
+int api_product(const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy, const uint8_t* g2_inf, size_t n, size_t k, uint64_t* out_gt) {
+    typedef typename E::PF PF;
+    if (k < 1 || k > MAX_PAIRS) { g_err = "the number of pairs per row must be 1, 2 or 3"; return GH_E_BAD_ARG; }
+    if (n && (!g1_xy || !g1_inf || !g2_xy || !g2_inf || !out_gt)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    size_t b;
+    if (mul_overflows(n, 4096, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (!all_below<PF>(g1_xy, 2 * n * k) || !all_below<PF>(g2_xy, 2 * E::BDEG * n * k)) { g_err = "a coordinate is not below the modulus"; return GH_E_BAD_ARG; }
+    if (n == 0) return GH_OK;
+    if (int rc = gh_rt::ensure_init()) return rc;
+    return run_product<E>(g1_xy, g1_inf, g2_xy, g2_inf, n, k, out_gt);
+}
+
+template <class E>
+int api_vk_create(int engine, const uint64_t* alpha_g1_beta_g2, const uint64_t* gamma_g2_xy, const uint64_t* delta_g2_xy,
+                  const uint64_t* gamma_abc_g1_xy, size_t n_abc, gh_groth16_vk** out) {
+    typedef typename E::PF PF;
+    constexpr size_t TW = tower_words<E>() / 2, TC = 2 * E::BDEG;       // u64 words / Fq coefficients of a G2 point and of a GT element
+    if (!alpha_g1_beta_g2 || !gamma_g2_xy || !delta_g2_xy || !gamma_abc_g1_xy) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    size_t b;
+    if (n_abc == 0 || mul_overflows(n_abc, 4096, &b)) { g_err = "gamma_abc_g1 must hold at least one point"; return GH_E_BAD_ARG; }
+    if (!all_below<PF>(alpha_g1_beta_g2, TC) || !all_below<PF>(gamma_g2_xy, TC) || !all_below<PF>(delta_g2_xy, TC) ||
+        !all_below<PF>(gamma_abc_g1_xy, 2 * n_abc)) {
+        g_err = "a coefficient of the verifying key is not below the modulus";
+        return GH_E_BAD_ARG;
+    }
+    if (!g2_on_curve<E>(gamma_g2_xy) || !g2_on_curve<E>(delta_g2_xy)) { g_err = "gamma_g2 or delta_g2 is not on the curve"; return GH_E_BAD_ARG; }
+    for (size_t j = 0; j < n_abc; j++)
+        if (!g1_on_curve<E>(gamma_abc_g1_xy + 24 * j)) { g_err = "a point of gamma_abc_g1 is not on the curve"; return GH_E_BAD_ARG; }
+    std::unique_ptr<gh_groth16_vk> h(new gh_groth16_vk());
+    h->engine = engine;
+    h->n_abc = n_abc;
+    h->gt.assign(alpha_g1_beta_g2, alpha_g1_beta_g2 + TW);
+    h->g2_neg.resize(2 * TW);
+    g2_negate<E>(h->g2_neg.data(), gamma_g2_xy);
+    g2_negate<E>(h->g2_neg.data() + TW, delta_g2_xy);
+    h->abc.assign(gamma_abc_g1_xy, gamma_abc_g1_xy + 24 * n_abc);
+    *out = h.release();
+    return GH_OK;
+}
+
+template <class E>
+int api_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+               const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
+    typedef typename E::PF PF;
+    if (n_inputs + 1 != h->n_abc) { g_err = "the number of public inputs does not match gamma_abc_g1 (MalformedVerifyingKey)"; return GH_E_BAD_ARG; }
+    if (n && (!a_xy || !a_inf || !b_xy || !b_inf || !c_xy || !c_inf || (n_inputs && !inputs) || !out_status)) {
+        g_err = "null argument";
+        return GH_E_BAD_ARG;
+    }
+    size_t ni = 0, b = 0;
+    if (mul_overflows(n, n_inputs, &ni) || mul_overflows(ni, 96 * 4, &b) || mul_overflows(n, 4096, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (!all_below<PF>(a_xy, 2 * n) || !all_below<PF>(b_xy, 2 * E::BDEG * n) || !all_below<PF>(c_xy, 2 * n)) {
+        g_err = "a proof coordinate is not below the modulus";
+        return GH_E_BAD_ARG;
+    }
+    if (n_inputs && !all_below<typename EngineHost<E>::PS>(inputs, ni)) { g_err = "a public input is not below the modulus"; return GH_E_BAD_ARG; }
+    if (n == 0) return GH_OK;
+    if (int rc = gh_rt::ensure_init()) return rc;
+    return run_verify<E>(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);
+}
+
+int api_last_timing(float* phase_ms, int max_phases, float* total_ms) { return g_tm.copy_out(phase_ms, max_phases, total_ms); }
+
+}  // namespace
+
+// the unit's engine behind gh_rt::NAME()
+#define GH_DEFINE_PAIRING_OPS(ENGINE, NAME)                                                                                 \
+    namespace gh_rt {                                                                                                        \
+    const PairingOps* NAME() {                                                                                               \
+        static const PairingOps ops = {&api_product<ENGINE>, &api_vk_create<ENGINE>, &api_verify<ENGINE>, &api_last_timing}; \
+        return &ops;                                                                                                         \
+    }                                                                                                                        \
+    }
+

@@ -1,5 +1,5 @@
-"""Batched MNT4-753 ate pairings and Groth16 verification on the device (include/ginger_hip_pairing.h), with the reference's
-names (algebra PairingEngine, proof-systems/src/groth16/verifier.rs):
+"""Batched MNT4-753 and MNT6-753 ate pairings and Groth16 verification on the device (include/ginger_hip_pairing.h), with the
+reference's names (algebra PairingEngine, proof-systems/src/groth16/verifier.rs):
 
     pairing_product(g1, g2, k=1) -> (n, 48)              final_exponentiation(prod_j miller_loop(P_ij, Q_ij)): pairing for
                                                          k = 1, product_of_pairings for k = 2, 3
@@ -13,7 +13,11 @@ names (algebra PairingEngine, proof-systems/src/groth16/verifier.rs):
 Field elements are rows of 12 u64 limbs of the Montgomery form x * 2^768 (numpy uint64).  A batch of G1 points is
 (xy: (m, 24), inf: (m,) uint8), of G2 points (xy: (m, 48), inf) with a coordinate as c0 || c1; an Fq4 value is a row of 48
 limbs in the order c0.c0, c0.c1, c1.c0, c1.c1 (Fp4::write).  Public inputs are Montgomery rows of MNT4-753 Fr.  Subgroup
-membership of the points is the caller's business (the reference checks it where a point is read)."""
+membership of the points is the caller's business (the reference checks it where a point is read).
+
+The engine is "mnt4753" unless a call says engine="mnt6753" (pairing="mnt6753" where a Parameters stream is read).  Over
+MNT6-753 a G2 coordinate is c0 || c1 || c2, so a G2 batch is (m, 72), an Fq6 value a row of 72 limbs in the order c0.c0,
+c0.c1, c0.c2, c1.c0, c1.c1, c1.c2 (Fp6::write, 576 bytes), a G2 record 577 bytes, and public inputs are rows of MNT6-753 Fr."""
 import numpy as np
 
 from . import GingerHipError, _check, _ptr    # noqa: F401 (GingerHipError: re-exported)
@@ -26,12 +30,25 @@ _ARGTYPES = {"gh_pairing_product": [ci, vp, vp, vp, vp, sz, sz, vp],
 # every symbol include/ginger_hip_pairing.h declares
 PAIRING_SYMBOLS = list(_ARGTYPES)
 PHASES = ["upload", "g_ic", "miller", "final_exp", "compare", "download"]
-ENGINES = {"mnt4753": 0}
+ENGINES = {"mnt4753": 0, "mnt6753": 2}
 _lib = _handles.binder("pairing", _ARGTYPES)
 
-_FQ = groth16._MODULUS["mnt6753"]        # MNT4-753 Fq = MNT6-753 Fr
-_FR = groth16._MODULUS["mnt4753"]
-_G1_REC, _G2_REC, _GT_BYTES = 193, 385, 384
+_G1_REC = 193
+
+
+class _Widths:
+    """what an engine's layouts are made of: deg Fq coefficients per G2 coordinate and per half of a GT element"""
+
+    def __init__(self, engine):
+        self.deg = groth16._G2_DEG[engine]
+        self.fq = groth16._MODULUS["mnt6753" if engine == "mnt4753" else "mnt4753"]     # the base field is the other curve's Fr
+        self.fr = groth16._MODULUS[engine]
+        self.g2_words = self.gt_words = 24 * self.deg
+        self.g2_rec = 192 * self.deg + 1
+        self.gt_bytes = 192 * self.deg
+
+
+_WIDTHS = {e: _Widths(e) for e in ENGINES}
 
 
 def last_timing():
@@ -50,26 +67,31 @@ def _points(pts, words):
 
 
 def pairing_product(g1, g2, k=1, engine="mnt4753"):
-    """out[i] = final_exponentiation(prod_{j<k} miller_loop(P_ij, Q_ij)) as (n, 48) limbs; pair j of row i is point i * k + j"""
+    """out[i] = final_exponentiation(prod_{j<k} miller_loop(P_ij, Q_ij)) as (n, 48) limbs ((n, 72) over MNT6-753); pair j of
+    row i is point i * k + j"""
+    w = _WIDTHS[engine]
     xy1, inf1 = _points(g1, 24)
-    xy2, inf2 = _points(g2, 48)
+    xy2, inf2 = _points(g2, w.g2_words)
     m = xy1.shape[0]
     if xy2.shape[0] != m or k < 1 or m % k:
         raise ValueError("one G2 point per G1 point, k of each per row")
     n = m // k
-    out = np.zeros((n, 48), dtype=np.uint64)
+    out = np.zeros((n, w.gt_words), dtype=np.uint64)
     _check(_lib().gh_pairing_product(ENGINES[engine], _ptr(xy1), _ptr(inf1), _ptr(xy2), _ptr(inf2), n, k, _ptr(out)))
     return out
 
 
-def gt_to_bytes(gt):
-    """one Fq4 row (48 Montgomery limbs) -> its Fp4::write bytes: 4 x 96 canonical little-endian"""
-    ints = groth16._ints_from_mont_rows(np.asarray(gt, dtype=np.uint64).reshape(4, 12), _FQ)
+def gt_to_bytes(gt, engine="mnt4753"):
+    """one Fq4 row (48 Montgomery limbs) -> its Fp4::write bytes: 4 x 96 canonical little-endian; over MNT6-753 one Fq6 row
+    (72 limbs) -> the 6 x 96 bytes of Fp6::write"""
+    w = _WIDTHS[engine]
+    ints = groth16._ints_from_mont_rows(np.asarray(gt, dtype=np.uint64).reshape(2 * w.deg, 12), w.fq)
     return b"".join(int(v).to_bytes(96, "little") for v in ints)
 
 
-def _wire_rows(data, rec, coeffs):
+def _wire_rows(data, rec, coeffs, engine="mnt4753"):
     """GroupAffine::write records -> (Montgomery rows (n, 12 coeffs), infinity bytes); coefficients must be below the modulus"""
+    fq = _WIDTHS[engine].fq
     n = len(data) // rec
     if n * rec != len(data):
         raise ValueError("truncated point record")
@@ -79,10 +101,10 @@ def _wire_rows(data, rec, coeffs):
         inf[i] = 1 if r[rec - 1] else 0
         for c in range(coeffs):
             v = int.from_bytes(r[96 * c:96 * c + 96], "little")
-            if v >= _FQ:
+            if v >= fq:
                 raise ValueError("a coordinate is not below the modulus")
             vals.append(v)
-    return groth16._mont_rows(vals, _FQ).reshape(n, 12 * coeffs), inf
+    return groth16._mont_rows(vals, fq).reshape(n, 12 * coeffs), inf
 
 
 class PreparedVerifyingKey(_handles.Handle):
@@ -91,11 +113,13 @@ class PreparedVerifyingKey(_handles.Handle):
     _lib, _prefix = staticmethod(_lib), "gh_groth16_vk"
 
     def __init__(self, alpha_g1_beta_g2, gamma_g2, delta_g2, gamma_abc_g1, engine="mnt4753"):
-        gt = _rows(alpha_g1_beta_g2, 48)
-        g, d = _rows(gamma_g2, 48), _rows(delta_g2, 48)
+        w = _WIDTHS[engine]
+        gt = _rows(alpha_g1_beta_g2, w.gt_words)
+        g, d = _rows(gamma_g2, w.g2_words), _rows(delta_g2, w.g2_words)
         abc = _rows(gamma_abc_g1, 24)
         if gt.shape[0] != 1 or g.shape[0] != 1 or d.shape[0] != 1:
             raise ValueError("one alpha_g1_beta_g2, one gamma_g2, one delta_g2")
+        self.engine = engine
         self.num_inputs = abc.shape[0] - 1
         self.alpha_g1_beta_g2 = gt[0].copy()
         self._create(ENGINES[engine], _ptr(gt), _ptr(g), _ptr(d), _ptr(abc), abc.shape[0])
@@ -103,22 +127,24 @@ class PreparedVerifyingKey(_handles.Handle):
     @classmethod
     def from_parameters(cls, blob, pairing="mnt4753"):
         """from a Parameters::write stream (or groth16.parse_parameters' dict of it); points at infinity are refused"""
+        w = _WIDTHS[pairing]
         pk = blob if isinstance(blob, dict) else groth16.parse_parameters(pairing, blob)
-        gt = [int.from_bytes(pk["vk_alpha_g1_beta_g2"][96 * c:96 * c + 96], "little") for c in range(4)]
-        if any(v >= _FQ for v in gt):
-            raise ValueError("alpha_g1_beta_g2 is not an Fq4 element (the filler of groth16.generate_parameters? see parameters_with_pairing)")
-        gt = groth16._mont_rows(gt, _FQ)
-        g, gi = _wire_rows(pk["vk_gamma_g2"], _G2_REC, 4)
-        d, di = _wire_rows(pk["vk_delta_g2"], _G2_REC, 4)
-        abc, ai = _wire_rows(pk["vk_gamma_abc_g1"], _G1_REC, 2)
+        gt = [int.from_bytes(pk["vk_alpha_g1_beta_g2"][96 * c:96 * c + 96], "little") for c in range(2 * w.deg)]
+        if any(v >= w.fq for v in gt):
+            raise ValueError("alpha_g1_beta_g2 is not an element of the target field (the filler of groth16.generate_parameters? "
+                             "see parameters_with_pairing)")
+        gt = groth16._mont_rows(gt, w.fq)
+        g, gi = _wire_rows(pk["vk_gamma_g2"], w.g2_rec, 2 * w.deg, pairing)
+        d, di = _wire_rows(pk["vk_delta_g2"], w.g2_rec, 2 * w.deg, pairing)
+        abc, ai = _wire_rows(pk["vk_gamma_abc_g1"], _G1_REC, 2, pairing)
         if gi.any() or di.any() or ai.any():
             raise ValueError("a point of the verifying key is the point at infinity")
-        return cls(gt.reshape(1, 48), g, d, abc, engine=pairing)
+        return cls(gt.reshape(1, w.gt_words), g, d, abc, engine=pairing)
 
     def verify(self, a, b, c, inputs):
         """a, c: G1 batches, b: a G2 batch, inputs: (n, num_inputs, 12) Montgomery rows of Fr -> status (n,) uint8"""
         axy, ainf = _points(a, 24)
-        bxy, binf = _points(b, 48)
+        bxy, binf = _points(b, _WIDTHS[self.engine].g2_words)
         cxy, cinf = _points(c, 24)
         n = axy.shape[0]
         x = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(n, -1) if n else np.zeros((0, 12 * self.num_inputs), dtype=np.uint64)
@@ -133,27 +159,30 @@ class PreparedVerifyingKey(_handles.Handle):
 def verify_proofs(pvk, proofs, inputs):
     """proofs: Proof::write byte strings (A || B || C records, mod.rs:35-42); inputs: one list of integers per proof.
     -> status (n,) uint8: 1 Ok(true), 0 Ok(false), 2 a proof point is not on its curve"""
+    w = _WIDTHS[pvk.engine]
     n = len(proofs)
     if len(inputs) != n:
         raise ValueError("one list of inputs per proof")
-    rec = _G1_REC + _G2_REC + _G1_REC
+    rec = _G1_REC + w.g2_rec + _G1_REC
     if any(len(p) != rec for p in proofs):
         raise ValueError("a proof is not %d bytes" % rec)
-    a = _wire_rows(b"".join(p[:_G1_REC] for p in proofs), _G1_REC, 2)
-    b = _wire_rows(b"".join(p[_G1_REC:_G1_REC + _G2_REC] for p in proofs), _G2_REC, 4)
-    c = _wire_rows(b"".join(p[_G1_REC + _G2_REC:] for p in proofs), _G1_REC, 2)
+    a = _wire_rows(b"".join(p[:_G1_REC] for p in proofs), _G1_REC, 2, pvk.engine)
+    b = _wire_rows(b"".join(p[_G1_REC:_G1_REC + w.g2_rec] for p in proofs), w.g2_rec, 2 * w.deg, pvk.engine)
+    c = _wire_rows(b"".join(p[_G1_REC + w.g2_rec:] for p in proofs), _G1_REC, 2, pvk.engine)
     if any(len(row) != pvk.num_inputs for row in inputs):
         raise ValueError("the number of public inputs does not match the verifying key")
     flat = [int(v) for row in inputs for v in row]
-    if any(v < 0 or v >= _FR for v in flat):
+    if any(v < 0 or v >= w.fr for v in flat):
         raise ValueError("a public input is not below the modulus")
-    x = groth16._mont_rows(flat, _FR).reshape(n, pvk.num_inputs * 12)
+    x = groth16._mont_rows(flat, w.fr).reshape(n, pvk.num_inputs * 12)
     return pvk.verify(a, b, c, x)
 
 
 def parameters_with_pairing(blob, pairing="mnt4753"):
     """the Parameters::write stream `blob` with vk.alpha_g1_beta_g2 = e(alpha_g1, beta_g2) computed on the device in place of
-    its first 384 bytes (generator.rs:313)"""
+    its first 384 bytes (576 over MNT6-753; generator.rs:313)"""
+    w = _WIDTHS[pairing]
     pk = groth16.parse_parameters(pairing, blob)
-    gt = pairing_product(_wire_rows(pk["alpha_g1"], _G1_REC, 2), _wire_rows(pk["beta_g2"], _G2_REC, 4), engine=pairing)
-    return gt_to_bytes(gt[0]) + bytes(blob[_GT_BYTES:])
+    gt = pairing_product(_wire_rows(pk["alpha_g1"], _G1_REC, 2, pairing), _wire_rows(pk["beta_g2"], w.g2_rec, 2 * w.deg, pairing),
+                         engine=pairing)
+    return gt_to_bytes(gt[0], pairing) + bytes(blob[w.gt_bytes:])

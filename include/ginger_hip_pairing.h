@@ -1,6 +1,8 @@
-/* ginger_hip_pairing.h -- C ABI of the batched MNT4-753 reduced ate pairing and of the Groth16 verifier built on it:
+/* ginger_hip_pairing.h -- C ABI of the batched MNT4-753 and MNT6-753 reduced ate pairings and of the Groth16 verifier built
+ * on them:
  *
- *   algebra/src/curves/models/mnt4/mod.rs:157-269   ate_miller_loop, final_exponentiation
+ *   algebra/src/curves/models/mnt4/mod.rs:157-269   ate_miller_loop, final_exponentiation (engine GH_PAIRING_MNT4753)
+ *   algebra/src/curves/models/mnt6/mod.rs:158-272   the same for MNT6-753                 (engine GH_PAIRING_MNT6753)
  *   PairingEngine::pairing / product_of_pairings    -> gh_pairing_product
  *   proof-systems/src/groth16/verifier.rs:9-16      prepare_verifying_key -> gh_groth16_vk_create
  *   proof-systems/src/groth16/verifier.rs:18-44     verify_proof          -> gh_groth16_verify
@@ -20,6 +22,11 @@
  * G1Prepared / G2Prepared of the point at infinity compute with the coordinates (0, 1) of GroupAffine::zero() instead, a
  * value without meaning; callers of the reference never pair the point at infinity.
  *
+ * Engine GH_PAIRING_MNT6753: the same rules over MNT6-753 Fq.  A G1 point is x || y (24 words); a G2 point is
+ * x.c0 || x.c1 || x.c2 || y.c0 || y.c1 || y.c2 (72 words); an element of the target field Fq6 is c0.c0 || c0.c1 || c0.c2 ||
+ * c1.c0 || c1.c1 || c1.c2 (72 words), the order of Fp6::write; public inputs are in the Montgomery form of MNT6-753 Fr.  Points at
+ * infinity, rows with a point off its curve (status 2), subgroup membership and bad arguments are treated as for MNT4-753.
+ *
  * Subgroup membership is the caller's job.  The reference checks it where a point is read (GroupAffine::read), not in the
  * pairing or the verifier; G1 has cofactor 1, so there it is the curve equation.  For a G2 point on the curve but outside the
  * subgroup of order r the value is unspecified; no input faults, hangs or loops, and the inverse of zero is taken as zero.
@@ -33,7 +40,8 @@
 extern "C" {
 #endif
 
-#define GH_PAIRING_MNT4753 0    /* the one engine (MNT6-753's scalar field has 2-adicity 15: SURVEY F5) */
+#define GH_PAIRING_MNT4753 0
+#define GH_PAIRING_MNT6753 2    /* every other engine id, 1 included, is unknown: GH_E_BAD_ARG */
 
 typedef struct gh_groth16_vk* gh_groth16_vk_t;
 
@@ -43,7 +51,7 @@ int gh_pairing_product(int engine, const uint64_t* g1_xy, const uint8_t* g1_inf,
                        size_t n, size_t k, uint64_t* out_gt);
 /* prepare_verifying_key: keeps alpha_g1_beta_g2, -gamma_g2, -delta_g2 and gamma_abc_g1 (n_abc >= 1 affine points, none at
  * infinity).  Host only: checks that every coefficient is below the modulus and every point on its curve; the two prepared
- * line tables (499 x 3 Fq2 each) and the fixed-base tables of gamma_abc_g1[1..] are built on the device on first use. */
+ * line tables (499 x 3 Fq2 each, Fq3 on MNT6-753) and the fixed-base tables of gamma_abc_g1[1..] are built on the device on first use. */
 int gh_groth16_vk_create(int engine, const uint64_t* alpha_g1_beta_g2, const uint64_t* gamma_g2_xy, const uint64_t* delta_g2_xy,
                          const uint64_t* gamma_abc_g1_xy, size_t n_abc, gh_groth16_vk_t* out);
 int gh_groth16_vk_free(gh_groth16_vk_t h);

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
-"""MNT4-753 pairings and Groth16 verification on the device: pairings/s (gh_pairing_product, k = 1) and verifications/s
+"""MNT4-753 (or, with --engine mnt6753, MNT6-753) pairings and Groth16 verification on the device: pairings/s (gh_pairing_product, k = 1) and verifications/s
 (gh_groth16_verify, two public inputs) at 2^16 and 2^20 rows, warmed, best of 3, timed around the call (which synchronises
 the device before it returns), the phase split of every call, and the Miller and final-exponentiation kernels' products per
-row (counted from the formulas as written in csrc/pairing29.h, squarings as products) over their kernel time as a fraction of
+row (counted from the formulas as written in csrc/pairing29.h and pairing29_mnt6.h, squarings as products) over their kernel time as a fraction of
 the product peak gh_measure_fpmul_peak measures in the same run.
 
 The rows are valid proofs of a key made from random scalars, so that (A, B, C) is known in the exponent:
     a b = alpha beta + (k_0 + sum_j x_j k_j) gamma + c delta;
 4096 distinct rows are tiled to the batch size (no kernel looks at another row).  Every status must be 1.
-Prints one JSON document.  Usage: timeout -k 10 900 python tools/pairing_bench.py [--log2n 16 20] [--reps 3] > out.json"""
+Prints one JSON document.
+Usage: timeout -k 10 900 python tools/pairing_bench.py [--engine mnt4753|mnt6753] [--log2n 16 20] [--reps 3] > out.json"""
 import argparse
 import json
 import os
@@ -26,25 +27,40 @@ from schnorr_bench import INV, MADD, ADD   # noqa: E402
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 DISTINCT = 4096
 N_INPUTS = 2
-# products of the steps of csrc/pairing29.h (its header counts them)
+# products of the steps of csrc/pairing29.h and csrc/pairing29_mnt6.h (their headers count them)
 FQ4_MUL, FQ4_SQR, MUL_023, CYC_SQR = 9, 6, 8, 4
 DBL_STEP, ADD_STEP, PREPARED_LINE = 25 + 4, 28 + 8, 2
+FQ3_MUL, FQ3_SQR = 6, 5
+FQ6_MUL, FQ6_SQR, MUL_2345, CYC_SQR6 = 3 * FQ3_MUL, 2 * FQ3_MUL, 3 + 2 * FQ3_MUL, 2 * FQ3_SQR
+DBL_STEP6, ADD_STEP6, PREPARED_LINE6 = 11 * FQ3_SQR + FQ3_MUL + 6, 7 * FQ3_MUL + 4 * FQ3_SQR + 15, 3
 
 
-def products(consts):
+def products(consts, engine="mnt4753"):
     naf, w0 = consts["ate_naf"], consts["w0_naf"]
     dig, nz = len(naf), sum(1 for d in naf if d)
-    variable = dig * (DBL_STEP + FQ4_MUL) + nz * (ADD_STEP + FQ4_MUL)
-    prepared = (dig + nz) * (PREPARED_LINE + MUL_023)
-    squarings = dig * FQ4_SQR
-    fq4_inv = 4 + (2 + INV + 2 + 2) + 6
-    final_exp = fq4_inv + 2 * FQ4_MUL + 3 * 2 + (len(w0) - 1) * CYC_SQR + (sum(1 for d in w0 if d) - 1) * FQ4_MUL + FQ4_MUL + 4
     g_ic = N_INPUTS * (2 + -(-753 // 8) * MADD + ADD) + (1 + 3 + INV / 16 + 2)
+    if engine == "mnt4753":
+        variable = dig * (DBL_STEP + FQ4_MUL) + nz * (ADD_STEP + FQ4_MUL)
+        prepared = (dig + nz) * (PREPARED_LINE + MUL_023)
+        squarings = dig * FQ4_SQR
+        fq4_inv = 4 + (2 + INV + 2 + 2) + 6
+        final_exp = fq4_inv + 2 * FQ4_MUL + 3 * 2 + (len(w0) - 1) * CYC_SQR + (sum(1 for d in w0 if d) - 1) * FQ4_MUL + FQ4_MUL + 4
+        setup1, setup3, checks = 6, 10, 21
+    else:
+        variable = dig * (DBL_STEP6 + FQ6_MUL) + nz * (ADD_STEP6 + FQ6_MUL)
+        prepared = (dig + nz) * (PREPARED_LINE6 + MUL_2345)
+        squarings = dig * FQ6_SQR
+        # inverse: two Fq3 squarings, the Fq3 inverse (9 + 3 products and one inversion), two Fq3 products
+        fq6_inv = 2 * FQ3_SQR + (9 + INV + 3) + 2 * FQ3_MUL
+        # Frobenius: power 3 costs 3 products (c1 times one coefficient), power 1 costs 4 + 3
+        final_exp = fq6_inv + 3 + FQ6_MUL + 7 + FQ6_MUL + 7 + (len(w0) - 1) * CYC_SQR6 + (sum(1 for d in w0 if d) - 1) * FQ6_MUL + FQ6_MUL + 6
+        # setup: the conversions of x_P, y_P (2) and of x_Q, y_Q (6) per pair; checks: the proof points' curve equations
+        setup1, setup3, checks = 8, 12, 4 + 6 + (2 * FQ3_SQR + FQ3_MUL + 6)
     return {"variable_pair": variable, "prepared_pair": prepared, "shared_squarings": squarings, "final_exponentiation": final_exp,
-            "pairing_miller": variable + squarings + 6, "groth16_miller": variable + 2 * prepared + squarings + 10,
-            "groth16_g_ic_and_checks": g_ic + 21,
-            "pairing_total": variable + squarings + 6 + final_exp,
-            "groth16_total": variable + 2 * prepared + squarings + 10 + final_exp + g_ic + 21}
+            "pairing_miller": variable + squarings + setup1, "groth16_miller": variable + 2 * prepared + squarings + setup3,
+            "groth16_g_ic_and_checks": g_ic + checks,
+            "pairing_total": variable + squarings + setup1 + final_exp,
+            "groth16_total": variable + 2 * prepared + squarings + setup3 + final_exp + g_ic + checks}
 
 
 def _rows(vals):
@@ -55,21 +71,26 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2n", type=int, nargs="*", default=[16, 20])
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--engine", choices=["mnt4753", "mnt6753"], default="mnt4753")
     a = ap.parse_args()
+    eng = a.engine
     from __graft_entry__ import _load_pkg
     gl = _load_pkg()
     gl.init()
     from ginger_lib_amd import groth16, pairing
     peak = gl.measure_fpmul_peak()
     C = json.load(open(os.path.join(GOLDEN, "constants.json")))
-    consts = json.load(open(os.path.join(GOLDEN, "pairing_constants.json")))
-    prod = products(consts)
+    consts = json.load(open(os.path.join(GOLDEN, "pairing_constants.json" if eng == "mnt4753" else "pairing6_constants.json")))
+    prod = products(consts, eng)
     p, r = int(C["fields"]["p4"]["p"], 16), int(C["fields"]["p6"]["p"], 16)
+    if eng == "mnt6753":
+        p, r = r, p                                             # the cycle: MNT6-753's base field is MNT4-753's group order
     mont = lambda vals: groth16._mont_rows(vals, p).reshape(-1)
-    c1, c2 = C["curves"]["mnt4753_g1"], C["curves"]["mnt4753_g2"]
+    c1, c2 = C["curves"][eng + "_g1"], C["curves"][eng + "_g2"]
+    deg = len(c2["gx"])
     g1_xyz = mont([int(c1["gx"][0], 16), int(c1["gy"][0], 16), 1])
-    g2_xyz = mont([int(v, 16) for v in c2["gx"] + c2["gy"]] + [1, 0])
-    t1, t2 = gl.FixedBaseMSM("mnt4753_g1", g1_xyz, 753, 10), gl.FixedBaseMSM("mnt4753_g2", g2_xyz, 753, 8)
+    g2_xyz = mont([int(v, 16) for v in c2["gx"] + c2["gy"]] + [1] + [0] * (deg - 1))
+    t1, t2 = gl.FixedBaseMSM(eng + "_g1", g1_xyz, 753, 10), gl.FixedBaseMSM(eng + "_g2", g2_xyz, 753, 8)
     g1 = lambda ks: t1.multi_scalar_mul_affine(_rows(ks))
     g2 = lambda ks: t2.multi_scalar_mul_affine(_rows(ks))
     rng = random.Random(14)
@@ -83,18 +104,18 @@ def main():
     A, B, Cc = g1(av), g2(bv), g1(cv)
     vk2 = g2([gamma, delta, beta])
     abc = g1(ks + [alpha])
-    gt = pairing.pairing_product((abc[0][-1:], abc[1][-1:]), (vk2[0][2:], vk2[1][2:]))
-    pvk = pairing.PreparedVerifyingKey(gt, vk2[0][0], vk2[0][1], abc[0][:-1])
+    gt = pairing.pairing_product((abc[0][-1:], abc[1][-1:]), (vk2[0][2:], vk2[1][2:]), engine=eng)
+    pvk = pairing.PreparedVerifyingKey(gt, vk2[0][0], vk2[0][1], abc[0][:-1], engine=eng)
     X = groth16._mont_rows([u for xs in xv for u in xs], r).reshape(DISTINCT, N_INPUTS * 12)
     t1.free()
     t2.free()
-    doc = {"device": gl.device_name(), "fpmul_peak_per_s": peak, "public_inputs": N_INPUTS, "products_per_row": prod, "rows": {}}
+    doc = {"device": gl.device_name(), "engine": eng, "fpmul_peak_per_s": peak, "public_inputs": N_INPUTS, "products_per_row": prod, "rows": {}}
     for lg in a.log2n:
         n = 1 << lg
         tile = lambda arr: np.ascontiguousarray(np.tile(arr, (-(-n // DISTINCT),) + (1,) * (arr.ndim - 1))[:n])
         pa, pb, pc, px = [(tile(q[0]), tile(q[1])) for q in (A, B, Cc)] + [tile(X)]
         res = {"rows": n}
-        for name, call, ok, miller in (("pairing", lambda: pairing.pairing_product(pa, pb), None, prod["pairing_miller"]),
+        for name, call, ok, miller in (("pairing", lambda: pairing.pairing_product(pa, pb, engine=eng), None, prod["pairing_miller"]),
                                        ("groth16_verify", lambda: pvk.verify(pa, pb, pc, px), 1, prod["groth16_miller"])):
             out = call()                                        # warm: tables, pooled buffers
             if ok is not None:
