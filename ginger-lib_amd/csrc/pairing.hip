@@ -1,12 +1,14 @@
-// pairing.hip -- the C ABI of include/ginger_hip_pairing.h: the entry points take the lock, find the engine's PairingOps and
-// call them.  The kernels and the host steps are the templates of pairing_impl.h; this unit instantiates them for MNT4-753,
-// pairing_mnt6753.hip for MNT6-753.  DESIGN.md section 14.
+// pairing.hip -- the C ABI of include/ginger_hip_pairing.h and include/ginger_hip_gm17.h: the entry points take the lock, find
+// the engine's PairingOps and call them.  The kernels and the host steps are the templates of pairing_impl.h and
+// gm17_verify_impl.h; this unit instantiates them for MNT4-753, pairing_mnt6753.hip for MNT6-753.  DESIGN.md sections 14, 14b.
 #include "pairing_impl.h"
+#include "gm17_verify_impl.h"
 GH_DEFINE_PAIRING_OPS(gh::Mnt4Pairing, pairing_ops_mnt4753)
 
 namespace {
 
 int g_last_engine = GH_PAIRING_MNT4753;            // whose timing record gh_pairing_last_timing reports
+int g_last_gm17_engine = GH_PAIRING_MNT4753;       // the same for gh_gm17_last_timing
 
 const gh_rt::PairingOps* ops_of_engine(int engine) {
     switch (engine) {
@@ -18,6 +20,10 @@ const gh_rt::PairingOps* ops_of_engine(int engine) {
 }
 int checked_handle(gh_groth16_vk* h) {
     if (!h || h->magic != gh_groth16_vk::MAGIC) { g_err = "not a Groth16 verifying key"; return GH_E_BAD_HANDLE; }
+    return GH_OK;
+}
+int checked_handle(gh_gm17_vk* h) {
+    if (!h || h->magic != gh_gm17_vk::MAGIC) { g_err = "not a GM17 verifying key"; return GH_E_BAD_HANDLE; }
     return GH_OK;
 }
 
@@ -70,6 +76,41 @@ int gh_groth16_verify(gh_groth16_vk_t h, const uint64_t* a_xy, const uint8_t* a_
 int gh_pairing_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     return ops_of_engine(g_last_engine)->last_timing(phase_ms, max_phases, total_ms);
+} catch (...) { return gh_rt::api_exception(); }
+
+// ---- include/ginger_hip_gm17.h
+int gh_gm17_vk_create(int engine, const uint64_t* g_alpha_g1_xy, const uint64_t* h_beta_g2_xy, const uint64_t* g_gamma_g1_xy,
+                      const uint64_t* h_gamma_g2_xy, const uint64_t* h_g2_xy, const uint64_t* query_g1_xy, size_t n_query, gh_gm17_vk_t* out) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    *out = nullptr;
+    const PairingOps* ops = ops_of_engine(engine);
+    if (!ops) return GH_E_BAD_ARG;
+    return ops->gm17_vk_create(engine, g_alpha_g1_xy, h_beta_g2_xy, g_gamma_g1_xy, h_gamma_g2_xy, h_g2_xy, query_g1_xy, n_query, out);
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_gm17_vk_free(gh_gm17_vk_t h) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    if (!h) return GH_OK;
+    if (int rc = checked_handle(h)) return rc;
+    delete h;
+    return GH_OK;
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_gm17_verify(gh_gm17_vk_t h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                   const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    Trim trim_;
+    if (int rc = checked_handle(h)) return rc;
+    const PairingOps* ops = ops_of_engine(h->engine);
+    if (!ops) return GH_E_BAD_HANDLE;
+    g_last_gm17_engine = h->engine;
+    return ops->gm17_verify(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_gm17_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    return ops_of_engine(g_last_gm17_engine)->gm17_last_timing(phase_ms, max_phases, total_ms);
 } catch (...) { return gh_rt::api_exception(); }
 
 }  // extern "C"

@@ -40,6 +40,8 @@ struct gh_groth16_vk {
     }
 };
 
+struct gh_gm17_vk;                                 // gm17_verify_impl.h
+
 // what the C ABI calls for a key's or a call's engine: the bodies of the entry points after the lock and the engine check
 namespace gh_rt {
 struct PairingOps {
@@ -49,6 +51,12 @@ struct PairingOps {
     int (*verify)(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
                   const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status);
     int (*last_timing)(float* phase_ms, int max_phases, float* total_ms);
+    // the GM17 verifier of gm17_verify_impl.h (include/ginger_hip_gm17.h)
+    int (*gm17_vk_create)(int engine, const uint64_t* g_alpha_g1_xy, const uint64_t* h_beta_g2_xy, const uint64_t* g_gamma_g1_xy,
+                          const uint64_t* h_gamma_g2_xy, const uint64_t* h_g2_xy, const uint64_t* query_g1_xy, size_t n_query, gh_gm17_vk** out);
+    int (*gm17_verify)(gh_gm17_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                       const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status);
+    int (*gm17_last_timing)(float* phase_ms, int max_phases, float* total_ms);
 };
 const PairingOps* pairing_ops_mnt4753();
 const PairingOps* pairing_ops_mnt6753();
@@ -387,6 +395,21 @@ size_t abc_table_count(size_t n_inputs) {
     return std::min(n_inputs, knob >= 0 ? (size_t)knob : fit);
 }
 
+// the fixed-base tables of the points after the first of `pts` (n_pts x 24 words, ABI), for as many as abc_table_count allows; a
+// later call resumes where an earlier one failed
+template <class E> int ensure_abc_tables(const uint64_t* pts, size_t n_pts, std::vector<gh_rt::FixedTable*>& tables) {
+    const size_t nt = abc_table_count(n_pts - 1);
+    while (tables.size() < nt) {
+        uint64_t xyz[36];
+        memcpy(xyz, pts + 24 * (tables.size() + 1), 192);
+        memcpy(xyz + 24, EngineHost<E>::one(), 96);
+        gh_rt::FixedTable* t = nullptr;
+        if (int rc = gh_rt::fixed_table_create(EngineHost<E>::g1_curve, xyz, VB_BITS, ABC_WINDOW, &t)) return rc;
+        tables.push_back(t);
+    }
+    return GH_OK;
+}
+
 // the device side of a key: the two prepared tables, alpha_g1_beta_g2, gamma_abc_g1 and its fixed-base tables
 template <class E> int vk_ensure(gh_groth16_vk* h) {
     if (h->built) return GH_OK;
@@ -402,15 +425,7 @@ template <class E> int vk_ensure(gh_groth16_vk* h) {
     GH_LAUNCH((g2_prepare_kernel<E>), dim3(1), dim3(BLOCK), 0, g.stream, d_g2.as<const uint32_t>(), 2, d_tab.as<typename E::Coeff>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g.stream));
-    const size_t nt = abc_table_count(h->n_abc - 1);
-    while (h->tables.size() < nt) {
-        uint64_t xyz[36];
-        memcpy(xyz, h->abc.data() + 24 * (h->tables.size() + 1), 192);
-        memcpy(xyz + 24, EngineHost<E>::one(), 96);
-        gh_rt::FixedTable* t = nullptr;
-        if ((rc = gh_rt::fixed_table_create(EngineHost<E>::g1_curve, xyz, VB_BITS, ABC_WINDOW, &t))) return rc;   // a later call resumes here
-        h->tables.push_back(t);
-    }
+    if ((rc = ensure_abc_tables<E>(h->abc.data(), h->n_abc, h->tables))) return rc;
     h->d_tab = std::move(d_tab);
     h->d_gt = std::move(d_gt);
     h->d_abc = std::move(d_abc);
@@ -418,8 +433,12 @@ template <class E> int vk_ensure(gh_groth16_vk* h) {
     return GH_OK;
 }
 
-// d_acc[i] = gamma_abc_g1[0] + sum_j inputs[i][j] gamma_abc_g1[j + 1], then affine in ABI form at d_xy / d_inf
-template <class E> int launch_g_ic(gh_groth16_vk* h, const uint64_t* d_inputs, size_t n, size_t n_inputs, uint64_t* d_xy, uint8_t* d_inf) {
+// d_acc[i] = abc[0] + sum_j inputs[i][j] abc[j + 1], then affine in ABI form at d_xy / d_inf.  abc: the n_inputs + 1 base points
+// on the device (Groth16's gamma_abc_g1, GM17's query); tables: the fixed-base tables of abc[1 ..], the inputs beyond them go
+// through the variable-base kernels
+template <class E>
+int launch_g_ic(const uint32_t* abc, const std::vector<gh_rt::FixedTable*>& tables, const uint64_t* d_inputs, size_t n, size_t n_inputs,
+                uint64_t* d_xy, uint8_t* d_inf) {
     typedef typename E::G1 C;
     Proj<C>*d_acc, *d_tmp;
     Fp* d_zp;
@@ -429,16 +448,15 @@ template <class E> int launch_g_ic(gh_groth16_vk* h, const uint64_t* d_inputs, s
     if (!rc) rc = dbuf("vb_p2", n, &d_tmp);
     if (!rc) rc = dbuf("vb_zp", n, &d_zp);
     if (!rc && n_inputs) rc = dbuf("vb_pair_k", n * n_inputs * 24, &d_k);
-    if (!rc && h->tables.size() < n_inputs) rc = dbuf("vb_pk", n * 24, &d_base);
+    if (!rc && tables.size() < n_inputs) rc = dbuf("vb_pk", n * 24, &d_base);
     if (rc) return rc;
-    const uint32_t* abc = h->d_abc.as<const uint32_t>();
     GH_LAUNCH((fill_proj_kernel<C>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, d_acc, n, abc);
     if (n_inputs)
         GH_LAUNCH((inputs_to_int_kernel<typename EngineHost<E>::PS>), dim3(blocks(n * n_inputs, 256)), dim3(256), 0, g.stream, (const uint32_t*)d_inputs, n, n_inputs, d_k);
     for (size_t j = 0; j < n_inputs; j++) {
         const uint32_t* kj = d_k + j * n * 24;
-        if (j < h->tables.size()) {
-            if ((rc = gh_rt::fixed_table_sums(h->tables[j], kj, n, d_tmp))) return rc;
+        if (j < tables.size()) {
+            if ((rc = gh_rt::fixed_table_sums(tables[j], kj, n, d_tmp))) return rc;
         } else {
             GH_LAUNCH(bcast_xy_kernel, dim3(blocks(n * 48, 256)), dim3(256), 0, g.stream, abc + 48 * (j + 1), n, (uint32_t*)d_base);
             if ((rc = vb_single<C, 4>(d_base, nullptr, 0, &kj, &d_tmp, 1, n))) return rc;
@@ -477,7 +495,7 @@ int run_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, con
     GH_LAUNCH((proof_check_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_a, (const uint8_t*)d_ai,
               (const uint32_t*)d_b, (const uint8_t*)d_bi, (const uint32_t*)d_c, (const uint8_t*)d_ci, n, curve_b<typename E::G1>(),
               EngineHost<E>::g2_b(), d_st);
-    if ((rc = launch_g_ic<E>(h, d_in, n, n_inputs, d_gic, d_gi)) || (rc = ph.mark())) return rc;
+    if ((rc = launch_g_ic<E>(h->d_abc.as<const uint32_t>(), h->tables, d_in, n, n_inputs, d_gic, d_gi)) || (rc = ph.mark())) return rc;
     PairIn in{};
     const uint64_t* g1s[3] = {d_a, d_gic, d_c};
     const uint8_t* infs[3] = {d_ai, d_gi, d_ci};
@@ -592,7 +610,8 @@ int api_last_timing(float* phase_ms, int max_phases, float* total_ms) { return g
 #define GH_DEFINE_PAIRING_OPS(ENGINE, NAME)                                                                                 \
     namespace gh_rt {                                                                                                        \
     const PairingOps* NAME() {                                                                                               \
-        static const PairingOps ops = {&api_product<ENGINE>, &api_vk_create<ENGINE>, &api_verify<ENGINE>, &api_last_timing}; \
+        static const PairingOps ops = {&api_product<ENGINE>,        &api_vk_create<ENGINE>, &api_verify<ENGINE>,  &api_last_timing, \
+                                       &api_gm17_vk_create<ENGINE>, &api_gm17_verify<ENGINE>, &api_gm17_last_timing};           \
         return &ops;                                                                                                         \
     }                                                                                                                        \
     }

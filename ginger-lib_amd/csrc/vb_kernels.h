@@ -326,7 +326,7 @@ struct GeneratorTable {
 
 // A unit's timing record, what its *_last_timing reports.  Each unit has its own instance: the two report separately.
 struct Timing {
-    static constexpr int MAX_PHASES = 7;  // g.ev holds 8 events
+    static constexpr int MAX_PHASES = 9;  // g.ev holds 10 events
     int nph;
     float ms[MAX_PHASES] = {};
     float total_ms = 0;

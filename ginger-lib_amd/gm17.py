@@ -291,6 +291,32 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, t, g1_xyz, g2_xyz)
     return pk, info
 
 
+def verifying_key(gl, pairing, pk, alpha, beta, gamma, g1_xyz, g2_xyz):
+    """The VerifyingKey of generate_parameters' `pk` (generator.rs:305-321) for the same toxic waste and generators: the five
+    single points h_g2 = h, g_alpha_g1 = alpha g, h_beta_g2 = beta h, g_gamma_g1 = gamma g, h_gamma_g2 = gamma h by host-side
+    scalar multiplications (gh_proj_mul) and into_affine, and query = pk["verifier_query"].  Returns a dict of Montgomery limb
+    rows (G1 24, G2 24 * deg u64; query: num_inputs x 24) plus "pairing": what gm17_verify.PreparedVerifyingKey.from_key takes.
+    As in the reference, proofs of `pk` satisfy the verifier's first equation for gamma = 1 only, the value
+    generate_random_parameters fixes (generator.rs:27): the C queries carry gamma c_i + (alpha + beta) a_i for the public inputs
+    and for the auxiliary variables alike, and the two differ by (gamma - 1)((alpha + beta) sum a_i x_i + gamma sum c_i x_i)
+    over the auxiliary variables."""
+    r = _MODULUS[pairing]
+    g1c, g2c = pairing + "_g1", pairing + "_g2"
+
+    def point(curve, xyz, k):
+        xy, inf = gl.proj_to_affine(curve, gl.proj_mul(curve, xyz, _canon_rows([k % r])[0]))
+        if inf:
+            raise ValueError("a point of the verifying key is the point at infinity")
+        return np.asarray(xy, dtype=np.uint64).reshape(-1)
+
+    query = np.ascontiguousarray(pk["verifier_query"], dtype=np.uint64).reshape(-1, 24)
+    if not query.any(axis=1).all():                                                # GroupAffine::zero() written as zeros: an input no constraint uses
+        raise ValueError("a point of the verifying key is the point at infinity")
+    return {"pairing": pairing, "h_g2": point(g2c, g2_xyz, 1), "g_alpha_g1": point(g1c, g1_xyz, alpha), "h_beta_g2": point(g2c, g2_xyz, beta),
+            "g_gamma_g1": point(g1c, g1_xyz, gamma), "h_gamma_g2": point(g2c, g2_xyz, gamma),
+            "query": query}
+
+
 def proof_bytes(pairing, proof):
     """A || B || C as GroupAffine::write records (GM17's own Proof::write is unimplemented upstream: gm17/mod.rs:59-69)"""
     (a, ai), (b, bi), (c, ci) = proof

@@ -9,7 +9,12 @@ The rows are valid proofs of a key made from random scalars, so that (A, B, C) i
     a b = alpha beta + (k_0 + sum_j x_j k_j) gamma + c delta;
 4096 distinct rows are tiled to the batch size (no kernel looks at another row).  Every status must be 1.
 Prints one JSON document.
-Usage: timeout -k 10 900 python tools/pairing_bench.py [--engine mnt4753|mnt6753] [--log2n 16 20] [--reps 3] > out.json"""
+
+--scheme gm17 measures gh_gm17_verify instead of the pairing: valid proofs (a G, a H, c G) of a GM17 key known in the exponent,
+    (a + alpha)(a + beta) = alpha beta + (k_0 + sum_j x_j k_j) gamma + c,
+two public inputs, next to gh_groth16_verify in the same run (their ratio), with the product counts it divides by, and merges
+the document into --out (profiles/pairing_bench.json) under "gm17" / the engine.
+Usage: timeout -k 10 900 python tools/pairing_bench.py [--engine mnt4753|mnt6753] [--scheme groth16|gm17] [--log2n 16 20] [--reps 3] > out.json"""
 import argparse
 import json
 import os
@@ -56,7 +61,16 @@ def products(consts, engine="mnt4753"):
         final_exp = fq6_inv + 3 + FQ6_MUL + 7 + FQ6_MUL + 7 + (len(w0) - 1) * CYC_SQR6 + (sum(1 for d in w0 if d) - 1) * FQ6_MUL + FQ6_MUL + 6
         # setup: the conversions of x_P, y_P (2) and of x_Q, y_Q (6) per pair; checks: the proof points' curve equations
         setup1, setup3, checks = 8, 12, 4 + 6 + (2 * FQ3_SQR + FQ3_MUL + 6)
-    return {"variable_pair": variable, "prepared_pair": prepared, "shared_squarings": squarings, "final_exponentiation": final_exp,
+    # GM17 (csrc/gm17_sum.h counts the sums): test1 is Groth16's Miller shape, test2 one variable and one prepared pair; the sums
+    # kernel converts A, B and the two key points (2 + 2 D + 2 + 2 D), writes -S1, S2, -B (2 + 4 D) and adds in G1 and in G2
+    d = 2 if engine == "mnt4753" else 3
+    sum_g1, sum_g2 = 4 + INV + 2, (10 + 2 + INV + 2 + 2 if d == 2 else 22 + 9 + INV + 2 + 3)
+    sums = sum_g1 + sum_g2 + 4 + 4 * d + 2 + 4 * d
+    setup2 = setup3 - 2
+    gm17 = {"gm17_sums": sums, "gm17_test1_miller": variable + 2 * prepared + squarings + setup3,
+            "gm17_test2_miller": variable + prepared + squarings + setup2, "gm17_g_psi_and_checks": g_ic + checks,
+            "gm17_total": 2 * variable + 3 * prepared + 2 * squarings + setup3 + setup2 + 2 * final_exp + sums + g_ic + checks}
+    return {**gm17, "variable_pair": variable, "prepared_pair": prepared, "shared_squarings": squarings, "final_exponentiation": final_exp,
             "pairing_miller": variable + squarings + setup1, "groth16_miller": variable + 2 * prepared + squarings + setup3,
             "groth16_g_ic_and_checks": g_ic + checks,
             "pairing_total": variable + squarings + setup1 + final_exp,
@@ -72,6 +86,8 @@ def main():
     ap.add_argument("--log2n", type=int, nargs="*", default=[16, 20])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--engine", choices=["mnt4753", "mnt6753"], default="mnt4753")
+    ap.add_argument("--scheme", choices=["groth16", "gm17"], default="groth16")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pairing_bench.json"), help="--scheme gm17: the document to merge into")
     a = ap.parse_args()
     eng = a.engine
     from __graft_entry__ import _load_pkg
@@ -107,6 +123,13 @@ def main():
     gt = pairing.pairing_product((abc[0][-1:], abc[1][-1:]), (vk2[0][2:], vk2[1][2:]), engine=eng)
     pvk = pairing.PreparedVerifyingKey(gt, vk2[0][0], vk2[0][1], abc[0][:-1], engine=eng)
     X = groth16._mont_rows([u for xs in xv for u in xs], r).reshape(DISTINCT, N_INPUTS * 12)
+    if a.scheme == "gm17":
+        from ginger_lib_amd import gm17_verify
+        cg = [((x + alpha) * (x + beta) - alpha * beta - (ks[0] + sum(u * k for u, k in zip(xs, ks[1:]))) * gamma) % r for x, xs in zip(av, xv)]
+        gB, gC = g2(av), g1(cg)
+        k1, k2 = g1([alpha, gamma]), g2([beta, gamma, 1])
+        gpvk = gm17_verify.PreparedVerifyingKey(k1[0][0], k2[0][0], k1[0][1], k2[0][1], k2[0][2], abc[0][:-1], engine=eng)
+        print("products per row: %s" % json.dumps({k: v for k, v in prod.items() if k.startswith(("gm17", "groth16"))}), file=sys.stderr, flush=True)
     t1.free()
     t2.free()
     doc = {"device": gl.device_name(), "engine": eng, "fpmul_peak_per_s": peak, "public_inputs": N_INPUTS, "products_per_row": prod, "rows": {}}
@@ -115,8 +138,12 @@ def main():
         tile = lambda arr: np.ascontiguousarray(np.tile(arr, (-(-n // DISTINCT),) + (1,) * (arr.ndim - 1))[:n])
         pa, pb, pc, px = [(tile(q[0]), tile(q[1])) for q in (A, B, Cc)] + [tile(X)]
         res = {"rows": n}
-        for name, call, ok, miller in (("pairing", lambda: pairing.pairing_product(pa, pb, engine=eng), None, prod["pairing_miller"]),
-                                       ("groth16_verify", lambda: pvk.verify(pa, pb, pc, px), 1, prod["groth16_miller"])):
+        calls = [("pairing", lambda: pairing.pairing_product(pa, pb, engine=eng), None, prod["pairing_miller"], pairing),
+                 ("groth16_verify", lambda: pvk.verify(pa, pb, pc, px), 1, prod["groth16_miller"], pairing)]
+        if a.scheme == "gm17":
+            qb, qc = [(tile(q[0]), tile(q[1])) for q in (gB, gC)]
+            calls = calls[1:] + [("gm17_verify", lambda: gpvk.verify(pa, qb, qc, px), 1, None, gm17_verify)]
+        for name, call, ok, miller, mod in calls:
             out = call()                                        # warm: tables, pooled buffers
             if ok is not None:
                 assert (out == ok).all(), "a valid proof did not verify"
@@ -126,8 +153,20 @@ def main():
                 call()
                 dt = time.perf_counter() - t0
                 if best is None or dt < best:
-                    best, phases = dt, pairing.last_timing()
+                    best, phases = dt, mod.last_timing()
             ms = phases[0]
+            if name == "gm17_verify":
+                mil = ms["test1_miller"] + ms["test2_miller"]
+                fe = ms["test1_final_exp"] + ms["test2_final_exp"]
+                res[name] = {"s": best, "per_s": n / best, "phases_ms": ms, "total_ms": phases[1],
+                             "miller_fraction_of_peak": (prod["gm17_test1_miller"] + prod["gm17_test2_miller"]) * n / (mil / 1e3) / peak,
+                             "final_exp_fraction_of_peak": 2 * prod["final_exponentiation"] * n / (fe / 1e3) / peak,
+                             "ratio_to_groth16_verify": best / res["groth16_verify"]["s"],
+                             "predicted_ratio": prod["gm17_total"] / prod["groth16_total"]}
+                print("gm17_verify 2^%d: %.0f /s, Miller %.1f + %.1f ms (%.3f of peak), final exponentiation %.1f ms, %.2f x groth16_verify (products: %.2f)" % (
+                    lg, n / best, ms["test1_miller"], ms["test2_miller"], res[name]["miller_fraction_of_peak"], fe,
+                    res[name]["ratio_to_groth16_verify"], res[name]["predicted_ratio"]), file=sys.stderr, flush=True)
+                continue
             res[name] = {"s": best, "per_s": n / best, "phases_ms": ms, "total_ms": phases[1],
                          "miller_fraction_of_peak": miller * n / (ms["miller"] / 1e3) / peak,
                          "final_exp_fraction_of_peak": prod["final_exponentiation"] * n / (ms["final_exp"] / 1e3) / peak}
@@ -136,6 +175,12 @@ def main():
                 res[name]["final_exp_fraction_of_peak"]), file=sys.stderr, flush=True)
         doc["rows"][str(lg)] = res
     pvk.close()
+    if a.scheme == "gm17":
+        gpvk.close()
+        merged = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        merged.setdefault("gm17", {})[eng] = doc
+        with open(a.out, "w") as f:
+            f.write(json.dumps(merged, indent=1) + "\n")
     print(json.dumps(doc, indent=1))
 
 
