@@ -10,7 +10,7 @@ import os
 import subprocess
 import sys
 
-from . import g1_xyzz, g2_rounds, microbench, ntt_pass
+from . import g1_reduce, g1_xyzz, g2_rounds, microbench, ntt_pass
 from .isa import module_text
 
 LLVM = os.environ.get("GH_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
@@ -24,6 +24,9 @@ def programs():
     progs = [
         g1_xyzz.build("gh_asm_acc_g1_p4", P4, R % P4),
         g1_xyzz.build("gh_asm_acc_g1_p6", P6, R % P6),
+        # lean level 1 of the G1 bucket reduction (the common path; msm_reduce_kernels.h keeps the doubling detour)
+        g1_reduce.build("gh_asm_red_g1_p4", P4, R % P4),
+        g1_reduce.build("gh_asm_red_g1_p6", P6, R % P6),
     ]
     # the affine rounds of the G2 MSMs: forward / backward kernel of round 0 and of the later rounds, per tower
     c2 = g2_rounds.Cfg(2, 13, P4, R % P4)          # MNT4-753 G2: Fq2 = Fq[u] / (u^2 - 13)   (fields/mnt4753/fq2.rs:19)

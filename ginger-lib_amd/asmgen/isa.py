@@ -122,6 +122,7 @@ class Prog:
         self.max_v = 0
         self.max_a = -1
         self.max_s = 0
+        self.wg_id_y = 0             # 1: a two-dimensional grid (workgroup id y in the SGPR after id x)
         self._uniq = 0
 
     # ---- emission
@@ -195,7 +196,7 @@ class Prog:
             ("uses_dynamic_stack", 0),
             ("enable_private_segment", 0),
             ("system_sgpr_workgroup_id_x", 1),
-            ("system_sgpr_workgroup_id_y", 0),
+            ("system_sgpr_workgroup_id_y", self.wg_id_y),
             ("system_sgpr_workgroup_id_z", 0),
             ("system_vgpr_workitem_id", 0),
             ("next_free_vgpr", max(next_free_vgpr, 1)),

@@ -26,6 +26,7 @@ struct State {
     bool tried = false;
     hipModule_t mod = nullptr;
     hipFunction_t acc_g1[2] = {nullptr, nullptr};   // [0]: p4 (MNT4-753 G1), [1]: p6 (MNT6-753 G1)
+    hipFunction_t red_g1[2] = {nullptr, nullptr};   // [0]: p4, [1]: p6
     hipFunction_t aff[4][2][2] = {};                // [kind: f2, f3, f1p4, f1p6][fwd][r0]
     hipFunction_t mb_mulpair = nullptr;
     hipFunction_t ntt[2][3] = {};                   // [p4, p6][k - 6]
@@ -65,6 +66,15 @@ int load_locked() {
         e = hipModuleGetFunction(&s.acc_g1[i], m, names[i]);
         if (e != hipSuccess) {
             g_err = std::string("hipModuleGetFunction(") + names[i] + ") failed: " + hipGetErrorString(e);
+            hipModuleUnload(m);
+            return GH_E_HIP;
+        }
+    }
+    static const char* red_names[2] = {"gh_asm_red_g1_p4", "gh_asm_red_g1_p6"};
+    for (int i = 0; i < 2; i++) {
+        e = hipModuleGetFunction(&s.red_g1[i], m, red_names[i]);
+        if (e != hipSuccess) {
+            g_err = std::string("hipModuleGetFunction(") + red_names[i] + ") failed: " + hipGetErrorString(e);
             hipModuleUnload(m);
             return GH_E_HIP;
         }
@@ -128,6 +138,27 @@ int acc_g1_launch(int prime, const void* bases, const uint32_t* sorted, const Ac
     size_t size = sizeof args;
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     HIPCHK(hipModuleLaunchKernel(s.acc_g1[prime == 6 ? 1 : 0], (n_tasks + 255) / 256, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
+    return GH_OK;
+}
+
+bool reduce_enabled() {
+    static const bool on = gh_rt::msm_knobs().reduce_asm != 0;
+    return on && load_locked() == GH_OK;
+}
+
+int red_g1_launch(int prime, const RedArgs& a, uint32_t windows, hipStream_t st) {
+    if (a.n_programs == 0) return GH_OK;
+    // what the kernel's 32-bit index arithmetic assumes (asmgen/g1_reduce.py): item indices, and a grid of (segs, windows)
+    if (a.L < 2 || a.segs == 0 || windows == 0 || windows > 65535u || (uint64_t)windows * a.segs != a.n_programs ||
+        (uint64_t)windows * a.count + (uint64_t)a.segs * 64u * a.L >= (1ull << 32) || a.n_programs >= (1u << 24)) {
+        g_err = "internal: bucket reduction outside the assembly kernel's index range";
+        return GH_E_UNSUPPORTED;
+    }
+    if (int rc = load_locked()) return rc;
+    RedArgs args = a;
+    size_t size = sizeof args;
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    HIPCHK(hipModuleLaunchKernel(s.red_g1[prime == 6 ? 1 : 0], a.segs, windows, 1, 64, 1, 1, 0, st, nullptr, extra));
     return GH_OK;
 }
 
@@ -210,6 +241,8 @@ int kernel_resources(const char* which, uint32_t* scratch, uint32_t* vgprs, uint
     const std::string w = which ? which : "";
     if (w == "g1_acc_p4") f = s.acc_g1[0];
     else if (w == "g1_acc_p6") f = s.acc_g1[1];
+    else if (w == "g1_red_p4") f = s.red_g1[0];
+    else if (w == "g1_red_p6") f = s.red_g1[1];
     else if (w == "g2_f2_fwd_r0") f = s.aff[0][1][1];
     else if (w == "g2_f2_bwd_r0") f = s.aff[0][0][1];
     else if (w == "g2_f2_bwd_rn") f = s.aff[0][0][0];

@@ -210,6 +210,7 @@ struct MsmJob {
     uint32_t *counts = nullptr, *starts = nullptr, *cursor = nullptr, *sorted = nullptr, *order = nullptr, *size_hist = nullptr,
              *size_cursor = nullptr, *chunk_start = nullptr, *plan = nullptr;
     Proj<C>*buckets = nullptr, *seg_out = nullptr, *win_out = nullptr, *partials = nullptr, *lane_out = nullptr;
+    uint32_t* red_flag = nullptr;                        // lean level 1 by the generated kernel: per program, "compute it again"
     uint32_t *aff_cnt = nullptr, *aff_st = nullptr;      // affine rounds: per round, the buckets' sizes and offsets
     bool aff_sticky_pending = false;
     uint32_t* hplan = nullptr;      // pinned
@@ -272,6 +273,7 @@ struct MsmJob {
         // (also for the last MSM of a batch, which does not use it: a buffer that is first allocated in the middle of a later batch
         //  costs that batch a device-wide wait -- 9 ms at 2^20)
         if (p.lane_buf && (rc = slot_buf("lane_out", slot, (size_t)p.RW * p.segs_per_window * 64 * 2 * sizeof(Proj<C>), &lane_out))) return rc;
+        if (p.lane_buf && (rc = slot_buf("reduce_flag", slot, (size_t)p.RW * p.segs_per_window * 4 + 64, &red_flag))) return rc;
         if ((rc = pinned(es, 0, 512, (void**)&hplan))) return rc;
         if ((rc = pinned(es, 1, (size_t)9 * p.RW * sizeof(Proj<C>), (void**)&hw))) return rc;
         return GH_OK;
@@ -600,18 +602,48 @@ struct MsmJob {
     // one level of the bucket reduction: `grid` wave programs (msm_reduce_kernels.h) over up to three inputs.  G1: the 512-register
     // build of the program (one_wave) or the 256-register one; G2: the lane-group program.
     int reduce_level(unsigned grid, const WaveReduceIn<C>& i0, const WaveReduceIn<C>& i1, const WaveReduceIn<C>& i2, uint32_t per_input,
-                     uint32_t n_inputs, uint32_t segs, int L, Proj<C>* out, uint32_t* slabs, bool one_wave, hipStream_t st) {
+                     uint32_t n_inputs, uint32_t segs, int L, Proj<C>* out, uint32_t* slabs, bool one_wave, hipStream_t st,
+                     const uint32_t* run_if = nullptr) {
         if constexpr (DEG >= 2) {
             GH_LAUNCH((msm_wave_reduce_split_kernel<C, FS, FS::LANES, DEG == 2 ? 32 : 16>), dim3(grid), dim3(64), 64 * sizeof(P3), st,
                       i0, i1, i2, per_input, n_inputs, segs, L, (const Aff<C>*)salts, out, slabs);
         } else if (one_wave) {
             GH_LAUNCH((msm_wave_reduce_kernel<C, 1>), dim3(grid), dim3(64), 64 * sizeof(Proj<C>), st,
-                      i0, i1, i2, per_input, n_inputs, segs, L, (const Aff<C>*)salts, out, slabs);
+                      i0, i1, i2, per_input, n_inputs, segs, L, (const Aff<C>*)salts, out, slabs, run_if);
         } else {
             GH_LAUNCH((msm_wave_reduce_kernel<C, 2>), dim3(grid), dim3(64), 64 * sizeof(Proj<C>), st,
-                      i0, i1, i2, per_input, n_inputs, segs, L, (const Aff<C>*)salts, out, slabs);
+                      i0, i1, i2, per_input, n_inputs, segs, L, (const Aff<C>*)salts, out, slabs, run_if);
         }
         return GH_OK;
+    }
+
+    // Lean level 1.  G1: the generated kernel (asmgen/g1_reduce.py: the common path of the addition, no scratch) on the 256-register
+    // side, i.e. unless GH_REDUCE_WAVES=1 asks for the 512-register build of the C++ program; behind it the C++ program in its
+    // 256-register build over the same programs with run_if = the generated kernel's flags: a program that met a doubling is
+    // computed again, whole, from the buckets and overwrites its rows of lane_out -- the C++ kernel stays the one place that
+    // knows the salt detour.
+    int lean_level1(const WaveReduceIn<C>& i0, unsigned nb1, uint32_t segs, uint32_t* slabs, bool one_wave, hipStream_t st) {
+        const WaveReduceIn<C> none{nullptr, 0, 0, 0, 0, 0};
+        if constexpr (DEG == 1) {
+            if (msm_knobs().reduce_waves != 1 && p.L1 >= 2 && red_flag && gh_asm::reduce_enabled()) {
+                gh_asm::RedArgs a;
+                a.items = i0.base; a.out = lane_out; a.slabs = slabs; a.flag = red_flag;
+                a.count = i0.count; a.valid = i0.valid; a.segs = segs; a.L = (uint32_t)p.L1; a.n_programs = nb1; a.pad = 0;
+                int rc;
+                if ((rc = gh_asm::red_g1_launch(std::is_same<C, Mnt6G1>::value ? 6 : 4, a, (uint32_t)p.RW, st)) ||
+                    (rc = reduce_level(nb1, i0, none, none, nb1, 1u, segs, p.L1, lane_out, slabs, false, st, red_flag))) return rc;
+                if (msm_knobs().reduce_debug) {   // GH_REDUCE_DEBUG: how many programs the C++ kernel computed again
+                    std::vector<uint32_t> fw(nb1);
+                    HIPCHK(hipStreamSynchronize(st));
+                    HIPCHK(hipMemcpy(fw.data(), red_flag, (size_t)nb1 * 4, hipMemcpyDeviceToHost));
+                    unsigned redone = 0;
+                    for (uint32_t v : fw) redone += v != 0;
+                    fprintf(stderr, "reduce: programs %u redone %u\n", nb1, redone);
+                }
+                return GH_OK;
+            }
+        }
+        return reduce_level(nb1, i0, none, none, nb1, 1u, segs, p.L1, lane_out, slabs, one_wave, st);
     }
 
     // stage 3 (stream st): the two wave-program levels of the bucket reduction; window sums -> host
@@ -636,7 +668,7 @@ struct MsmJob {
             const uint32_t lanes_per_window = segs * 64u;
             const WaveReduceIn<C> i0{buckets, 1, 0, p.Q, 2, (uint32_t)p.total};
             const WaveReduceIn<C> l0{lane_out, 2, 0, lanes_per_window, 0, all}, l1{lane_out, 2, 1, lanes_per_window, 1, all};
-            if ((rc = reduce_level(nb1, i0, none, none, nb1, 1u, segs, p.L1, lane_out, slabs, one_wave, st)) ||
+            if ((rc = lean_level1(i0, nb1, segs, slabs, one_wave, st)) ||
                 (rc = reduce_level(2 * RW, l0, l1, none, RW, 2u, 1u, (int)segs, win_out, slabs, one_wave, st))) return rc;
         } else {
             // level 1: one wave per segment of tpw * L1 bucket slots -> (runW, A, Bv) per segment

@@ -34,6 +34,8 @@ struct MsmKnobs {
     int reduce_l = 0;               // GH_REDUCE_L: segment length of the reduction programs (a power of two in 4..128; 0 = chosen)
     int reduce_lean = -1;           // GH_REDUCE_LEAN=0 / 1: segment form / lane-level form of a G1 reduction everywhere (-1 = chosen)
     int reduce_waves = 0;           // GH_REDUCE_WAVES=1 / 2: the 512- / 256-register build of the G1 reduction program (0 = by `solo`)
+    int reduce_asm = 1;             // GH_REDUCE_ASM=0: lean level 1 of a G1 reduction on the C++ kernel instead of the generated one (A/B)
+    bool reduce_debug = false;      // GH_REDUCE_DEBUG (set): per lean level 1, programs run / computed again (stderr; synchronises)
     int affine = -1;                // GH_AFFINE=0 / 1 / 2: overrides gh_msm_set_affine (-1 = unset)
     int agg_iters = 12;             // GH_AGG_ITERS: keys a wave folds into one atomic in the small-input histogram / scatter
     int sort = 0;                   // GH_SORT=atomic (1) / part (2): bucket lists by device-scope atomics / by the LDS counting sort
@@ -57,6 +59,8 @@ struct MsmKnobs {
         k.reduce_l = env_int("GH_REDUCE_L", k.reduce_l);
         k.reduce_lean = env_int("GH_REDUCE_LEAN", k.reduce_lean);
         k.reduce_waves = env_int("GH_REDUCE_WAVES", k.reduce_waves);
+        k.reduce_asm = env_int("GH_REDUCE_ASM", k.reduce_asm);
+        k.reduce_debug = getenv("GH_REDUCE_DEBUG") != nullptr;
         k.affine = env_int("GH_AFFINE", k.affine);
         const int agg = env_int("GH_AGG_ITERS", -1);
         if (agg >= 0) k.agg_iters = agg;

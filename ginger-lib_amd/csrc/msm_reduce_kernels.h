@@ -296,7 +296,7 @@ template <class C, int WAVES = 2>
 __global__ void __launch_bounds__(256, WAVES)
 msm_wave_reduce_kernel(WaveReduceIn<C> in0, WaveReduceIn<C> in1, WaveReduceIn<C> in2, uint32_t blocks_per_input,
                        uint32_t n_inputs, uint32_t segs_per_window, int L, const Aff<C>* __restrict__ salts,
-                       Proj<C>* __restrict__ out, uint32_t* __restrict__ slabs) {
+                       Proj<C>* __restrict__ out, uint32_t* __restrict__ slabs, const uint32_t* __restrict__ run_if) {
     typedef typename C::F F;
     typedef WaveSlab<Proj<C>> SL;
     enum { RUN = 0, WACC = 1, TMP = 2 };
@@ -305,6 +305,9 @@ msm_wave_reduce_kernel(WaveReduceIn<C> in0, WaveReduceIn<C> in1, WaveReduceIn<C>
     Proj<C>* sh = reinterpret_cast<Proj<C>*>(lds_raw) + 64 * (threadIdx.x >> 6);
     const uint32_t gb = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // one program per wave
     if (gb >= n_inputs * blocks_per_input) return;
+    // run_if (lean level 1 behind the generated kernel, asmgen/g1_reduce.py): only the programs that kernel flagged -- they met a
+    // doubling, which it leaves to the detour below -- are computed, whole, from the buckets
+    if (run_if && run_if[gb] == 0) return;
     const uint32_t which = gb / blocks_per_input, blk = gb % blocks_per_input;
     const WaveReduceIn<C> in = which == 0 ? in0 : (which == 1 ? in1 : in2);
     const uint32_t w = blk / segs_per_window, seg = blk % segs_per_window;
