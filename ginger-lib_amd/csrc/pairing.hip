@@ -1,4 +1,5 @@
-// pairing.hip -- the C ABI of include/ginger_hip_pairing.h and include/ginger_hip_gm17.h: the entry points take the lock, find
+// pairing.hip -- the C ABI of include/ginger_hip_pairing.h and include/ginger_hip_gm17.h, and the two validating verifiers of
+// include/ginger_hip_points.h: the entry points take the lock, find
 // the engine's PairingOps and call them.  The kernels and the host steps are the templates of pairing_impl.h and
 // gm17_verify_impl.h; this unit instantiates them for MNT4-753, pairing_mnt6753.hip for MNT6-753.  DESIGN.md sections 14, 14b.
 #include "pairing_impl.h"
@@ -76,6 +77,31 @@ int gh_groth16_verify(gh_groth16_vk_t h, const uint64_t* a_xy, const uint8_t* a_
 int gh_pairing_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     return ops_of_engine(g_last_engine)->last_timing(phase_ms, max_phases, total_ms);
+} catch (...) { return gh_rt::api_exception(); }
+
+// ---- include/ginger_hip_points.h: the verifiers that validate their proof points first (the rest of that header: points.hip)
+int gh_groth16_verify_checked(gh_groth16_vk_t h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf,
+                              const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status,
+                              uint8_t* out_point_status) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    Trim trim_;
+    if (int rc = checked_handle(h)) return rc;
+    const PairingOps* ops = ops_of_engine(h->engine);
+    if (!ops) return GH_E_BAD_HANDLE;
+    g_last_engine = h->engine;
+    return ops->verify_validated(h, 0, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status, out_point_status);
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_groth16_verify_compressed(gh_groth16_vk_t h, const uint64_t* a_x, const uint8_t* a_flags, const uint64_t* b_x, const uint8_t* b_flags,
+                                 const uint64_t* c_x, const uint8_t* c_flags, const uint64_t* inputs, size_t n, size_t n_inputs,
+                                 uint8_t* out_status, uint8_t* out_point_status) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    Trim trim_;
+    if (int rc = checked_handle(h)) return rc;
+    const PairingOps* ops = ops_of_engine(h->engine);
+    if (!ops) return GH_E_BAD_HANDLE;
+    g_last_engine = h->engine;
+    return ops->verify_validated(h, 1, a_x, a_flags, b_x, b_flags, c_x, c_flags, inputs, n, n_inputs, out_status, out_point_status);
 } catch (...) { return gh_rt::api_exception(); }
 
 // ---- include/ginger_hip_gm17.h

@@ -10,7 +10,7 @@
 // with the row index fastest like the slabs of vb_kernels.h, so a wave reads 256 consecutive bytes per limb.  A prepared Q
 // (the verifying key's -gamma and -delta) is a table of 499 line coefficients in global memory that every lane reads at the
 // same step.
-//   pair_setup_kernel    ABI points -> the row's slab, the pair's skip flag (a point at infinity, or a row of status 2)
+//   pair_setup_kernel    ABI points -> the row's slab, the pair's skip flag (a point at infinity, or a row of status 2 or 3)
 //   miller_kernel        KV variable + KP prepared pairs with one shared f: f is squared once per digit and multiplied by every
 //                        pair's line.  The loop over the 376 signed digits is wave-uniform; only skipped pairs diverge.
 //   final_exp_kernel     the reference's split final exponentiation, out in ABI form
@@ -20,6 +20,7 @@
 #include "vb_kernels.h"
 #include "pairing29_mnt6.h"
 #include "../../include/ginger_hip_pairing.h"
+#include "../../include/ginger_hip_points.h"
 
 struct gh_groth16_vk {
     static constexpr uint32_t MAGIC = 0x67684756u;
@@ -51,6 +52,11 @@ struct PairingOps {
     int (*verify)(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
                   const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status);
     int (*last_timing)(float* phase_ms, int max_phases, float* total_ms);
+    // include/ginger_hip_points.h: verify after the membership test of A, B, C (compressed == 0: the points as for verify) or
+    // after their decompression (compressed != 0: a, b, c hold canonical x, the *_inf arguments the flags bytes)
+    int (*verify_validated)(gh_groth16_vk* h, int compressed, const uint64_t* a, const uint8_t* a_inf, const uint64_t* b, const uint8_t* b_inf,
+                            const uint64_t* c, const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status,
+                            uint8_t* out_point_status);
     // the GM17 verifier of gm17_verify_impl.h (include/ginger_hip_gm17.h)
     int (*gm17_vk_create)(int engine, const uint64_t* g_alpha_g1_xy, const uint64_t* h_beta_g2_xy, const uint64_t* g_gamma_g1_xy,
                           const uint64_t* h_gamma_g2_xy, const uint64_t* h_g2_xy, const uint64_t* query_g1_xy, size_t n_query, gh_gm17_vk** out);
@@ -152,7 +158,7 @@ pair_setup_kernel(PairIn in, const uint8_t* __restrict__ status, size_t row0, si
     if (t >= cnt) return;
     const size_t i = row0 + t;
     const RowSlab s{slab + t, cnt};
-    const bool dead = status && status[i] == 2;
+    const bool dead = status && status[i] >= 2;               // 2: a point off its curve, 3: a point failed validation
 #pragma unroll
     for (int j = 0; j < KV + KP; j++) {
         bool sk = dead || in.g1_inf[j][i * in.g1_inf_stride[j]] != 0;
@@ -281,13 +287,20 @@ proof_check_kernel(const uint32_t* __restrict__ a, const uint8_t* __restrict__ a
     status[i] = ok ? 0 : 2;
 }
 
-// 1 if the row's value (W u64 words) is the key's alpha_g1_beta_g2, 0 if not; rows of status 2 keep it
+// status 3 (GH_VERIFY_INVALID_POINT) for a row with a non-zero point code (pst: 3 per row, A, B, C), over what proof_check_kernel wrote
+__global__ void __launch_bounds__(256) point_status_kernel(const uint8_t* __restrict__ pst, size_t n, uint8_t* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (pst[3 * i] | pst[3 * i + 1] | pst[3 * i + 2]) status[i] = GH_VERIFY_INVALID_POINT;
+}
+
+// 1 if the row's value (W u64 words) is the key's alpha_g1_beta_g2, 0 if not; rows of status 2 and 3 keep it
 template <int W>
 __global__ void __launch_bounds__(256) gt_compare_kernel(const uint64_t* __restrict__ val, const uint64_t* __restrict__ gt, size_t n,
                                                          uint8_t* __restrict__ status) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (status[i] == 2) return;
+    if (status[i] >= 2) return;
     bool eq = true;
     for (int w = 0; w < W; w++) eq &= val[i * W + w] == gt[w];
     status[i] = eq;
@@ -468,54 +481,126 @@ int launch_g_ic(const uint32_t* abc, const std::vector<gh_rt::FixedTable*>& tabl
     return GH_OK;
 }
 
-template <class E>
-int run_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
-               const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
-    constexpr size_t TW = tower_words<E>() / 2;    // u64 words of a G2 point and of a GT element
-    if (int rc = vk_ensure<E>(h)) return rc;
+// the pooled buffers of a verification of n rows: A, B, C with their infinity bytes, the inputs, g_ic, the rows' values and status
+struct VerifyBufs {
     uint64_t *d_a, *d_b, *d_c, *d_in = nullptr, *d_gic, *d_val;
     uint8_t *d_ai, *d_bi, *d_ci, *d_gi, *d_st;
-    int rc = dbuf("vb_pair_g1", n * 24, &d_a);
-    if (!rc) rc = dbuf("vb_pair_g2", n * TW, &d_b);
-    if (!rc) rc = dbuf("vb_pair_c", n * 24, &d_c);
-    if (!rc) rc = dbuf("vb_pair_i1", n, &d_ai);
-    if (!rc) rc = dbuf("vb_pair_i2", n, &d_bi);
-    if (!rc) rc = dbuf("vb_pair_i3", n, &d_ci);
-    if (!rc && n_inputs) rc = dbuf("vb_pair_in", n * n_inputs * 12, &d_in);
-    if (!rc) rc = dbuf("vb_xy", n * 24, &d_gic);
-    if (!rc) rc = dbuf("vb_inf", n, &d_gi);
-    if (!rc) rc = dbuf("vb_pair_val", n * TW, &d_val);
-    if (!rc) rc = dbuf("vb_st", n, &d_st);
-    if (rc) return rc;
-    Phases ph{g_tm};
-    if ((rc = ph.mark())) return rc;
-    if ((rc = up(d_a, a_xy, n * 24)) || (rc = up(d_b, b_xy, n * TW)) || (rc = up(d_c, c_xy, n * 24)) || (rc = up(d_ai, a_inf, n)) ||
-        (rc = up(d_bi, b_inf, n)) || (rc = up(d_ci, c_inf, n)) || (n_inputs && (rc = up(d_in, inputs, n * n_inputs * 12))) || (rc = ph.mark()))
-        return rc;
-    GH_LAUNCH((proof_check_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_a, (const uint8_t*)d_ai,
-              (const uint32_t*)d_b, (const uint8_t*)d_bi, (const uint32_t*)d_c, (const uint8_t*)d_ci, n, curve_b<typename E::G1>(),
-              EngineHost<E>::g2_b(), d_st);
-    if ((rc = launch_g_ic<E>(h->d_abc.as<const uint32_t>(), h->tables, d_in, n, n_inputs, d_gic, d_gi)) || (rc = ph.mark())) return rc;
+};
+template <class E> int verify_bufs(size_t n, size_t n_inputs, VerifyBufs& v) {
+    constexpr size_t TW = tower_words<E>() / 2;    // u64 words of a G2 point and of a GT element
+    int rc = dbuf("vb_pair_g1", n * 24, &v.d_a);
+    if (!rc) rc = dbuf("vb_pair_g2", n * TW, &v.d_b);
+    if (!rc) rc = dbuf("vb_pair_c", n * 24, &v.d_c);
+    if (!rc) rc = dbuf("vb_pair_i1", n, &v.d_ai);
+    if (!rc) rc = dbuf("vb_pair_i2", n, &v.d_bi);
+    if (!rc) rc = dbuf("vb_pair_i3", n, &v.d_ci);
+    if (!rc && n_inputs) rc = dbuf("vb_pair_in", n * n_inputs * 12, &v.d_in);
+    if (!rc) rc = dbuf("vb_xy", n * 24, &v.d_gic);
+    if (!rc) rc = dbuf("vb_inf", n, &v.d_gi);
+    if (!rc) rc = dbuf("vb_pair_val", n * TW, &v.d_val);
+    if (!rc) rc = dbuf("vb_st", n, &v.d_st);
+    return rc;
+}
+
+// the device part of a verification, over proof points and inputs that are on the device: the curve check, g_ic, the Miller
+// loops, the final exponentiation and the compare, with the marks of those phases; v.d_st holds the rows' status.  d_pst
+// (nullable): 3 point codes per row, a row with a non-zero one gets status 3 and is not evaluated.
+template <class E> int verify_device(gh_groth16_vk* h, const VerifyBufs& v, const uint8_t* d_pst, size_t n, size_t n_inputs, Phases& ph) {
+    constexpr size_t TW = tower_words<E>() / 2;
+    int rc;
+    GH_LAUNCH((proof_check_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)v.d_a, (const uint8_t*)v.d_ai,
+              (const uint32_t*)v.d_b, (const uint8_t*)v.d_bi, (const uint32_t*)v.d_c, (const uint8_t*)v.d_ci, n, curve_b<typename E::G1>(),
+              EngineHost<E>::g2_b(), v.d_st);
+    if (d_pst) GH_LAUNCH(point_status_kernel, dim3(blocks(n, 256)), dim3(256), 0, g.stream, d_pst, n, v.d_st);
+    if ((rc = launch_g_ic<E>(h->d_abc.as<const uint32_t>(), h->tables, v.d_in, n, n_inputs, v.d_gic, v.d_gi)) || (rc = ph.mark())) return rc;
     PairIn in{};
-    const uint64_t* g1s[3] = {d_a, d_gic, d_c};
-    const uint8_t* infs[3] = {d_ai, d_gi, d_ci};
+    const uint64_t* g1s[3] = {v.d_a, v.d_gic, v.d_c};
+    const uint8_t* infs[3] = {v.d_ai, v.d_gi, v.d_ci};
     for (int j = 0; j < 3; j++) {
         in.g1[j] = (const uint32_t*)g1s[j];
         in.g1_inf[j] = infs[j];
         in.g1_stride[j] = 48;
         in.g1_inf_stride[j] = 1;
     }
-    in.g2[0] = (const uint32_t*)d_b;
-    in.g2_inf[0] = d_bi;
+    in.g2[0] = (const uint32_t*)v.d_b;
+    in.g2_inf[0] = v.d_bi;
     in.g2_stride[0] = 2 * TW;
     in.g2_inf_stride[0] = 1;
-    if ((rc = launch_pairs<E, 1, 2>(in, d_st, h->d_tab.as<const typename E::Coeff>(), n, d_val, &ph))) return rc;
-    GH_LAUNCH((gt_compare_kernel<(int)TW>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)d_val, h->d_gt.as<const uint64_t>(), n, d_st);
+    if ((rc = launch_pairs<E, 1, 2>(in, v.d_st, h->d_tab.as<const typename E::Coeff>(), n, v.d_val, &ph))) return rc;
+    GH_LAUNCH((gt_compare_kernel<(int)TW>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)v.d_val, h->d_gt.as<const uint64_t>(), n, v.d_st);
     HIPCHK(hipGetLastError());
+    return ph.mark();
+}
+
+template <class E>
+int run_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+               const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
+    constexpr size_t TW = tower_words<E>() / 2;
+    if (int rc = vk_ensure<E>(h)) return rc;
+    VerifyBufs v;
+    int rc = verify_bufs<E>(n, n_inputs, v);
+    if (rc) return rc;
+    Phases ph{g_tm};
     if ((rc = ph.mark())) return rc;
-    HIPCHK(hipMemcpyAsync(out_status, d_st, n, hipMemcpyDeviceToHost, g.stream));
+    if ((rc = up(v.d_a, a_xy, n * 24)) || (rc = up(v.d_b, b_xy, n * TW)) || (rc = up(v.d_c, c_xy, n * 24)) || (rc = up(v.d_ai, a_inf, n)) ||
+        (rc = up(v.d_bi, b_inf, n)) || (rc = up(v.d_ci, c_inf, n)) || (n_inputs && (rc = up(v.d_in, inputs, n * n_inputs * 12))) || (rc = ph.mark()))
+        return rc;
+    if ((rc = verify_device<E>(h, v, nullptr, n, n_inputs, ph))) return rc;
+    HIPCHK(hipMemcpyAsync(out_status, v.d_st, n, hipMemcpyDeviceToHost, g.stream));
     if ((rc = ph.mark())) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
+    return ph.finish();
+}
+
+// gh_groth16_verify_checked / _compressed: the proof points are validated on the device (points.hip) before the verification
+// body runs over them; the validation belongs to the upload phase of this unit's timing record and is the validate phase of
+// gh_points_last_timing.  compressed: a, b, c hold canonical x (12 D u64 per row for B), the *_fl arguments the flags bytes.
+template <class E>
+int run_verify_validated(gh_groth16_vk* h, int compressed, const uint64_t* a, const uint8_t* a_fl, const uint64_t* b, const uint8_t* b_fl,
+                         const uint64_t* c, const uint8_t* c_fl, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status,
+                         uint8_t* out_point_status) {
+    constexpr size_t TW = tower_words<E>() / 2;
+    constexpr gh_curve_t G1 = EngineHost<E>::g1_curve, G2 = (gh_curve_t)(EngineHost<E>::g1_curve + 1);
+    if (int rc = vk_ensure<E>(h)) return rc;
+    VerifyBufs v;
+    uint8_t* d_pst;
+    uint64_t *d_ax = nullptr, *d_bx = nullptr, *d_cx = nullptr;
+    uint8_t *d_af = nullptr, *d_bf = nullptr, *d_cf = nullptr;
+    int rc = verify_bufs<E>(n, n_inputs, v);
+    if (!rc) rc = dbuf("vb_pts_pst", n * 3, &d_pst);
+    if (!rc && compressed) {
+        rc = dbuf("vb_pts_ax", n * 12, &d_ax);
+        if (!rc) rc = dbuf("vb_pts_bx", n * TW / 2, &d_bx);
+        if (!rc) rc = dbuf("vb_pts_cx", n * 12, &d_cx);
+        if (!rc) rc = dbuf("vb_pts_af", n, &d_af);
+        if (!rc) rc = dbuf("vb_pts_bf", n, &d_bf);
+        if (!rc) rc = dbuf("vb_pts_cf", n, &d_cf);
+    }
+    if (rc) return rc;
+    Phases ph{g_tm};
+    if ((rc = ph.mark())) return rc;
+    if (n_inputs && (rc = up(v.d_in, inputs, n * n_inputs * 12))) return rc;
+    if (compressed) {
+        if ((rc = up(d_ax, a, n * 12)) || (rc = up(d_bx, b, n * TW / 2)) || (rc = up(d_cx, c, n * 12)) || (rc = up(d_af, a_fl, n)) ||
+            (rc = up(d_bf, b_fl, n)) || (rc = up(d_cf, c_fl, n)) || (rc = gh_rt::points_validate_mark(0)) ||
+            (rc = gh_rt::points_decompress_dev(G1, d_ax, d_af, n, v.d_a, v.d_ai, d_pst, 3)) ||
+            (rc = gh_rt::points_decompress_dev(G2, d_bx, d_bf, n, v.d_b, v.d_bi, d_pst + 1, 3)) ||
+            (rc = gh_rt::points_decompress_dev(G1, d_cx, d_cf, n, v.d_c, v.d_ci, d_pst + 2, 3)))
+            return rc;
+    } else {
+        if ((rc = up(v.d_a, a, n * 24)) || (rc = up(v.d_b, b, n * TW)) || (rc = up(v.d_c, c, n * 24)) || (rc = up(v.d_ai, a_fl, n)) ||
+            (rc = up(v.d_bi, b_fl, n)) || (rc = up(v.d_ci, c_fl, n)) || (rc = gh_rt::points_validate_mark(0)) ||
+            (rc = gh_rt::points_member_dev(G1, v.d_a, v.d_ai, n, d_pst, 3)) || (rc = gh_rt::points_member_dev(G2, v.d_b, v.d_bi, n, d_pst + 1, 3)) ||
+            (rc = gh_rt::points_member_dev(G1, v.d_c, v.d_ci, n, d_pst + 2, 3)))
+            return rc;
+    }
+    if ((rc = gh_rt::points_validate_mark(1)) || (rc = ph.mark())) return rc;
+    if ((rc = verify_device<E>(h, v, d_pst, n, n_inputs, ph))) return rc;
+    HIPCHK(hipMemcpyAsync(out_status, v.d_st, n, hipMemcpyDeviceToHost, g.stream));
+    if (out_point_status) HIPCHK(hipMemcpyAsync(out_point_status, d_pst, n * 3, hipMemcpyDeviceToHost, g.stream));
+    if ((rc = ph.mark())) return rc;
+    HIPCHK(hipStreamSynchronize(g.stream));
+    if ((rc = gh_rt::points_validate_finish())) return rc;
     return ph.finish();
 }
 
@@ -602,6 +687,26 @@ int api_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, con
     return run_verify<E>(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);
 }
 
+template <class E>
+int api_verify_validated(gh_groth16_vk* h, int compressed, const uint64_t* a, const uint8_t* a_fl, const uint64_t* b, const uint8_t* b_fl,
+                         const uint64_t* c, const uint8_t* c_fl, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status,
+                         uint8_t* out_point_status) {
+    typedef typename E::PF PF;
+    if (n_inputs + 1 != h->n_abc) { g_err = "the number of public inputs does not match gamma_abc_g1 (MalformedVerifyingKey)"; return GH_E_BAD_ARG; }
+    if (n && (!a || !a_fl || !b || !b_fl || !c || !c_fl || (n_inputs && !inputs) || !out_status)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    size_t ni = 0, by = 0;
+    if (mul_overflows(n, n_inputs, &ni) || mul_overflows(ni, 96 * 4, &by) || mul_overflows(n, 4096, &by)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    // compressed coordinates are untrusted data: what is wrong with them is a row's status, not an argument error
+    if (!compressed && (!all_below<PF>(a, 2 * n) || !all_below<PF>(b, 2 * E::BDEG * n) || !all_below<PF>(c, 2 * n))) {
+        g_err = "a proof coordinate is not below the modulus";
+        return GH_E_BAD_ARG;
+    }
+    if (n_inputs && !all_below<typename EngineHost<E>::PS>(inputs, ni)) { g_err = "a public input is not below the modulus"; return GH_E_BAD_ARG; }
+    if (n == 0) return GH_OK;
+    if (int rc = gh_rt::ensure_init()) return rc;
+    return run_verify_validated<E>(h, compressed, a, a_fl, b, b_fl, c, c_fl, inputs, n, n_inputs, out_status, out_point_status);
+}
+
 int api_last_timing(float* phase_ms, int max_phases, float* total_ms) { return g_tm.copy_out(phase_ms, max_phases, total_ms); }
 
 }  // namespace
@@ -610,7 +715,7 @@ int api_last_timing(float* phase_ms, int max_phases, float* total_ms) { return g
 #define GH_DEFINE_PAIRING_OPS(ENGINE, NAME)                                                                                 \
     namespace gh_rt {                                                                                                        \
     const PairingOps* NAME() {                                                                                               \
-        static const PairingOps ops = {&api_product<ENGINE>,        &api_vk_create<ENGINE>, &api_verify<ENGINE>,  &api_last_timing, \
+        static const PairingOps ops = {&api_product<ENGINE>,        &api_vk_create<ENGINE>, &api_verify<ENGINE>,  &api_last_timing, &api_verify_validated<ENGINE>, \
                                        &api_gm17_vk_create<ENGINE>, &api_gm17_verify<ENGINE>, &api_gm17_last_timing};           \
         return &ops;                                                                                                         \
     }                                                                                                                        \

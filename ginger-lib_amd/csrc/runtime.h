@@ -245,5 +245,13 @@ void fixed_table_destroy(FixedTable* t);          // null is fine
 int poseidon_field(const gh_poseidon* h, gh_field_t* out);                              // GH_E_BAD_HANDLE if h is none
 int poseidon_hash_dev_locked(gh_poseidon* h, const void* d_in, size_t n, size_t len, void* d_out);   // on g.stream, no sync
 void poseidon_trim_slab();                         // the release of a large slab every Poseidon entry point does on return
+// points.hip, on g.stream, no sync: d_code[i * stride] = the GH_POINT_* code of point i (membership: 0, 3 or 4; decompression: 0 .. 4,
+// d_xy / d_inf the points, failed rows zero).  points_validate_mark(0 / 1) brackets such launches with the two events
+// no Phases uses for a mark-to-mark time (g.ev[8], g.ev[9]); points_validate_finish(), after the caller's stream synchronise and before
+// anything else records an event, makes their distance the validate phase of gh_points_last_timing.
+int points_member_dev(gh_curve_t curve, const void* d_xy, const uint8_t* d_inf, size_t n, uint8_t* d_code, size_t stride);
+int points_decompress_dev(gh_curve_t curve, const void* d_x, const uint8_t* d_flags, size_t n, void* d_xy, uint8_t* d_inf, uint8_t* d_code, size_t stride);
+int points_validate_mark(int end);
+int points_validate_finish();
 
 }  // namespace gh_rt

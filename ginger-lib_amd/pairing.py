@@ -13,7 +13,8 @@ reference's names (algebra PairingEngine, proof-systems/src/groth16/verifier.rs)
 Field elements are rows of 12 u64 limbs of the Montgomery form x * 2^768 (numpy uint64).  A batch of G1 points is
 (xy: (m, 24), inf: (m,) uint8), of G2 points (xy: (m, 48), inf) with a coordinate as c0 || c1; an Fq4 value is a row of 48
 limbs in the order c0.c0, c0.c1, c1.c0, c1.c1 (Fp4::write).  Public inputs are Montgomery rows of MNT4-753 Fr.  Subgroup
-membership of the points is the caller's business (the reference checks it where a point is read).
+membership of the points is the caller's business (the reference checks it where a point is read): verify does not test it,
+.verify_checked and .verify_compressed (include/ginger_hip_points.h, module points) do, on the device.
 
 The engine is "mnt4753" unless a call says engine="mnt6753" (pairing="mnt6753" where a Parameters stream is read).  Over
 MNT6-753 a G2 coordinate is c0 || c1 || c2, so a G2 batch is (m, 72), an Fq6 value a row of 72 limbs in the order c0.c0,
@@ -154,6 +155,18 @@ class PreparedVerifyingKey(_handles.Handle):
         _check(_lib().gh_groth16_verify(self.handle, _ptr(axy), _ptr(ainf), _ptr(bxy), _ptr(binf), _ptr(cxy), _ptr(cinf),
                                         _ptr(x) if x.size else None, n, x.shape[1] // 12, _ptr(st)))
         return st
+
+    def verify_checked(self, a, b, c, inputs):
+        """verify after group_membership_test of A, B, C on the device -> (status (n,), point status (n, 3)); status 3: a
+        proof point is not a member of its group (its code, points.NOT_ON_CURVE or NOT_PRIME_ORDER, under A, B or C)"""
+        from . import points
+        return points._verify_validated(self, False, a, b, c, inputs)
+
+    def verify_compressed(self, a, b, c, inputs):
+        """the same for proofs in the wire form: a, b, c are (canonical x limbs, flags) as points.compress_limbs gives them,
+        decompressed and verified on the device; point status: the decompression code of A, B, C"""
+        from . import points
+        return points._verify_validated(self, True, a, b, c, inputs)
 
 
 def verify_proofs(pvk, proofs, inputs):

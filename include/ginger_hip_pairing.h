@@ -27,9 +27,11 @@
  * c1.c0 || c1.c1 || c1.c2 (72 words), the order of Fp6::write; public inputs are in the Montgomery form of MNT6-753 Fr.  Points at
  * infinity, rows with a point off its curve (status 2), subgroup membership and bad arguments are treated as for MNT4-753.
  *
- * Subgroup membership is the caller's job.  The reference checks it where a point is read (GroupAffine::read), not in the
- * pairing or the verifier; G1 has cofactor 1, so there it is the curve equation.  For a G2 point on the curve but outside the
- * subgroup of order r the value is unspecified; no input faults, hangs or loops, and the inverse of zero is taken as zero.
+ * Subgroup membership is the caller's job in this header.  The reference checks it where a point is read (GroupAffine::read),
+ * not in the pairing or the verifier; G1 has cofactor 1, so there it is the curve equation.  For a G2 point on the curve but
+ * outside the subgroup of order r the value is unspecified; no input faults, hangs or loops, and the inverse of zero is taken
+ * as zero.  ginger_hip_points.h does that job on the device: gh_group_membership, and gh_groth16_verify_checked /
+ * gh_groth16_verify_compressed, which validate A, B and C before they verify.
  */
 #ifndef GINGER_HIP_PAIRING_H
 #define GINGER_HIP_PAIRING_H
