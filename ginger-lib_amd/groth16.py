@@ -125,7 +125,7 @@ def _canon_rows_fast(vals):
     return np.frombuffer(b"".join(int(v).to_bytes(96, "little") for v in vals), dtype=np.uint64).reshape(-1, 12) if len(vals) else np.zeros((0, 12), np.uint64)
 
 
-def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, g2_xyz, vk_pairing_bytes=None):
+def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, g2_xyz, vk_pairing_bytes=None, r1cs=None):
     """generate_parameters (proof-systems/src/groth16/generator.rs:146-335) above the C ABI, for a constraint system given as
     linear combinations; the toxic waste, the evaluation point t (sample_element_outside_domain, :181) and the two
     generators (:225-226, `rand`) are arguments instead of RNG draws.  Returns (Parameters::write bytes, info).
@@ -134,7 +134,9 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, 
       * the five queries and gamma_abc_g1: FixedBaseMSM on the device with the reference's window rule (:233-311), followed
         by batch_normalization + into_affine (:318-335) -- gh_fixed_base_msm_affine, straight into the serialised form;
       * vk.alpha_g1_beta_g2 is a pairing value (:313) that the prover never reads -- filler bytes unless the caller supplies
-        them; pairing.parameters_with_pairing puts the real value into an MNT4-753 stream."""
+        them; pairing.parameters_with_pairing puts the real value into an MNT4-753 stream;
+      * r1cs (an r1cs.ResidentR1CS of the same lcs): the Lagrange coefficients stay on the device
+        (gh_lagrange_coefficients_dev) and gh_r1cs_instance_map_dev takes the place of the host loop -- same bytes."""
     r = _MODULUS[pairing]
     field = "mnt4753_fr" if pairing == "mnt4753" else "mnt6753_fr"
     g1c, g2c = pairing + "_g1", pairing + "_g2"
@@ -146,18 +148,11 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, 
     log_n = size.bit_length() - 1
     zt = (pow(t, size, r) - 1) % r                                               # evaluate_vanishing_polynomial
     tau = _mont_rows([t], r)[0]
-    u_rows = np.zeros((size, 12), dtype=np.uint64)
-    gl._check(gl.load_library().gh_lagrange_coefficients(gl.FIELDS[field], log_n, gl._ptr(tau), gl._ptr(u_rows)))
-    u = _ints_from_mont_rows(u_rows, r)
     nv = (num_inputs - 1) + num_aux
-    a, b, c = [0] * (nv + 1), [0] * (nv + 1), [0] * (nv + 1)
-    for i in range(num_inputs):
-        a[i] = u[n_con + i]
-    for rows, acc in ((at, a), (bt, b), (ct, c)):
-        for i, row in enumerate(rows):
-            ui = u[i]
-            for cf, ix in row:
-                acc[ix] = (acc[ix] + (ui if cf == 1 else ui * cf)) % r
+    if r1cs is not None:
+        a, b, c = _instance_map_on_device(gl, field, r1cs, (num_inputs, num_aux, n_con, log_n), tau)
+    else:
+        a, b, c = _instance_map_on_host(gl, field, lcs, size, tau, r)
     non_zero_a = sum(1 for v in a[:nv] if v)
     non_zero_b = sum(1 for v in b[:nv] if v)
     gi, di = pow(gamma, -1, r), pow(delta, -1, r)
@@ -215,6 +210,50 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, 
     info = {"num_inputs": num_inputs, "log_n": log_n, "qap": (a, b, c, l, zt), "g1_window": g1_window, "g2_window": g2_window,
             "non_zero": (non_zero_a, non_zero_b), "fixed_base": stats}
     return bytes(blob), info
+
+
+def _instance_map_on_host(gl, field, lcs, size, tau, r):
+    """instance_map_with_evaluation (r1cs_to_qap.rs:14-69): the Lagrange coefficients from the device, the loops on host integers"""
+    num_inputs, num_aux, at, bt, ct = lcs
+    n_con, log_n = len(at), size.bit_length() - 1
+    u_rows = np.zeros((size, 12), dtype=np.uint64)
+    gl._check(gl.load_library().gh_lagrange_coefficients(gl.FIELDS[field], log_n, gl._ptr(tau), gl._ptr(u_rows)))
+    u = _ints_from_mont_rows(u_rows, r)
+    nv = (num_inputs - 1) + num_aux
+    a, b, c = [0] * (nv + 1), [0] * (nv + 1), [0] * (nv + 1)
+    for i in range(num_inputs):
+        a[i] = u[n_con + i]
+    for rows, acc in ((at, a), (bt, b), (ct, c)):
+        for i, row in enumerate(rows):
+            ui = u[i]
+            for cf, ix in row:
+                acc[ix] = (acc[ix] + (ui if cf == 1 else ui * cf)) % r
+    return a, b, c
+
+
+def _instance_map_on_device(gl, field, r1cs, shape, tau):
+    """the same with u left on the device (gh_lagrange_coefficients_dev) and the three transposed products there
+    (gh_r1cs_instance_map_dev); into_repr on the device as well, so the host only reads limbs -> a, b, c as integers"""
+    num_inputs, num_aux, n_con, log_n = shape
+    if (r1cs.num_inputs, r1cs.num_aux, r1cs.num_constraints, r1cs.log_n) != shape:
+        raise ValueError("the resident constraint system is not the one of lcs")
+    nv1 = num_inputs + num_aux
+    d_u = gl.DeviceBuffer(96 << log_n)
+    outs = [gl.DeviceBuffer(nv1 * 96) for _ in range(3)]
+    try:
+        gl._check(gl.load_library().gh_lagrange_coefficients_dev(gl.FIELDS[field], log_n, gl._ptr(tau), d_u.ptr))
+        r1cs.instance_map_dev(d_u, *outs)
+        one_plain = np.zeros(12, dtype=np.uint64)
+        one_plain[0] = 1
+        res = []
+        for o in outs:
+            gl._check(gl.load_library().gh_vec_scale_dev(gl.FIELDS[field], o.ptr, gl._ptr(one_plain), nv1))
+            raw = o.download()[:nv1 * 12].tobytes()
+            res.append([int.from_bytes(raw[96 * i:96 * i + 96], "little") for i in range(nv1)])
+        return tuple(res)
+    finally:
+        for buf in [d_u] + outs:
+            buf.free()
 
 
 def _mont_rows(vals, modulus):
@@ -394,11 +433,16 @@ class ResidentProvingKey:
         Python integers (benchmark_circuit_rows); d1, d2, d3, r, s integers.  Returns Proof::write bytes (mod.rs:35-42)."""
         return self.prove_prepared(self.prepare_rows(circuit_rows, d1, d2, d3), r, s)
 
-    def create_proof_msms(self, input_assignment, aux_assignment, h_input_assignment, h_aux_assignment, r, s, h_dev=None):
+    def create_proof_msms(self, input_assignment, aux_assignment, h_input_assignment, h_aux_assignment, r, s, h_dev=None, scalars_dev=None):
         """All arguments are canonical 12-u64 scalars (rows).  Returns (A, B, C) as (xy, is_infinity) pairs:
         exactly Proof { a: g_a.into_affine(), b: g2_b.into_affine(), c: g_c.into_affine() } (prover.rs:340-344).
         h_dev = (DeviceBuffer, rows): the coefficients of h already on the device as canonical scalars (the output
-        of gh_witness_map_dev after into_repr); h_input_assignment / h_aux_assignment are then ignored."""
+        of gh_witness_map_dev after into_repr); h_input_assignment / h_aux_assignment are then ignored.
+        scalars_dev = (DeviceBuffer of at least n + 4 rows, n), with h_dev: input || aux already on the device as canonical
+        scalars in the buffer's first n rows (gh_r1cs_witness_map_dev's d_scalars); the four rows after them are written
+        here, the buffer stays the caller's, and input_assignment / aux_assignment are ignored."""
+        if scalars_dev is not None:
+            return self._msms_from_device(scalars_dev, h_dev, r, s)
         gl, pk, ni = self.gl, self.pk, self.num_inputs
         g1, g2 = self.g1, self.g2
         add, mul = gl.proj_add, gl.proj_mul
@@ -463,3 +507,79 @@ class ResidentProvingKey:
         g_c = add(g1, g_c, l_acc)
         g_c = add(g1, g_c, h_acc)
         return gl.proj_to_affine(g1, g_a), gl.proj_to_affine(g2, g2_b), gl.proj_to_affine(g1, g_c)
+
+    def _msms_from_device(self, scalars_dev, h_dev, r, s):
+        """create_proof_msms over input || aux already on the device: the same five MSMs over the same scalar vector
+        input || aux || 1 || 1 || r || s, of which only the last four rows come from the host; then C as there"""
+        import ctypes
+        gl, pk, ni = self.gl, self.pk, self.num_inputs
+        g1, g2 = self.g1, self.g2
+        add, mul = gl.proj_add, gl.proj_mul
+        d_r, n = scalars_dev[0], int(scalars_dev[1])
+        d_h, n_h = h_dev[0], int(h_dev[1])
+        n_var = self.keys["a"].n - 4
+        if n != n_var or self.keys["b1"].n - 4 != n_var or self.keys["b2"].n - 4 != n_var or d_r.nbytes < (n + 4) * 96:
+            raise ValueError("the scalar vector must hold one row per variable of the key's queries, and room for four more")
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(1, 12)
+        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(1, 12)
+        one = np.zeros((1, 12), dtype=np.uint64)
+        one[0, 0] = 1
+        tail = np.ascontiguousarray(np.concatenate([one, one, r, s]), dtype=np.uint64)
+        gl._check(gl.load_library().gh_dev_upload(ctypes.c_void_p(d_r.ptr.value + n * 96), gl._ptr(tail), tail.nbytes))
+
+        class _View:                          # aux_assignment inside d_r
+            ptr = ctypes.c_void_p(d_r.ptr.value + (ni - 1) * 96)
+        k = self.keys
+        g_a, g1_b, h_acc, l_acc = gl.msm_batch_dev([
+            (k["a"], d_r, n + 4), (k["b1"], d_r, n + 4), (k["h"], d_h, n_h), (k["l"], _View, n - (ni - 1))])
+        g2_b = k["b2"].msm_dev(d_r, n + 4)
+        delta = np.zeros(36, dtype=np.uint64)
+        delta[:24] = np.asarray(pk["delta_g1"], dtype=np.uint64).ravel()
+        delta[24:] = gl.field_one(g1)
+        g_c = add(g1, mul(g1, g_a, s), mul(g1, g1_b, r))
+        g_c = add(g1, g_c, gl.proj_neg(g1, mul(g1, mul(g1, delta, r), s)))
+        g_c = add(g1, g_c, l_acc)
+        g_c = add(g1, g_c, h_acc)
+        return gl.proj_to_affine(g1, g_a), gl.proj_to_affine(g2, g2_b), gl.proj_to_affine(g1, g_c)
+
+    def create_proof_r1cs(self, r1cs, assignment, d1, d2, d3, r, s, timing=None):
+        """create_proof (prover.rs:201-345) over resident constraint matrices (r1cs.ResidentR1CS): the assignment goes to the
+        device once, as Montgomery rows ((n, 12) uint64, or Python integers that are converted first);
+        gh_r1cs_witness_map_dev evaluates the constraint rows there, runs the witness map and leaves input || aux as
+        canonical scalars for the five MSMs.  Returns Proof::write bytes: those of create_proof on the same circuit.
+        timing (a dict) receives wall-clock ms per stage."""
+        import time
+        gl, pairing = self.gl, self.pairing
+        modulus = _MODULUS[pairing]
+        field = "mnt4753_fr" if pairing == "mnt4753" else "mnt6753_fr"
+        if r1cs.num_inputs != self.num_inputs:
+            raise ValueError("the constraint system and the key disagree on the number of inputs")
+        z = assignment if isinstance(assignment, np.ndarray) else _mont_rows(list(assignment), modulus)
+        z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 12)
+        nv, size = r1cs.num_variables, r1cs.size
+        if len(z) != nv:
+            raise ValueError("the assignment must have one row per variable")
+        dd = _mont_rows([d1, d2, d3], modulus)
+        lib = gl.load_library()
+        t0 = time.perf_counter()
+        d_z, d_h, d_s = gl.DeviceBuffer(nv * 96), gl.DeviceBuffer(size * 96 + 96), gl.DeviceBuffer((nv + 3) * 96)
+        try:
+            d_z.upload(z)
+            lib.gh_dev_sync()
+            t1 = time.perf_counter()
+            r1cs.witness_map_dev(d_z, dd, d_h, d_s)
+            one_plain = np.zeros(12, dtype=np.uint64)
+            one_plain[0] = 1
+            gl._check(lib.gh_vec_scale_dev(gl.FIELDS[field], d_h.ptr, gl._ptr(one_plain), size + 1))          # into_repr of h (:256-267)
+            lib.gh_dev_sync()
+            t2 = time.perf_counter()
+            self.pk = dict(self.pk, delta_g1=self.pk_delta_g1)
+            A_, B_, C_ = self.create_proof_msms(None, None, None, None, _canon_rows([r])[0], _canon_rows([s])[0],
+                                                h_dev=(d_h, self.keys["h"].n), scalars_dev=(d_s, nv - 1))
+            t3 = time.perf_counter()
+        finally:
+            for buf in (d_z, d_h, d_s):
+                buf.free()
+        if timing is not None:
+            timing.update(assignment_upload_ms=(t1 - t0) * 1e3, witness_map_ms=(t2 - t1) * 1e3, msm_stage_ms=(t3 - t2) * 1e3)
+        return affine_to_wire(pairing, "g1", *A_) + affine_to_wire(pairing, "g2", *B_) + affine_to_wire(pairing, "g1", *C_)

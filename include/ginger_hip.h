@@ -255,8 +255,10 @@ int gh_vec_scale(gh_field_t field, uint64_t* a, const uint64_t* scalar12, size_t
 
 /* QAP witness map, device resident: the transform part of R1CStoQAP::witness_map
  * (proof-systems/src/groth16/r1cs_to_qap.rs:121-166).  d_a, d_b, d_c hold the 2^log_n evaluations
- * of the A, B, C rows at the assignment (:105-119, :141-151; computed by the caller -- circuit
- * synthesis is CPU scalar code and out of scope); they are overwritten.  d_h receives the
+ * of the A, B, C rows at the assignment (:105-119, :141-151): by the caller, or on the device over
+ * resident matrices by gh_r1cs_evaluate_dev (ginger_hip_r1cs.h; gh_r1cs_witness_map_dev is the two
+ * calls in one).  Only producing the assignment -- circuit synthesis, CPU scalar code -- is out of
+ * scope.  The three vectors are overwritten.  d_h receives the
  * 2^log_n + 1 coefficients of h:
  *   a = coset_fft(ifft(a)); b = coset_fft(ifft(b)); ab = a .* b; c = coset_fft(ifft(c));
  *   ab = (ab - c) * (g^N - 1)^-1; ab = coset_ifft(ab);
