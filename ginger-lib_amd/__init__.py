@@ -263,6 +263,17 @@ def kernel_resources(which):
     return {"scratch_bytes_per_lane": int(a.value), "registers": int(b.value), "lds_bytes": int(c.value)}
 
 
+def acc_stamps(max_records=1 << 16):
+    """records of the last stamped G1 accumulation (gh_acc_stamps_read, a diagnostic entry outside the header; csrc/ginger_hip.hip):
+    uint32 array (n, 16)"""
+    buf = np.zeros((max_records, 16), dtype=np.uint32)
+    n = ctypes.c_uint32(0)
+    fn = load_library().gh_acc_stamps_read
+    fn.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
+    _check(fn(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), buf.size, ctypes.byref(n)))
+    return buf[:int(n.value)]
+
+
 def bases_key_id(curve, bases, infinity=None):
     """the four 64-bit lanes of a key's identity (gh_bases_key_id): [0:2] select the cache entry, [2:4] verify it; host-only"""
     deg = CURVE_DEG[curve]

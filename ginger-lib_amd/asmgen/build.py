@@ -24,6 +24,9 @@ def programs():
     progs = [
         g1_xyzz.build("gh_asm_acc_g1_p4", P4, R % P4),
         g1_xyzz.build("gh_asm_acc_g1_p6", P6, R % P6),
+        # the same update as one-wave workgroups that draw tiles of 64 tasks from a counter (GH_ACC_PERSIST=1)
+        g1_xyzz.build("gh_asm_acc_g1_p4_pw", P4, R % P4, persistent=True),
+        g1_xyzz.build("gh_asm_acc_g1_p6_pw", P6, R % P6, persistent=True),
         # lean level 1 of the G1 bucket reduction (the common path; msm_reduce_kernels.h keeps the doubling detour)
         g1_reduce.build("gh_asm_red_g1_p4", P4, R % P4),
         g1_reduce.build("gh_asm_red_g1_p6", P6, R % P6),
@@ -44,6 +47,9 @@ def programs():
     progs.append(microbench.build("gh_asm_mb_mulpair", P4))
     if os.environ.get("GH_ASM_DEBUG"):          # stage markers for tools/asm_g2_check.py (not shipped)
         progs.append(g2_rounds.build("gh_asm_aff_f2_bwd_r0_dbg", c2, False, True, debug=True))
+        for tag, prime in (("p4", P4), ("p6", P6)):     # stamped accumulation kernels for tools/acc_timeline.py (not shipped)
+            progs.append(g1_xyzz.build("gh_asm_acc_g1_%s_dbg" % tag, prime, R % prime, debug=True))
+            progs.append(g1_xyzz.build("gh_asm_acc_g1_%s_pw_dbg" % tag, prime, R % prime, persistent=True, debug=True))
     if os.environ.get("GH_ASM_VARIANTS"):      # A/B variants of the gather for tools/asm_mb/acc_run.hip (not shipped)
         progs += [g1_xyzz.build("gh_asm_acc_g1_p4_s1", P4, R % P4, split=1),
                   g1_xyzz.build("gh_asm_acc_g1_p4_s2", P4, R % P4, split=2),

@@ -12,6 +12,18 @@ Register plan (256 VGPRs = two waves per SIMD, 0 bytes of scratch):
   X, V = sigma Y and (between two steps) R^2 of the running sum are parked in LDS, word-major: park[3][26][256].
 The prime, -p, the Montgomery constant and the limb mask live in SGPRs.
 
+Two launch forms of the same update (nothing between L_LOOP and L_ADV differs):
+  block (default)   a workgroup of four waves takes the 256 tasks its id names and ends; the grid is one block per 256 tasks.
+  persistent=True   a workgroup is ONE wave (park[3][26][64], 19 968 B of LDS: eight per CU hold what two blocks hold) that
+                    loads the constants once and then takes tiles of 64 consecutive tasks from a 32-bit counter in global memory
+                    (one lane, a returning global_atomic_add; relaxed: nothing is handed over through the counter) until the
+                    counter has passed n_tiles, or until it has taken `budget` tiles (0: no limit; the host launches at least
+                    n_tiles / budget waves).  No wave waits for another: any grid size and any residency give the same
+                    buckets, and a wave that starts after the counter ran out ends having stored nothing.  The counter must
+                    be 0 when the launch starts (msm_kernels.h msm_acc_tasks_kernel writes it).
+debug=True adds stamps (shader clock, constant-rate clock, hardware id) per tile / per wave of a block into a side buffer;
+the shipped kernels hold none (build.py: GH_ASM_DEBUG).
+
 Order of the products (each one chain of mads, pairs back to back -- `seq`; the subtractions of a pair stay interleaved):
   U2, S2  P, W  PP, RR  park RR  PPP, ZZ3  Q, ZZZ3  X3, T  dual(W T + V PPP)
 """
@@ -20,9 +32,8 @@ from .field import FieldGen, Chain, interleave, run, NL, LM
 
 AFF_BYTES = 2 * NL * 4          # 208
 PROJ_WORDS = 3 * NL             # 78
-PARK_STRIDE = 256 * 4           # bytes between consecutive words of a parked element
 PARK_X, PARK_V, PARK_RR = 0, 1, 2
-LDS_BYTES = 3 * NL * PARK_STRIDE
+LDS_BYTES = 3 * NL * 256 * 4    # block form; the persistent form parks 64 lanes: a quarter
 
 # SGPR map
 S_KARG = S(0, 2)
@@ -40,6 +51,13 @@ S_SAVE = S(86, 2)
 S_DETOUR = S(88, 2)
 S_T2 = S(90, 2)
 S_ZERO = S(92, 2)
+# persistent form: the tile counter's address, the number of tiles, the tile in hand
+S_CTR = S(96, 2)
+S_NTILES = S(98)
+S_TILE = S(99)
+S_BUDGET = S(3)                 # tiles this wave may still take (the launch's budget; 0 = no limit)
+S_STAMPS = S(100, 2)            # debug form: the stamp records
+STAMP_BYTES = 64                # a record: clk0, rt0 | clk1, rt1 | hw id, xcc id, index, live lanes (low word) | unused
 
 V_TID, V_LDS = V(0), V(1)
 V_CUR = V(2, 2)
@@ -55,6 +73,8 @@ V_LDS2 = V(24)
 V_ENEXT = V(25)
 V_TOUCH = V(26)
 V_NADDR = V(28, 2)
+# debug form (never together with prefetch): the start stamps, the end stamps, the ids, the record's offset
+V_ST0, V_ST1, V_STID, V_STOFF = V(30, 4), V(34, 4), V(26, 4), V(38)
 
 
 def slot(i):
@@ -73,13 +93,23 @@ def seq(*gens):
 E = [slot(i) for i in range(8)]
 
 
-def build(name, p, one_mont, prefetch=False, split=4):
-    """p: the base prime; one_mont = 2^754 mod p (internal Montgomery one)."""
+def build(name, p, one_mont, prefetch=False, split=4, persistent=False, debug=False):
+    """p: the base prime; one_mont = 2^754 mod p (internal Montgomery one).
+    Arguments: bases, sorted, tasks, salts, n_tasks; persistent: + n_tiles, counter, budget; debug: + stamps (last)."""
+    assert not (debug and prefetch)
     g = Prog(name)
-    g.lds_bytes = LDS_BYTES
+    lanes = 64 if persistent else 256
+    park_stride = lanes * 4                                         # bytes between consecutive words of a parked element
+    g.lds_bytes = 3 * NL * park_stride
     for _ in range(4):
         g.add_arg(8, "ptr")
     g.add_arg(4, "val")
+    if persistent:
+        g.add_arg(4, "val")
+        off_ctr = g.add_arg(8, "ptr")
+        off_budget = g.add_arg(4, "val")
+    if debug:
+        off_stamps = g.add_arg(8, "ptr")
     f = FieldGen(g, p, S_P, S_NP, S_INV, S_LM)
     chA = Chain(V(248, 2), V(252), V(253), S(14, 2), S(16, 2))
     chB = Chain(V(250, 2), V(254), V(255), S(18, 2), S(22, 2))
@@ -87,8 +117,8 @@ def build(name, p, one_mont, prefetch=False, split=4):
     def park_addr(which, w):
         # DS offsets are 16 bits: the third parked element is addressed from a second base register
         if which < 2:
-            return V_LDS, (which * NL + w) * PARK_STRIDE
-        return V_LDS2, ((which - 2) * NL + w) * PARK_STRIDE
+            return V_LDS, (which * NL + w) * park_stride
+        return V_LDS2, ((which - 2) * NL + w) * park_stride
 
     def park_put(which, sl):
         for w in range(NL):
@@ -104,37 +134,102 @@ def build(name, p, one_mont, prefetch=False, split=4):
         g.uniq(s) for s in ("loop", "init", "init_ret", "detour", "det_ret", "adv", "done", "start"))
     S_JMP = S(94, 2)                                                # scratch of the long jumps
 
+    def stamp(dst):
+        """dst[0:2] = shader clock, dst[2:4] = constant-rate clock (S_T0 / S_T1 are free outside the loop)"""
+        g.s_memtime(S_T0)
+        g.s_memrealtime(S_T1)
+        g.s_waitcnt(lgkmcnt=0)
+        g.v_mov_b32(dst.sub(0), S_T0.lo()); g.v_mov_b32(dst.sub(1), S_T0.hi())
+        g.v_mov_b32(dst.sub(2), S_T1.lo()); g.v_mov_b32(dst.sub(3), S_T1.hi())
+
+    def stamp_store():
+        """the record of this tile / wave, by every live lane alike (ordinary vector stores into the side buffer)"""
+        stamp(V_ST1)
+        g.s_getreg_b32(S_T0.lo(), "hwreg(HW_REG_HW_ID)")
+        g.s_getreg_b32(S_T0.hi(), "hwreg(HW_REG_XCC_ID)")
+        g.v_mov_b32(V_STID.sub(0), S_T0.lo()); g.v_mov_b32(V_STID.sub(1), S_T0.hi())
+        g.v_mov_b32(V_STID.sub(3), S_LAUNCH.lo())
+        for k, r in enumerate((V_ST0, V_ST1, V_STID)):
+            g.global_store_dwordx4(V_STOFF, r, S_STAMPS, offset=16 * k)
+
+    def wave_constants():
+        g.v_mov_b32(V_BASES.lo(), S_BASES.lo()); g.v_mov_b32(V_BASES.hi(), S_BASES.hi())
+        g.v_mov_b32(V_SALTS.lo(), S_SALTS.lo()); g.v_mov_b32(V_SALTS.hi(), S_SALTS.hi())
+
+    def reset_task(v_task, with_constants=False):
+        """the task row of v_task and the state of an empty running sum; ends in front of L_LOOP"""
+        g.v_lshlrev_b32(V_T[1], 4, v_task)
+        g.global_load_dwordx4(V(16, 4), V_T[1], S_TASKS)            # beg, cnt, dst
+        if with_constants:
+            wave_constants()
+        g.v_mov_b32(V_CUR.lo(), S_SORTED.lo()); g.v_mov_b32(V_CUR.hi(), S_SORTED.hi())
+        g.v_mov_b32(V_PHASE, 0); g.v_mov_b32(V_SNEG, 0); g.v_mov_b32(V_SALT, 0)
+        for w in range(NL):                                         # ZZ = ZZZ = 0: the running sum is the point at infinity
+            g.v_mov_b32(E[0].sub(w), 0)
+            g.v_mov_b32(E[1].sub(w), 0)
+        g.s_waitcnt(vmcnt=0)
+        g.v_mov_b32(V_LEFT, V(17))
+        g.v_mov_b32(V_DST.lo(), V(18)); g.v_mov_b32(V_DST.hi(), V(19))
+        g.v_mad_u64_u32(V_CUR, chA.sdum, V(16), 4, V_CUR)
+        g.v_lshl_add_u32(V_GUARD, V_LEFT, 2, 8)                     # at most 4 cnt + 8 iterations (the C++ kernel's guard)
+
     # ------------------------------------------------------------ prologue
+    L_FETCH, L_EXIT = g.uniq("fetch"), g.uniq("exit")
+    if debug and not persistent:
+        stamp(V_ST0)
     g.s_load_dwordx8(S(4, 8), S_KARG, 0)
     g.s_load_dword(S_NTASKS, S_KARG, 32)
+    if persistent:
+        g.s_load_dword(S_NTILES, S_KARG, 36)
+        g.s_load_dwordx2(S_CTR, S_KARG, off_ctr)
+        g.s_load_dword(S_BUDGET, S_KARG, off_budget)
+    if debug:
+        g.s_load_dwordx2(S_STAMPS, S_KARG, off_stamps)
     f.load_constants()
     g.s_mov_b32(S_208, AFF_BYTES)
     g.v_lshlrev_b32(V_LDS, 2, V_TID)
-    g.v_add_u32(V_LDS2, 2 * NL * PARK_STRIDE, V_LDS)
-    g.v_lshl_or_b32(V_T[0], S_WG, 8, V_TID)
-    g.s_waitcnt(lgkmcnt=0)
-    g.v_cmp_gt_u32(VCC, S_NTASKS, V_T[0])
-    g.s_and_saveexec_b64(S_LAUNCH, VCC)
-    g.s_cbranch_execnz(L_START)
-    g.s_endpgm()
-    g.label(L_START)
-    g.s_mov_b64(S_LAUNCH, EXEC)
-    g.v_lshlrev_b32(V_T[1], 4, V_T[0])
-    g.global_load_dwordx4(V(16, 4), V_T[1], S_TASKS)                # beg, cnt, dst
-    g.v_mov_b32(V_BASES.lo(), S_BASES.lo()); g.v_mov_b32(V_BASES.hi(), S_BASES.hi())
-    g.v_mov_b32(V_SALTS.lo(), S_SALTS.lo()); g.v_mov_b32(V_SALTS.hi(), S_SALTS.hi())
-    g.v_mov_b32(V_CUR.lo(), S_SORTED.lo()); g.v_mov_b32(V_CUR.hi(), S_SORTED.hi())
-    g.v_mov_b32(V_PHASE, 0); g.v_mov_b32(V_SNEG, 0); g.v_mov_b32(V_SALT, 0)
-    for w in range(NL):                                             # ZZ = ZZZ = 0: the running sum is the point at infinity
-        g.v_mov_b32(E[0].sub(w), 0)
-        g.v_mov_b32(E[1].sub(w), 0)
-    g.s_waitcnt(vmcnt=0)
-    g.v_mov_b32(V_LEFT, V(17))
-    g.v_mov_b32(V_DST.lo(), V(18)); g.v_mov_b32(V_DST.hi(), V(19))
-    g.v_mad_u64_u32(V_CUR, chA.sdum, V(16), 4, V_CUR)
-    g.v_lshl_add_u32(V_GUARD, V_LEFT, 2, 8)                         # at most 4 cnt + 8 iterations (the C++ kernel's guard)
-
-    g.s_branch(L_LOOP)
+    g.v_add_u32(V_LDS2, 2 * NL * park_stride, V_LDS)
+    if not persistent:
+        g.v_lshl_or_b32(V_T[0], S_WG, 8, V_TID)
+        g.s_waitcnt(lgkmcnt=0)
+        g.v_cmp_gt_u32(VCC, S_NTASKS, V_T[0])
+        g.s_and_saveexec_b64(S_LAUNCH, VCC)
+        g.s_cbranch_execnz(L_START)
+        g.s_endpgm()
+        g.label(L_START)
+        g.s_mov_b64(S_LAUNCH, EXEC)
+        if debug:                                                   # one record per wave of the block: 4 wg + wave
+            g.v_lshrrev_b32(V_STID.sub(2), 6, V_T[0])
+            g.v_lshlrev_b32(V_STOFF, 6, V_STID.sub(2))
+        reset_task(V_T[0], with_constants=True)
+        g.s_branch(L_LOOP)
+    else:
+        g.s_waitcnt(lgkmcnt=0)
+        wave_constants()
+        # -------------------------------------------------------- tile loop: one lane draws the next tile
+        g.label(L_FETCH)
+        g.s_mov_b64(EXEC, 1)
+        g.v_mov_b32(V_T[0], 1)
+        g.v_mov_b32(V_T[1], 0)
+        g.global_atomic_add(V_T[2], V_T[1], V_T[0], S_CTR, sc0=True)   # sc0: the count before the add
+        g.s_waitcnt(vmcnt=0)                                        # (also the stores of the tile before)
+        g.v_readfirstlane_b32(S_TILE, V_T[2])
+        g.s_mov_b64(EXEC, -1)
+        g.s_cmp_ge_u32(S_TILE, S_NTILES)
+        g.s_cbranch_scc1(L_EXIT)
+        g.v_lshl_or_b32(V_T[0], S_TILE, 6, V_TID)
+        g.v_cmp_gt_u32(VCC, S_NTASKS, V_T[0])                       # the last tile may be ragged
+        g.s_and_b64(EXEC, EXEC, VCC)
+        g.s_cbranch_execz(L_FETCH)
+        g.s_mov_b64(S_LAUNCH, EXEC)
+        if debug:                                                   # one record per tile
+            stamp(V_ST0)
+            g.v_mov_b32(V_STID.sub(2), S_TILE)
+            g.v_lshlrev_b32(V_STOFF, 6, V_STID.sub(2))
+        reset_task(V_T[0])
+        g.s_branch(L_LOOP)
+        g.label(L_EXIT)
+        g.s_endpgm()
 
     # ------------------------------------------------------------ epilogue: (X ZZZ : Y ZZ : ZZ ZZZ), infinity -> (0, 1, 0)
     g.label(L_DONE)
@@ -162,7 +257,17 @@ def build(name, p, one_mont, prefetch=False, split=4):
     g.s_mov_b64(EXEC, S_SAVE)
     for j in range(PROJ_WORDS // 2):                                # E4, E5, E6 are contiguous: Proj = x[26] y[26] z[26]
         g.global_store_dwordx2(V_DST, V(E[4].idx + 2 * j, 2), OFF, offset=8 * j)
-    g.s_endpgm()
+    if debug:
+        stamp_store()
+    if persistent:
+        # a wave that has used up its budget ends, so that the dispatcher can hand its slot to whatever waits -- the next
+        # workgroup of this grid, or a kernel of another stream.  A budget of 0 wraps: no limit.
+        g.s_sub_u32(S_BUDGET, S_BUDGET, 1)
+        g.s_cmp_eq_u32(S_BUDGET, 0)
+        g.s_cbranch_scc0(L_FETCH)
+        g.s_endpgm()
+    else:
+        g.s_endpgm()
 
     # ------------------------------------------------------------ loop head
     g.label(L_LOOP)

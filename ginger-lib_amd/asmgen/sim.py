@@ -913,3 +913,17 @@ def _gatomic_add(w, i):
         old = int(w.mem.load(int(addrs[l]), 1)[0])
         w.mem.store(int(addrs[l]), [(old + int(vals[l])) & M32])
         w.V[w.ridx(d)][l] = old
+
+
+# ------------------------------------------------------------------ clocks and hardware ids (the stamps of g1_xyzz.py debug=True):
+# a counter that advances with the executed instructions, ids of wave 0 -- enough to check where the stamps go
+@op("s_memtime", "s_memrealtime")
+def _s_memtime(w, i):
+    d, = i.args
+    w.wr_smask(d, w.executed)
+
+
+@op("s_getreg_b32")
+def _s_getreg(w, i):
+    d, _ = i.args
+    w.ws(d, 0)

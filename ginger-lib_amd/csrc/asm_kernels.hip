@@ -26,6 +26,13 @@ struct State {
     bool tried = false;
     hipModule_t mod = nullptr;
     hipFunction_t acc_g1[2] = {nullptr, nullptr};   // [0]: p4 (MNT4-753 G1), [1]: p6 (MNT6-753 G1)
+    hipFunction_t acc_g1_pw[2] = {nullptr, nullptr};      // the persistent form
+    hipFunction_t acc_g1_dbg[2][2] = {};            // [persistent][prime]: the stamped variants; only in a GH_ASM_DEBUG code object
+    // records of the stamped launches, two buffers in turn: under GH_ACC_ALT=1 a launch is prepared while its predecessor runs
+    uint32_t* stamps[2] = {nullptr, nullptr};
+    size_t stamps_cap[2] = {0, 0};
+    uint32_t stamps_n = 0;
+    int stamps_last = 1;
     hipFunction_t red_g1[2] = {nullptr, nullptr};   // [0]: p4, [1]: p6
     hipFunction_t aff[4][2][2] = {};                // [kind: f2, f3, f1p4, f1p6][fwd][r0]
     hipFunction_t mb_mulpair = nullptr;
@@ -70,6 +77,27 @@ int load_locked() {
             return GH_E_HIP;
         }
     }
+    static const char* pw_names[2] = {"gh_asm_acc_g1_p4_pw", "gh_asm_acc_g1_p6_pw"};
+    for (int i = 0; i < 2; i++) {
+        e = hipModuleGetFunction(&s.acc_g1_pw[i], m, pw_names[i]);
+        if (e != hipSuccess) {
+            g_err = std::string("hipModuleGetFunction(") + pw_names[i] + ") failed: " + hipGetErrorString(e);
+            hipModuleUnload(m);
+            return GH_E_HIP;
+        }
+    }
+    if (getenv("GH_ACC_STAMPS")) {      // absent from the shipped code object: asking for them without a diagnostic build is an error
+        static const char* dbg_names[2][2] = {{"gh_asm_acc_g1_p4_dbg", "gh_asm_acc_g1_p6_dbg"}, {"gh_asm_acc_g1_p4_pw_dbg", "gh_asm_acc_g1_p6_pw_dbg"}};
+        for (int pw = 0; pw < 2; pw++)
+            for (int i = 0; i < 2; i++) {
+                e = hipModuleGetFunction(&s.acc_g1_dbg[pw][i], m, dbg_names[pw][i]);
+                if (e != hipSuccess) {
+                    g_err = std::string("GH_ACC_STAMPS: ") + dbg_names[pw][i] + " is not in the code object (build it with GH_ASM_DEBUG=1): " + hipGetErrorString(e);
+                    hipModuleUnload(m);
+                    return GH_E_HIP;
+                }
+            }
+    }
     static const char* red_names[2] = {"gh_asm_red_g1_p4", "gh_asm_red_g1_p6"};
     for (int i = 0; i < 2; i++) {
         e = hipModuleGetFunction(&s.red_g1[i], m, red_names[i]);
@@ -112,6 +140,7 @@ int load_locked() {
     s.mod = m;
     g.at_shutdown.push_back([] {
         if (s.mod) hipModuleUnload(s.mod);
+        for (uint32_t* b : s.stamps) if (b) (void)hipFree(b);
         s = State();
     });
     return GH_OK;
@@ -123,10 +152,65 @@ bool enabled() {
     return on;
 }
 
+// the side buffer of a stamped launch: `records` records of 64 bytes, zeroed on the launch's stream
+static int stamps_prepare(uint32_t records, hipStream_t st, uint32_t** out) {
+    const size_t bytes = (size_t)records * 64;
+    const int b = s.stamps_last ^ 1;
+    if (s.stamps_cap[b] < bytes) {
+        if (s.stamps[b]) HIPCHK(hipFree(s.stamps[b]));
+        s.stamps[b] = nullptr; s.stamps_cap[b] = 0;
+        HIPCHK(hipMalloc((void**)&s.stamps[b], bytes));
+        s.stamps_cap[b] = bytes;
+    }
+    HIPCHK(hipMemsetAsync(s.stamps[b], 0, bytes, st));
+    s.stamps_n = records;
+    s.stamps_last = b;
+    *out = s.stamps[b];
+    return GH_OK;
+}
+
 int acc_g1_launch(int prime, const void* bases, const uint32_t* sorted, const AccTask* tasks, const void* salts,
-                  uint32_t n_tasks, hipStream_t st) {
+                  uint32_t n_tasks, uint32_t* tile_counter, hipStream_t st) {
     if (n_tasks == 0) return GH_OK;
     if (int rc = load_locked()) return rc;
+    const gh_rt::MsmKnobs& knobs = gh_rt::msm_knobs();
+    static const bool stamped = getenv("GH_ACC_STAMPS") != nullptr;
+    const int pi = prime == 6 ? 1 : 0;
+    if (knobs.acc_persist) {
+        const uint32_t n_tiles = (n_tasks + 63) / 64;
+        // eight one-wave workgroups per CU hold the LDS and the registers of two blocks: every wave slot the block form fills
+        uint32_t waves = knobs.acc_waves > 0 ? (uint32_t)knobs.acc_waves : (uint32_t)g.num_cus * 8u;
+        if (waves > n_tiles) waves = n_tiles;
+        // GH_ACC_TILES=K: a wave ends after K tiles, so the grid must hold tiles / K waves; the dispatcher places them as slots
+        // fall free, and kernels of other streams get a slot between two of them.  A grid that GH_ACC_WAVES made too small for
+        // the budget runs without one: whatever the knobs, every tile is taken.
+        uint32_t budget = knobs.acc_tiles > 0 ? (uint32_t)knobs.acc_tiles : 0u;
+        if (budget) {
+            const uint32_t need = (n_tiles + budget - 1) / budget;
+            if (knobs.acc_waves <= 0) waves = need;
+            else if (waves < need) budget = 0;
+        }
+        struct {
+            const void* bases;
+            const void* sorted;
+            const void* tasks;
+            const void* salts;
+            uint32_t n_tasks, n_tiles;
+            uint32_t* counter;
+            uint32_t budget, pad;
+            uint32_t* stamps;
+        } args = {bases, sorted, tasks, salts, n_tasks, n_tiles, tile_counter, budget, 0, nullptr};
+        size_t size = sizeof args - sizeof(uint32_t*);
+        hipFunction_t f = s.acc_g1_pw[pi];
+        if (stamped) {
+            if (int rc = stamps_prepare(n_tiles, st, &args.stamps)) return rc;
+            size = sizeof args;
+            f = s.acc_g1_dbg[1][pi];
+        }
+        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+        HIPCHK(hipModuleLaunchKernel(f, waves, 1, 1, 64, 1, 1, 0, st, nullptr, extra));
+        return GH_OK;
+    }
     struct {
         const void* bases;
         const void* sorted;
@@ -134,10 +218,27 @@ int acc_g1_launch(int prime, const void* bases, const uint32_t* sorted, const Ac
         const void* salts;
         uint32_t n_tasks;
         uint32_t pad;
-    } args = {bases, sorted, tasks, salts, n_tasks, 0};
-    size_t size = sizeof args;
+        uint32_t* stamps;
+    } args = {bases, sorted, tasks, salts, n_tasks, 0, nullptr};
+    size_t size = sizeof args - sizeof(uint32_t*);
+    hipFunction_t f = s.acc_g1[pi];
+    const uint32_t blocks = (n_tasks + 255) / 256;
+    if (stamped) {
+        if (int rc = stamps_prepare(blocks * 4, st, &args.stamps)) return rc;
+        size = sizeof args;
+        f = s.acc_g1_dbg[0][pi];
+    }
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    HIPCHK(hipModuleLaunchKernel(s.acc_g1[prime == 6 ? 1 : 0], (n_tasks + 255) / 256, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
+    HIPCHK(hipModuleLaunchKernel(f, blocks, 1, 1, 256, 1, 1, 0, st, nullptr, extra));
+    return GH_OK;
+}
+
+int acc_stamps_read(uint32_t* out_words, size_t cap_words, uint32_t* n_records) {
+    const uint32_t* last = s.stamps[s.stamps_last];
+    uint32_t n = last ? s.stamps_n : 0;
+    if ((size_t)n * 16 > cap_words) n = (uint32_t)(cap_words / 16);
+    if (n) HIPCHK(hipMemcpy(out_words, last, (size_t)n * 64, hipMemcpyDeviceToHost));
+    if (n_records) *n_records = n;
     return GH_OK;
 }
 
@@ -241,6 +342,8 @@ int kernel_resources(const char* which, uint32_t* scratch, uint32_t* vgprs, uint
     const std::string w = which ? which : "";
     if (w == "g1_acc_p4") f = s.acc_g1[0];
     else if (w == "g1_acc_p6") f = s.acc_g1[1];
+    else if (w == "g1_acc_p4_pw") f = s.acc_g1_pw[0];
+    else if (w == "g1_acc_p6_pw") f = s.acc_g1_pw[1];
     else if (w == "g1_red_p4") f = s.red_g1[0];
     else if (w == "g1_red_p6") f = s.red_g1[1];
     else if (w == "g2_f2_fwd_r0") f = s.aff[0][1][1];

@@ -64,6 +64,9 @@ int ensure_init() {
         HIPCHK(hipStreamCreateWithPriority(&g.stream_acc, hipStreamDefault, prio("GH_PRIO_ACC", least)));
         HIPCHK(hipStreamCreateWithPriority(&g.stream_red, hipStreamDefault, prio("GH_PRIO_RED", greatest)));
         HIPCHK(hipStreamCreateWithPriority(&g.stream_acc2, hipStreamDefault, prio("GH_PRIO_ACC", least)));
+        // msm_impl.h msm_batch: the stream of every other G1 accumulation of a batch (GH_ACC_ALT=0: not created).  HIP maps its
+        // streams onto at most GPU_MAX_HW_QUEUES hardware queues (4 by default), which the four streams above already reach.
+        if (msm_knobs().acc_alt) HIPCHK(hipStreamCreateWithPriority(&g.stream_acc_alt, hipStreamDefault, prio("GH_PRIO_ACC", least)));
     }
     for (auto& ev : g.tev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     for (auto& ev : g.ev) HIPCHK(hipEventCreate(&ev));
@@ -252,6 +255,8 @@ int gh_shutdown(void) try {
     for (auto& ev : g.tev) hipEventDestroy(ev);
     hipStreamDestroy(g.stream_acc);
     hipStreamDestroy(g.stream_acc2);
+    if (g.stream_acc_alt) hipStreamDestroy(g.stream_acc_alt);
+    g.stream_acc_alt = nullptr;
     hipStreamDestroy(g.stream_red);
     hipStreamDestroy(g.stream);
     g.scratch_reserved = 0;
@@ -915,6 +920,19 @@ int gh_kernel_resources(const char* which, uint32_t* scratch_bytes_per_lane, uin
     int rc = ensure_init();
     if (rc) return rc;
     return gh_asm::kernel_resources(which, scratch_bytes_per_lane, registers, lds_bytes);
+} catch (...) { return gh_rt::api_exception(); }
+
+// Diagnostic entry for tools/acc_timeline.py, not part of include/ginger_hip.h (it serves diagnostic builds of the code object
+// only: GH_ASM_DEBUG=1 at build time, GH_ACC_STAMPS=1 at run time): the records the last G1 accumulation wrote, 16 words each --
+// shader clock and constant-rate clock at the start (words 0-3) and at the end (4-7), hardware id, XCC id, tile (persistent
+// form) or 4 x block + wave, live lanes.  Waits for the MSM streams.  *n_records = 0 when no stamped launch has run.
+int gh_acc_stamps_read(uint32_t* out_words, size_t cap_words, uint32_t* n_records) try {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!out_words || !n_records) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    int rc = ensure_init();
+    if (rc) return rc;
+    HIPCHK(sync_msm_streams());
+    return gh_asm::acc_stamps_read(out_words, cap_words, n_records);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_fft_last_kernel_ms(float* ms) try {

@@ -100,10 +100,13 @@ int launch_bucket_sums(const BucketSumArgs<C>& a, const std::string& task_pool, 
     if constexpr (C::F::DEG == 1) {
         if (!AFFIN && gh_asm::enabled()) {
             gh_asm::AccTask* tk = nullptr;
-            if (int rc = pool_get(task_pool.c_str(), tasks * sizeof(gh_asm::AccTask), (void**)&tk)) return rc;
+            // 16 bytes behind the table: the tile counter of the persistent form
+            if (int rc = pool_get(task_pool.c_str(), tasks * sizeof(gh_asm::AccTask) + 16, (void**)&tk)) return rc;
+            uint32_t* const counter = (uint32_t*)(tk + tasks);
             GH_LAUNCH((msm_acc_tasks_kernel<C>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st, a.starts, a.counts, a.order,
-                      a.total, a.out, a.chunk_start, a.n_heavy, a.n_chunks, a.heavy_chunk, a.partials, (AccTaskRec*)tk);
-            return gh_asm::acc_g1_launch(std::is_same<typename C::PF, P6>::value ? 6 : 4, a.points, a.sorted, tk, a.salts, (uint32_t)tasks, st);
+                      a.total, a.out, a.chunk_start, a.n_heavy, a.n_chunks, a.heavy_chunk, a.partials, (AccTaskRec*)tk, counter);
+            return gh_asm::acc_g1_launch(std::is_same<typename C::PF, P6>::value ? 6 : 4, a.points, a.sorted, tk, a.salts, (uint32_t)tasks,
+                                         counter, st);
         }
         GH_LAUNCH((msm_accumulate_xyzz_kernel<C, AFFIN>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, st,
                   (const Aff<C>*)a.points, a.sorted, a.starts, a.counts, a.order, a.total, a.salts, a.out, a.chunk_start, a.n_heavy,
@@ -765,8 +768,15 @@ int msm_batch(BasesBase* const* hs, const void* const* d_scalars, const size_t* 
     if ((rc = issue_sort(0))) return rc;
     for (int k = 0; k < count; k++) {
         MsmJob<C>& j = jobs[(size_t)k];
-        if (k >= 2 && j.n) HIPCHK(hipStreamWaitEvent(g.stream_acc, g.pev[(k - 2) & 3][6], 0));   // reduce(k-2) is done with this slot's buckets
-        if ((rc = j.launch_accumulate(g.stream_acc))) return rc;
+        // GH_ACC_ALT (G1, persistent form): the odd jobs accumulate on a stream of their own, so that acc(k+1) no longer queues behind the last
+        // wave of acc(k) -- its workgroups take the slots acc(k)'s waves leave.  Stream and buffer slot alternate together (k & 1),
+        // so acc(k) still follows acc(k-2), the previous occupant of its slot, in stream order; it waits for its own sort on the
+        // host (launch_accumulate) and for reduce(k-2) by event, as before.  Every cleanup path waits for the stream with the
+        // others (runtime.h sync_msm_streams).
+        const bool alt = C::F::DEG == 1 && g.stream_acc_alt && gh_asm::enabled() && msm_knobs().acc_persist && (k & 1);
+        const hipStream_t st_acc = alt ? g.stream_acc_alt : g.stream_acc;
+        if (k >= 2 && j.n) HIPCHK(hipStreamWaitEvent(st_acc, g.pev[(k - 2) & 3][6], 0));   // reduce(k-2) is done with this slot's buckets
+        if ((rc = j.launch_accumulate(st_acc))) return rc;
         if (j.n) HIPCHK(hipStreamWaitEvent(g.stream_red, g.pev[k & 3][4], 0));
         if ((rc = j.launch_reduce(g.stream_red))) return rc;
         // sort(k+1) goes out before the host waits for the window sums of k-1: the two share a buffer slot but no buffer

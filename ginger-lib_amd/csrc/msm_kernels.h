@@ -716,8 +716,12 @@ template <class C>
 __global__ void __launch_bounds__(256)
 msm_acc_tasks_kernel(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ order,
                      uint32_t total, Proj<C>* __restrict__ buckets, const uint32_t* __restrict__ chunk_start, uint32_t n_heavy,
-                     uint32_t n_chunks, uint32_t chunk, Proj<C>* __restrict__ partials, AccTaskRec* __restrict__ out) {
+                     uint32_t n_chunks, uint32_t chunk, Proj<C>* __restrict__ partials, AccTaskRec* __restrict__ out,
+                     uint32_t* __restrict__ tile_counter) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    // the persistent accumulation draws its tiles from this word (asmgen/g1_xyzz.py): it starts every launch at 0.  This kernel
+    // is the accumulation's predecessor on its stream, so the reset costs no memset node and no launch of its own.
+    if (t == 0) __hip_atomic_store(tile_counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (t >= n_chunks + (total - n_heavy)) return;
     const auto k = acc_task_decode<false>(t, starts, counts, order, buckets, chunk_start, n_heavy, n_chunks, chunk, partials, 0, 0);
     AccTaskRec r;

@@ -48,6 +48,12 @@ struct MsmKnobs {
     int aff_split = 1;              // GH_AFF_SPLIT=0: affine rounds in one piece instead of two halves on two streams
     int aff_split_b = 32;           // GH_AFF_SPLIT_B: the smallest batch per lane group at which a round is split
     bool aff_debug = false;         // GH_AFF_DEBUG (set): per affine round, exceptions listed / round redone (stderr; synchronises)
+    // launch form of the assembly G1 accumulation (DESIGN.md section 9 "Launch form of the accumulation", profiles/acc_persist_ab.json)
+    int acc_persist = 1;            // GH_ACC_PERSIST=0: blocks of 256 tasks instead of one-wave workgroups that draw tiles of 64 tasks (A/B)
+    int acc_waves = 0;              // GH_ACC_WAVES=N: grid of the persistent form (0 = by the budget, or 8 per CU without one); for tests and sweeps
+    int acc_tiles = 1;              // GH_ACC_TILES=K: a persistent wave ends after K tiles, the grid is tiles / K (0 = no limit: a resident grid,
+                                    //   which keeps the sort and the reduction of the neighbouring MSMs of a batch off the card: +4.4 ms per MSM)
+    int acc_alt = 1;                // GH_ACC_ALT=0: the persistent G1 accumulations of a batch all on one stream instead of two in turn (A/B)
 
     // (round 3, profiles/r03_g2_knobs.txt: on the towers the projective finish costs 11 tower products per point against the rounds' 6,
     //  so fewer points are left to it: Fq3 1.5 (MNT6 G2 2^19: 5.75 -> 5.95 M/s together with the one-chunk scratch budget), Fq2 2.5)
@@ -75,6 +81,10 @@ struct MsmKnobs {
         k.aff_split = env_int("GH_AFF_SPLIT", k.aff_split);
         k.aff_split_b = env_int("GH_AFF_SPLIT_B", k.aff_split_b);
         k.aff_debug = getenv("GH_AFF_DEBUG") != nullptr;
+        k.acc_persist = env_int("GH_ACC_PERSIST", k.acc_persist);
+        k.acc_waves = env_int("GH_ACC_WAVES", k.acc_waves);
+        k.acc_tiles = env_int("GH_ACC_TILES", k.acc_tiles);
+        k.acc_alt = env_int("GH_ACC_ALT", k.acc_alt);
         return k;
     }
 };

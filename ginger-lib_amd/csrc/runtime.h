@@ -53,6 +53,7 @@ struct Ctx {
     hipStream_t stream_acc = nullptr;   // MSM accumulation (lowest priority: the filler of the pipeline)
     hipStream_t stream_red = nullptr;   // MSM bucket reduction (highest priority: short latency chains)
     hipStream_t stream_acc2 = nullptr;  // second half of a split affine round (msm_impl.h issue_round): same priority as stream_acc
+    hipStream_t stream_acc_alt = nullptr;   // the accumulations of the odd jobs of a G1 batch (msm_impl.h msm_batch); null under GH_ACC_ALT=0
     hipEvent_t tev[2] = {nullptr, nullptr};   // fork / join of a split round
     hipEvent_t ev[10];
     hipEvent_t pev[4][8];               // MSM stage events, one set per job in flight (job k of a batch uses set k & 3)
@@ -86,11 +87,13 @@ template <class T> int slot_buf(const char* name, int slot, size_t bytes, T** ou
     return pool_get(slot_name(name, slot).c_str(), bytes, (void**)out);
 }
 // (env_int / env_double, the readers of an environment knob: msm_plan.h)
-// Waits for every stream an MSM runs on, the second stream of a split affine round included: nothing may still read or write a
-// pooled buffer or a cached key when it is released.  Waits on all four even after an error; returns the first error.
+// Waits for every stream an MSM runs on, the second stream of a split affine round and the alternate accumulation stream
+// included: nothing may still read or write a pooled buffer or a cached key when it is released.  Waits on all of them even
+// after an error; returns the first error.
 inline hipError_t sync_msm_streams() {
     hipError_t e = hipSuccess;
-    for (hipStream_t s : {g.stream, g.stream_acc, g.stream_acc2, g.stream_red}) {
+    for (hipStream_t s : {g.stream, g.stream_acc, g.stream_acc2, g.stream_acc_alt, g.stream_red}) {
+        if (!s) continue;
         const hipError_t es = hipStreamSynchronize(s);
         if (e == hipSuccess) e = es;
     }
