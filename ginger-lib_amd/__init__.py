@@ -210,6 +210,12 @@ class DeviceBuffer:
             load_library().gh_dev_free(self.ptr)
             self.ptr = ctypes.c_void_p()
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
 
 def msm_cached(curve, bases, scalars, infinity=None):
     """VariableBaseMSM::multi_scalar_mul for an unchanged caller (gh_msm_cached): a pure function of (bases, scalars) whose

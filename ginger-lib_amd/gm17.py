@@ -18,16 +18,19 @@ GM17's Proof / Parameters have no byte format in the reference (gm17/mod.rs:59-6
 proof is returned as three affine points in the C ABI's form; `proof_bytes` writes them the way GroupAffine::write
 would (short_weierstrass_projective.rs:185-192), which is what the parity tests compare.
 """
+import contextlib
+
 import numpy as np
 
-from .groth16 import _MODULUS, _canon_rows, _canon_rows_fast, _ints_from_mont_rows, _mont_rows, affine_to_wire
+from .limbs import FR_FIELD, MODULUS, affine_to_wire, canon_rows, domain_size, ints_from_mont_rows, mont_rows
+from .prover import ResidentQueries, into_repr, upload_rows
 
 
 def sap_rows_from_r1cs(pairing, num_inputs, assignment, A, B, C):
     """The host part of R1CStoSAP::witness_map (r1cs_to_sap.rs:123-148, :159-184, :198-219): from the evaluated R1CS rows
     A_i = <at_i, x>, B_i, C_i and the assignment x (Python integers) to the extended assignment and the two vectors the
     transforms start from.  -> (full_assignment, a, c, log_n): a and c have 2^log_n entries."""
-    r = _MODULUS[pairing]
+    r = MODULUS[pairing]
     n_con = len(A)
     ni = num_inputs
     full = list(assignment)
@@ -36,9 +39,7 @@ def sap_rows_from_r1cs(pairing, num_inputs, assignment, A, B, C):
     full += extra
     for i in range(1, ni):                                       # :144-149
         full.append((full[i] - 1) * (full[i] - 1) % r)
-    size = 1
-    while size < 2 * n_con + 2 * (ni - 1) + 1:                   # :151-155
-        size <<= 1
+    size = domain_size(2 * n_con + 2 * (ni - 1) + 1)             # :151-155
     off = 2 * n_con
     var_off, var_off2 = n_var, n_var + n_con - 1
     a = [0] * size
@@ -58,24 +59,15 @@ def sap_rows_from_r1cs(pairing, num_inputs, assignment, A, B, C):
     return full, a, c, size.bit_length() - 1
 
 
-class ResidentGm17Key:
+class ResidentGm17Key(ResidentQueries):
     """pk: dict of numpy arrays in the ABI formats (Montgomery x || y rows, all points finite): a_query, c_query_2 (n x 24),
     c_query_1 (n - num_inputs rows), g_gamma2_z_t (m x 24), b_query (n x 24*deg), and the single points g_gamma_z,
     g_ab_gamma_z, g_gamma2_z2 (24 u64), h_gamma_z (24*deg u64)."""
 
     def __init__(self, gl, pairing, pk, num_inputs, precompute=True):
-        assert pairing in ("mnt4753", "mnt6753")
-        self.gl, self.pk, self.num_inputs, self.pairing = gl, pk, int(num_inputs), pairing
-        self.g1, self.g2 = pairing + "_g1", pairing + "_g2"
+        super().__init__(gl, pairing, num_inputs)
         row = lambda v: np.asarray(v, dtype=np.uint64).reshape(1, -1)
         cat = lambda *parts: np.ascontiguousarray(np.concatenate(parts), dtype=np.uint64)
-        vectors = {
-            "a": (self.g1, cat(pk["a_query"][1:], row(pk["a_query"][0]), row(pk["g_gamma_z"]))),
-            "b": (self.g2, cat(pk["b_query"][1:], row(pk["b_query"][0]), row(pk["h_gamma_z"]))),
-            "c1": (self.g1, cat(pk["c_query_1"], row(pk["g_gamma2_z2"]), row(pk["g_ab_gamma_z"]))),
-            "c2": (self.g1, cat(pk["c_query_2"][1:], row(pk["c_query_2"][0]))),
-            "g": (self.g1, cat(pk["g_gamma2_z_t"], row(pk["g_gamma2_z_t"][0]))),
-        }
         # keys made by generate_parameters hold GroupAffine::zero() wherever a variable does not occur in A (the extra SAP
         # variables: r1cs_to_sap.rs:68, :85-91): pk["<query>_inf"] flags them (absent = all finite)
         def flags(q, head_last, tail):
@@ -85,21 +77,13 @@ class ResidentGm17Key:
             f = np.asarray(f, dtype=np.uint8)
             f = np.concatenate([f[1:], f[:1]]) if head_last else f
             return np.ascontiguousarray(np.concatenate([f, np.zeros(tail, dtype=np.uint8)]))
-        inf = {"a": flags("a_query", True, 1), "b": flags("b_query", True, 1), "c1": flags("c_query_1", False, 2),
-               "c2": flags("c_query_2", True, 0), "g": None}
-        self.keys = {}
-        for name, (curve, rows) in vectors.items():
-            rb = gl.ResidentBases(curve, rows, infinity=inf[name])
-            if precompute and rb.n:
-                try:
-                    rb.precompute(0)
-                except gl.GingerHipError:
-                    pass                      # no memory for the table / a point of 2-power order: per-window path
-            self.keys[name] = rb
-
-    def free(self):
-        for rb in self.keys.values():
-            rb.free()
+        self._upload({
+            "a": (self.g1, cat(pk["a_query"][1:], row(pk["a_query"][0]), row(pk["g_gamma_z"])), flags("a_query", True, 1)),
+            "b": (self.g2, cat(pk["b_query"][1:], row(pk["b_query"][0]), row(pk["h_gamma_z"])), flags("b_query", True, 1)),
+            "c1": (self.g1, cat(pk["c_query_1"], row(pk["g_gamma2_z2"]), row(pk["g_ab_gamma_z"])), flags("c_query_1", False, 2)),
+            "c2": (self.g1, cat(pk["c_query_2"][1:], row(pk["c_query_2"][0])), flags("c_query_2", True, 0)),
+            "g": (self.g1, cat(pk["g_gamma2_z_t"], row(pk["g_gamma2_z_t"][0])), None),
+        }, precompute)
 
     def create_proof_msms(self, input_assignment, aux_assignment, h, d1, d2, r, h_dev=None):
         """prover.rs:267-352 after the witness map.  input_assignment: num_inputs - 1 rows, aux_assignment: the rest of
@@ -108,7 +92,7 @@ class ResidentGm17Key:
         scalars.  Returns (A, B, C) as (xy, is_infinity) pairs."""
         gl, ni = self.gl, self.num_inputs
         g1, g2 = self.g1, self.g2
-        mod = _MODULUS[self.pairing]
+        mod = MODULUS[self.pairing]
         inp = np.ascontiguousarray(input_assignment, dtype=np.uint64).reshape(-1, 12)
         aux = np.ascontiguousarray(aux_assignment, dtype=np.uint64).reshape(-1, 12)
         assert len(inp) == ni - 1
@@ -117,50 +101,30 @@ class ResidentGm17Key:
         assert k["b"].n - 2 == n_var and k["c2"].n - 1 == n_var and k["c1"].n - 2 == n_var - (ni - 1)
         aux_used = aux[:n_var - len(inp)]                        # the reference's zip cuts a longer vector here (variable_base.rs:36)
         pad = np.zeros((n_var - len(inp) - len(aux_used), 12), dtype=np.uint64)
-        one = np.zeros((1, 12), dtype=np.uint64)
-        one[0, 0] = 1
-        r_d1 = _canon_rows([(r + d1) % mod])
-        c1_tail = _canon_rows([(r * r + 2 * r * d1) % mod, (r + d1) % mod])
+        r_d1 = canon_rows([(r + d1) % mod])
+        c1_tail = canon_rows([(r * r + 2 * r * d1) % mod, (r + d1) % mod])
+        row_d2 = canon_rows([d2 % mod])
         # ONE device vector  input || aux || 1 || (r + d1) || (r^2 + 2 r d1) || (r + d1):
         #   a / b keys take rows [0, n_var + 2), c_2 rows [0, n_var + 1), c_1 rows [ni - 1, n_var) followed by its own two
         # -- c_1's tail is not contiguous with the aux part, so c_1 gets the aux rows again behind the shared vector
-        rows = [inp, aux_used, pad, one, r_d1]
-        d_s = gl.DeviceBuffer((n_var + 2) * 96)
-        d_c1 = gl.DeviceBuffer((n_var - (ni - 1) + 2) * 96)
-        import ctypes
-        lib = gl.load_library()
-
-        def fill(buf, parts):
-            row = 0
-            for part in parts:
-                if len(part):
-                    part = np.ascontiguousarray(part, dtype=np.uint64)
-                    gl._check(lib.gh_dev_upload(ctypes.c_void_p(buf.ptr.value + row * 96), gl._ptr(part), part.nbytes))
-                    row += len(part)
-            return row
-        assert fill(d_s, rows) == n_var + 2
-        assert fill(d_c1, [aux_used, pad, c1_tail]) == n_var - (ni - 1) + 2
-        own_h = h_dev is None
-        if own_h:
-            h_all = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 12)
-            n_h = min(len(h_all), k["g"].n - 1)
-            hv = np.concatenate([h_all[:n_h], np.zeros((k["g"].n - 1 - n_h, 12), dtype=np.uint64), _canon_rows([d2 % mod])])
-            d_h = gl.DeviceBuffer(hv.nbytes).upload(hv)
-        else:
-            d_h, n_h = h_dev[0], int(h_dev[1])
-            assert n_h == k["g"].n - 1                           # the caller left room for one more row behind h
-            row_d2 = _canon_rows([d2 % mod])
-            gl._check(lib.gh_dev_upload(ctypes.c_void_p(d_h.ptr.value + n_h * 96), gl._ptr(row_d2), 96))
-        try:
+        with contextlib.ExitStack() as stack:
+            d_s = stack.enter_context(gl.DeviceBuffer((n_var + 2) * 96))
+            d_c1 = stack.enter_context(gl.DeviceBuffer((n_var - (ni - 1) + 2) * 96))
+            assert upload_rows(gl, d_s, [inp, aux_used, pad, canon_rows([1]), r_d1]) == n_var + 2
+            assert upload_rows(gl, d_c1, [aux_used, pad, c1_tail]) == n_var - (ni - 1) + 2
+            if h_dev is None:
+                h_all = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 12)
+                n_h = min(len(h_all), k["g"].n - 1)
+                hv = np.concatenate([h_all[:n_h], np.zeros((k["g"].n - 1 - n_h, 12), dtype=np.uint64), row_d2])
+                d_h = stack.enter_context(gl.DeviceBuffer(hv.nbytes)).upload(hv)
+            else:
+                d_h, n_h = h_dev[0], int(h_dev[1])
+                assert n_h == k["g"].n - 1                           # the caller left room for one more row behind h
+                upload_rows(gl, d_h, [row_d2], n_h)
             g_a, c1, c2, g_acc = gl.msm_batch_dev([(k["a"], d_s, n_var + 2), (k["c1"], d_c1, n_var - (ni - 1) + 2),
                                                    (k["c2"], d_s, n_var + 1), (k["g"], d_h, k["g"].n)])
             g_b = k["b"].msm_dev(d_s, n_var + 2)
-        finally:
-            d_s.free()
-            d_c1.free()
-            if own_h:
-                d_h.free()
-        g_c = gl.proj_add(g1, c1, gl.proj_mul(g1, c2, _canon_rows([r % mod])[0]))
+        g_c = gl.proj_add(g1, c1, gl.proj_mul(g1, c2, canon_rows([r % mod])[0]))
         g_c = gl.proj_add(g1, g_c, g_acc)
         return gl.proj_to_affine(g1, g_a), gl.proj_to_affine(g2, g_b), gl.proj_to_affine(g1, g_c)
 
@@ -168,29 +132,24 @@ class ResidentGm17Key:
         """create_proof (prover.rs:201-352) for evaluated constraint rows (groth16.benchmark_circuit_rows form): the host part
         of the SAP witness map, its transforms on the device (gh_sap_witness_map_dev), into_repr on the device, the MSM stage."""
         gl, pairing = self.gl, self.pairing
-        mod = _MODULUS[pairing]
+        mod = MODULUS[pairing]
         num_inputs, assignment, A, B, C = circuit_rows
         assert num_inputs == self.num_inputs
         full, a, c, log_n = sap_rows_from_r1cs(pairing, num_inputs, assignment, A, B, C)
         size = 1 << log_n
-        field = "mnt4753_fr" if pairing == "mnt4753" else "mnt6753_fr"
-        dd = _mont_rows([d1, d2], mod)
-        lib = gl.load_library()
-        bufs = [gl.DeviceBuffer(size * 96 + 192) for _ in range(3)]
-        try:
-            bufs[0].upload(_mont_rows(a, mod))
-            bufs[1].upload(_mont_rows(c, mod))
+        field = FR_FIELD[pairing]
+        dd = mont_rows([d1, d2], mod)
+        with contextlib.ExitStack() as stack:
+            bufs = [stack.enter_context(gl.DeviceBuffer(size * 96 + 192)) for _ in range(3)]
+            bufs[0].upload(mont_rows(a, mod))
+            bufs[1].upload(mont_rows(c, mod))
+            lib = gl.load_library()
             gl._check(lib.gh_sap_witness_map_dev(gl.FIELDS[field], bufs[0].ptr, bufs[1].ptr, log_n, gl._ptr(dd[0]), gl._ptr(dd[1]), bufs[2].ptr))
-            one_plain = np.zeros(12, dtype=np.uint64)
-            one_plain[0] = 1
-            gl._check(lib.gh_vec_scale_dev(gl.FIELDS[field], bufs[2].ptr, gl._ptr(one_plain), size + 1))      # into_repr of h (:237-252)
-            scal = _canon_rows(full)
+            into_repr(gl, field, bufs[2], size + 1)                                                             # h (:237-252)
+            scal = canon_rows(full)
             n_h = self.keys["g"].n - 1
             assert n_h <= size + 1
             return self.create_proof_msms(scal[1:num_inputs], scal[num_inputs:], None, d1, d2, r, h_dev=(bufs[2], n_h))
-        finally:
-            for buf in bufs:
-                buf.free()
 
 
 def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, t, g1_xyz, g2_xyz):
@@ -205,20 +164,18 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, t, g1_xyz, g2_xyz)
       * the single points (:233-241) by host-side scalar multiplications (gh_proj_mul).
     Returns (pk, info): pk in ResidentGm17Key's form (Montgomery x || y rows + `<query>_inf` flags; GM17's Parameters::write is
     unimplemented upstream, gm17/mod.rs:186-196), info = the SAP evaluations a, c, Z(t) for a check in the exponent."""
-    r = _MODULUS[pairing]
-    field = "mnt4753_fr" if pairing == "mnt4753" else "mnt6753_fr"
+    r = MODULUS[pairing]
+    field = FR_FIELD[pairing]
     g1c, g2c = pairing + "_g1", pairing + "_g2"
     num_inputs, num_aux, at, bt, ct = lcs
     n_con = len(at)
     ni1 = num_inputs - 1
-    size = 1
-    while size < 2 * n_con + 2 * ni1 + 1:                                          # r1cs_to_sap.rs:18-21
-        size <<= 1
+    size = domain_size(2 * n_con + 2 * ni1 + 1)                                    # r1cs_to_sap.rs:18-21
     log_n = size.bit_length() - 1
     zt = (pow(t, size, r) - 1) % r
     u_rows = np.zeros((size, 12), dtype=np.uint64)
-    gl._check(gl.load_library().gh_lagrange_coefficients(gl.FIELDS[field], log_n, gl._ptr(_mont_rows([t], r)[0]), gl._ptr(u_rows)))
-    u = _ints_from_mont_rows(u_rows, r)
+    gl._check(gl.load_library().gh_lagrange_coefficients(gl.FIELDS[field], log_n, gl._ptr(mont_rows([t], r)[0]), gl._ptr(u_rows)))
+    u = ints_from_mont_rows(u_rows, r)
     sap_nv = 2 * ni1 + num_aux + n_con                                             # :30-31
     xvo, xco, xvo2 = ni1 + num_aux + 1, 2 * n_con, ni1 + num_aux + n_con           # :32-35
     a, c = [0] * (sap_nv + 1), [0] * (sap_nv + 1)
@@ -250,13 +207,13 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, t, g1_xyz, g2_xyz)
     stats = {"fixed_base_scalars": 0, "fixed_base_calls": 0}
 
     def rows(table, vals):
-        xy, inf = table.multi_scalar_mul_affine(_canon_rows_fast(vals), canonical=False)
+        xy, inf = table.multi_scalar_mul_affine(canon_rows(vals), canonical=False)
         stats["fixed_base_scalars"] += len(vals)
         stats["fixed_base_calls"] += 1
         return np.ascontiguousarray(xy, dtype=np.uint64), np.asarray(inf, dtype=np.uint8)
 
     def point(curve, xyz, k):
-        xy, inf = gl.proj_to_affine(curve, gl.proj_mul(curve, xyz, _canon_rows([k % r])[0]))
+        xy, inf = gl.proj_to_affine(curve, gl.proj_mul(curve, xyz, canon_rows([k % r])[0]))
         assert not inf
         return np.asarray(xy, dtype=np.uint64).reshape(-1)
 
@@ -276,7 +233,7 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, t, g1_xyz, g2_xyz)
         pk["c_query_2"], pk["c_query_2_inf"] = rows(tg, [v * (2 * gamma * gamma % r) % r * zt % r for v in a])
     finally:
         tg.free()
-    h_gamma = gl.proj_mul(g2c, g2_xyz, _canon_rows([gamma % r])[0])
+    h_gamma = gl.proj_mul(g2c, g2_xyz, canon_rows([gamma % r])[0])
     th = FB(g2c, h_gamma, 753, h_window)
     try:
         pk["b_query"], pk["b_query_inf"] = rows(th, a)
@@ -300,11 +257,11 @@ def verifying_key(gl, pairing, pk, alpha, beta, gamma, g1_xyz, g2_xyz):
     generate_random_parameters fixes (generator.rs:27): the C queries carry gamma c_i + (alpha + beta) a_i for the public inputs
     and for the auxiliary variables alike, and the two differ by (gamma - 1)((alpha + beta) sum a_i x_i + gamma sum c_i x_i)
     over the auxiliary variables."""
-    r = _MODULUS[pairing]
+    r = MODULUS[pairing]
     g1c, g2c = pairing + "_g1", pairing + "_g2"
 
     def point(curve, xyz, k):
-        xy, inf = gl.proj_to_affine(curve, gl.proj_mul(curve, xyz, _canon_rows([k % r])[0]))
+        xy, inf = gl.proj_to_affine(curve, gl.proj_mul(curve, xyz, canon_rows([k % r])[0]))
         if inf:
             raise ValueError("a point of the verifying key is the point at infinity")
         return np.asarray(xy, dtype=np.uint64).reshape(-1)

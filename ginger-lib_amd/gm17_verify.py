@@ -13,7 +13,7 @@ says engine="mnt6753".  No key point may be at infinity.  Subgroup membership of
 import numpy as np
 
 from . import GingerHipError, _check, _ptr    # noqa: F401 (GingerHipError: re-exported)
-from . import _handles, groth16
+from . import _handles, limbs
 from ._handles import _rows, ci, sz, vp
 from .pairing import ENGINES, _G1_REC, _WIDTHS, _points, _wire_rows
 
@@ -85,5 +85,5 @@ def verify_proofs(pvk, proofs, inputs):
     flat = [int(v) for row in inputs for v in row]
     if any(v < 0 or v >= w.fr for v in flat):
         raise ValueError("a public input is not below the modulus")
-    x = groth16._mont_rows(flat, w.fr).reshape(n, pvk.num_inputs * 12)
+    x = limbs.mont_rows(flat, w.fr).reshape(n, pvk.num_inputs * 12)
     return pvk.verify(a, b, c, x)

@@ -10,28 +10,27 @@ tests and for the replay of BASELINE config 5 from exported buffers (SURVEY.md s
     the few single points the reference adds by hand (ResidentProvingKey below);
   * five MSMs per proof instead of nine: four on G1 as ONE pipelined batch (gh_msm_resident_dev_batch),
     one on G2.
+
+Field constants and limb forms come from limbs.py; the resident query set (uploads, release) and the helpers for device
+vectors are prover.py's, shared with gm17.py.
 """
+import contextlib
 import struct
+import time
 
 import numpy as np
 
-# base-field bytes of one coordinate coefficient / degree of the G2 coordinate field / bytes of the target-field element
-# vk.alpha_g1_beta_g2 (Fq4 resp. Fq6: carried as opaque bytes -- the prover never reads it; pairing.py computes it for MNT4-753)
-_FQ_BYTES = 96
-_G2_DEG = {"mnt4753": 2, "mnt6753": 3}
-_FQK_BYTES = {"mnt4753": 4 * 96, "mnt6753": 6 * 96}
-_MODULUS = {   # r = scalar field of the pairing = base field of the other curve (SURVEY F5)
-    "mnt4753": 0x1c4c62d92c41110229022eee2cdadb7f997505b8fafed5eb7e8f96c97d87307fdb925e8a0ed8d99d124d9a15af79db26c5c28c859a99b3eebca9429212636b9dff97634993aa4d6c381bc3f0057974ea099170fa13a4fd90776e240000001,
-    "mnt6753": 0x1c4c62d92c41110229022eee2cdadb7f997505b8fafed5eb7e8f96c97d87307fdb925e8a0ed8d99d124d9a15af79db117e776f218059db80f0da5cb537e38685acce9767254a4638810719ac425f0e39d54522cdd119f5e9063de245e8001,
-}
+from .limbs import FQ_BYTES, FQK_BYTES, FR_FIELD, G2_DEG, MODULUS, affine_to_wire, canon_rows, domain_size, ints_from_canon_rows, \
+    ints_from_mont_rows, mont_rows
+from .prover import ResidentQueries, RowView, into_repr, upload_rows
 
 
 def parse_parameters(pairing, blob):
     """Parameters::write stream (proof-systems/src/groth16/mod.rs:188-208; VerifyingKey::write :104-114) -> dict of byte
     strings: single points as GroupAffine::write records (x || y || infinity byte, canonical little-endian coefficients:
     short_weierstrass_projective.rs:185-192), queries as their records back to back.  Lengths are big-endian u32."""
-    g1 = 2 * _FQ_BYTES + 1
-    g2 = 2 * _FQ_BYTES * _G2_DEG[pairing] + 1
+    g1 = 2 * FQ_BYTES + 1
+    g2 = 2 * FQ_BYTES * G2_DEG[pairing] + 1
     pos = 0
 
     def take(nbytes):
@@ -46,7 +45,7 @@ def parse_parameters(pairing, blob):
         (count,) = struct.unpack(">I", take(4))
         return take(count * rec)
 
-    pk = {"vk_alpha_g1_beta_g2": take(_FQK_BYTES[pairing]), "vk_gamma_g2": take(g2), "vk_delta_g2": take(g2)}
+    pk = {"vk_alpha_g1_beta_g2": take(FQK_BYTES[pairing]), "vk_gamma_g2": take(g2), "vk_delta_g2": take(g2)}
     pk["vk_gamma_abc_g1"] = vec(g1)
     for name, rec in (("alpha_g1", g1), ("beta_g1", g1), ("beta_g2", g2), ("delta_g1", g1), ("delta_g2", g2)):
         pk[name] = take(rec)
@@ -64,7 +63,7 @@ def benchmark_circuit_rows(pairing, num_constraints):
     Host scalar code, as in the reference (synthesis is not on the device path).  The circuit has two public inputs
     a = b = 1, alternating a + b = c / a * b = c steps and one closing constraint (sum of the recorded assignments)^2;
     the recording pushes (a, a) twice and never b -- reproduced as written (:31-36)."""
-    r = _MODULUS[pairing]
+    r = MODULUS[pairing]
     num_inputs = 3                                           # one, a, b
     inputs = [1, 1, 1]
     aux = []
@@ -115,16 +114,6 @@ def benchmark_circuit_lcs(num_constraints):
     return num_inputs, n_aux, at, bt, ct
 
 
-def _ints_from_mont_rows(rows, modulus):
-    rinv = pow(1 << 768, -1, modulus)
-    raw = np.ascontiguousarray(rows, dtype=np.uint64).tobytes()
-    return [int.from_bytes(raw[96 * i:96 * i + 96], "little") * rinv % modulus for i in range(len(raw) // 96)]
-
-
-def _canon_rows_fast(vals):
-    return np.frombuffer(b"".join(int(v).to_bytes(96, "little") for v in vals), dtype=np.uint64).reshape(-1, 12) if len(vals) else np.zeros((0, 12), np.uint64)
-
-
 def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, g2_xyz, vk_pairing_bytes=None, r1cs=None):
     """generate_parameters (proof-systems/src/groth16/generator.rs:146-335) above the C ABI, for a constraint system given as
     linear combinations; the toxic waste, the evaluation point t (sample_element_outside_domain, :181) and the two
@@ -137,17 +126,15 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, 
         them; pairing.parameters_with_pairing puts the real value into an MNT4-753 stream;
       * r1cs (an r1cs.ResidentR1CS of the same lcs): the Lagrange coefficients stay on the device
         (gh_lagrange_coefficients_dev) and gh_r1cs_instance_map_dev takes the place of the host loop -- same bytes."""
-    r = _MODULUS[pairing]
-    field = "mnt4753_fr" if pairing == "mnt4753" else "mnt6753_fr"
+    r = MODULUS[pairing]
+    field = FR_FIELD[pairing]
     g1c, g2c = pairing + "_g1", pairing + "_g2"
     num_inputs, num_aux, at, bt, ct = lcs
     n_con = len(at)
-    size = 1
-    while size < n_con + (num_inputs - 1) + 1:
-        size <<= 1
+    size = domain_size(n_con + num_inputs)
     log_n = size.bit_length() - 1
     zt = (pow(t, size, r) - 1) % r                                               # evaluate_vanishing_polynomial
-    tau = _mont_rows([t], r)[0]
+    tau = mont_rows([t], r)[0]
     nv = (num_inputs - 1) + num_aux
     if r1cs is not None:
         a, b, c = _instance_map_on_device(gl, field, r1cs, (num_inputs, num_aux, n_con, log_n), tau)
@@ -169,8 +156,7 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, 
     stats = {"fixed_base_scalars": 0, "fixed_base_s": 0.0}
 
     def wire_rows(table, deg, vals):
-        import time
-        rows = _canon_rows_fast(vals)                                          # host integers -> 96-byte rows: not part of the call
+        rows = canon_rows(vals)                                          # host integers -> 96-byte rows: not part of the call
         t0 = time.perf_counter()
         xy, inf = table.multi_scalar_mul_affine(rows, canonical=True)
         stats["fixed_base_s"] += time.perf_counter() - t0
@@ -181,10 +167,10 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, 
         return rec.tobytes()
 
     def wire_point(curve, deg, g_xyz, k):
-        xy, inf = gl.proj_to_affine(curve, gl.proj_mul(curve, g_xyz, _canon_rows([k])[0]))
+        xy, inf = gl.proj_to_affine(curve, gl.proj_mul(curve, g_xyz, canon_rows([k])[0]))
         return affine_to_wire(pairing, "g1" if deg == 1 else "g2", xy, inf)
 
-    deg2 = _G2_DEG[pairing]
+    deg2 = G2_DEG[pairing]
     t1 = FB(g1c, g1_xyz, 753, g1_window)
     try:
         a_q = wire_rows(t1, 1, a)
@@ -200,7 +186,7 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, delta, t, g1_xyz, 
     finally:
         t2.free()
     blob = bytearray()
-    blob += vk_pairing_bytes if vk_pairing_bytes is not None else bytes((i * 37 + 5) & 0xFF for i in range(_FQK_BYTES[pairing]))
+    blob += vk_pairing_bytes if vk_pairing_bytes is not None else bytes((i * 37 + 5) & 0xFF for i in range(FQK_BYTES[pairing]))
     blob += wire_point(g2c, deg2, g2_xyz, gamma) + wire_point(g2c, deg2, g2_xyz, delta)
     blob += struct.pack(">I", num_inputs) + abc_q
     blob += wire_point(g1c, 1, g1_xyz, alpha) + wire_point(g1c, 1, g1_xyz, beta) + wire_point(g2c, deg2, g2_xyz, beta)
@@ -218,7 +204,7 @@ def _instance_map_on_host(gl, field, lcs, size, tau, r):
     n_con, log_n = len(at), size.bit_length() - 1
     u_rows = np.zeros((size, 12), dtype=np.uint64)
     gl._check(gl.load_library().gh_lagrange_coefficients(gl.FIELDS[field], log_n, gl._ptr(tau), gl._ptr(u_rows)))
-    u = _ints_from_mont_rows(u_rows, r)
+    u = ints_from_mont_rows(u_rows, r)
     nv = (num_inputs - 1) + num_aux
     a, b, c = [0] * (nv + 1), [0] * (nv + 1), [0] * (nv + 1)
     for i in range(num_inputs):
@@ -238,61 +224,19 @@ def _instance_map_on_device(gl, field, r1cs, shape, tau):
     if (r1cs.num_inputs, r1cs.num_aux, r1cs.num_constraints, r1cs.log_n) != shape:
         raise ValueError("the resident constraint system is not the one of lcs")
     nv1 = num_inputs + num_aux
-    d_u = gl.DeviceBuffer(96 << log_n)
-    outs = [gl.DeviceBuffer(nv1 * 96) for _ in range(3)]
-    try:
+    with contextlib.ExitStack() as stack:
+        d_u = stack.enter_context(gl.DeviceBuffer(96 << log_n))
+        outs = [stack.enter_context(gl.DeviceBuffer(nv1 * 96)) for _ in range(3)]
         gl._check(gl.load_library().gh_lagrange_coefficients_dev(gl.FIELDS[field], log_n, gl._ptr(tau), d_u.ptr))
         r1cs.instance_map_dev(d_u, *outs)
-        one_plain = np.zeros(12, dtype=np.uint64)
-        one_plain[0] = 1
         res = []
         for o in outs:
-            gl._check(gl.load_library().gh_vec_scale_dev(gl.FIELDS[field], o.ptr, gl._ptr(one_plain), nv1))
-            raw = o.download()[:nv1 * 12].tobytes()
-            res.append([int.from_bytes(raw[96 * i:96 * i + 96], "little") for i in range(nv1)])
+            into_repr(gl, field, o, nv1)
+            res.append(ints_from_canon_rows(o.download()[:nv1 * 12]))
         return tuple(res)
-    finally:
-        for buf in [d_u] + outs:
-            buf.free()
 
 
-def _mont_rows(vals, modulus):
-    """Python integers -> n x 12 u64 Montgomery rows (x * 2^768 mod p), the in-memory form of Fp768 (fp_768.rs:24-30)"""
-    R = (1 << 768) % modulus
-    out = np.zeros((len(vals), 12), dtype=np.uint64)
-    mask = (1 << 64) - 1
-    for i, v in enumerate(vals):
-        x = v * R % modulus
-        for k in range(12):
-            out[i, k] = (x >> (64 * k)) & mask
-    return out
-
-
-def _canon_rows(vals):
-    out = np.zeros((len(vals), 12), dtype=np.uint64)
-    mask = (1 << 64) - 1
-    for i, v in enumerate(vals):
-        for k in range(12):
-            out[i, k] = (v >> (64 * k)) & mask
-    return out
-
-
-def affine_to_wire(pairing, group, xy, is_infinity):
-    """GroupAffine::write of an affine result (Montgomery x || y limbs from gh_proj_to_affine): canonical little-endian
-    coefficients + infinity byte; zero() is written as (0, 1, true) (swp.rs:130-132)."""
-    p = _MODULUS["mnt6753" if pairing == "mnt4753" else "mnt4753"]      # base field of the pairing's curves
-    deg = 1 if group == "g1" else _G2_DEG[pairing]
-    rinv = pow(1 << 768, -1, p)
-    v = [int(x) for x in np.asarray(xy, dtype=np.uint64).ravel()]
-    out = bytearray()
-    for c in range(2 * deg):
-        m = sum(v[12 * c + k] << (64 * k) for k in range(12))
-        out += (m * rinv % p).to_bytes(_FQ_BYTES, "little")
-    out.append(1 if is_infinity else 0)
-    return bytes(out)
-
-
-class ResidentProvingKey:
+class ResidentProvingKey(ResidentQueries):
     """pk: dict of numpy arrays in the ABI formats (Montgomery x||y rows, all points finite):
     alpha_g1, beta_g1, delta_g1 (24 u64), beta_g2, delta_g2 (24*deg u64), a_query, b_g1_query, h_query,
     l_query (n x 24), b_g2_query (n x 24*deg).
@@ -307,9 +251,7 @@ class ResidentProvingKey:
     the latency of a full bucket reduction."""
 
     def __init__(self, gl, pairing, pk, num_inputs, precompute=True):
-        assert pairing in ("mnt4753", "mnt6753")
-        self.gl, self.pk, self.num_inputs = gl, pk, int(num_inputs)
-        self.g1, self.g2 = pairing + "_g1", pairing + "_g2"
+        super().__init__(gl, pairing, num_inputs)
         row = lambda v: np.asarray(v, dtype=np.uint64).reshape(1, -1)
         def ext(q, c, d, delta_last):       # q[1..] || q[0] || c || (delta, infinity) or (infinity, delta)
             dl = row(pk[d])
@@ -318,20 +260,11 @@ class ResidentProvingKey:
             inf = np.zeros(len(rows), dtype=np.uint8)
             inf[-2 if delta_last else -1] = 1
             return rows, inf
-        vectors = {"a": (self.g1,) + ext("a_query", "alpha_g1", "delta_g1", False),
-                   "b1": (self.g1,) + ext("b_g1_query", "beta_g1", "delta_g1", True),
-                   "b2": (self.g2,) + ext("b_g2_query", "beta_g2", "delta_g2", True),
-                   "h": (self.g1, np.ascontiguousarray(pk["h_query"], dtype=np.uint64), None),
-                   "l": (self.g1, np.ascontiguousarray(pk["l_query"], dtype=np.uint64), None)}
-        self.keys = {}
-        for name, (curve, rows, inf) in vectors.items():
-            rb = gl.ResidentBases(curve, rows, infinity=inf)
-            if precompute and rb.n:
-                try:
-                    rb.precompute(0)
-                except gl.GingerHipError:
-                    pass                      # no memory for the table / a point of 2-power order: per-window path
-            self.keys[name] = rb
+        self._init_queries({"a": (self.g1,) + ext("a_query", "alpha_g1", "delta_g1", False),
+                            "b1": (self.g1,) + ext("b_g1_query", "beta_g1", "delta_g1", True),
+                            "b2": (self.g2,) + ext("b_g2_query", "beta_g2", "delta_g2", True),
+                            "h": (self.g1, np.ascontiguousarray(pk["h_query"], dtype=np.uint64), None),
+                            "l": (self.g1, np.ascontiguousarray(pk["l_query"], dtype=np.uint64), None)}, pk["delta_g1"], precompute)
 
     @classmethod
     def from_parameters(cls, gl, pairing, blob, num_inputs, precompute=True):
@@ -339,94 +272,80 @@ class ResidentProvingKey:
         device in its serialised form (gh_bases_upload_wire: canonical coefficients, infinity flags honoured -- keys made by
         the reference generator contain GroupAffine::zero() entries wherever a variable does not occur in A or B)."""
         self = cls.__new__(cls)
-        self.gl, self.num_inputs = gl, int(num_inputs)
-        self.g1, self.g2 = pairing + "_g1", pairing + "_g2"
+        ResidentQueries.__init__(self, gl, pairing, num_inputs)
         pk = parse_parameters(pairing, blob)
-        self.pk = pk
-        self.pairing = pairing
-        r1, r2 = 2 * _FQ_BYTES + 1, 2 * _FQ_BYTES * _G2_DEG[pairing] + 1
+        r1, r2 = 2 * FQ_BYTES + 1, 2 * FQ_BYTES * G2_DEG[pairing] + 1
         def ext(q, c, d, rec, delta_last):  # q[1..] || q[0] || c || (delta, infinity) or (infinity, delta), GroupAffine::write records
             zero = bytes(rec - 1) + b"\x01"                                             # an infinity record: flag byte set
             tail = zero + pk[d] if delta_last else pk[d] + zero
             return pk[q][rec:] + pk[q][:rec] + pk[c] + tail
-        vectors = {"a": (self.g1, ext("a_query", "alpha_g1", "delta_g1", r1, False)),
-                   "b1": (self.g1, ext("b_g1_query", "beta_g1", "delta_g1", r1, True)),
-                   "b2": (self.g2, ext("b_g2_query", "beta_g2", "delta_g2", r2, True)),
-                   "h": (self.g1, pk["h_query"]), "l": (self.g1, pk["l_query"])}
-        self.keys = {}
-        for name, (curve, data) in vectors.items():
-            rb = gl.ResidentBases.from_wire(curve, data)
-            if precompute and rb.n:
-                try:
-                    rb.precompute(0)
-                except gl.GingerHipError:
-                    pass
-            self.keys[name] = rb
-        # delta_g1 as Montgomery limbs for the host-side r * s * delta term: through the device converter (one point)
-        one = gl.ResidentBases.from_wire(self.g1, pk["delta_g1"])
-        self.pk_delta_g1 = one.download(0, 1)[0]
-        one.free()
+        self._init_queries({"a": (self.g1, ext("a_query", "alpha_g1", "delta_g1", r1, False)),
+                            "b1": (self.g1, ext("b_g1_query", "beta_g1", "delta_g1", r1, True)),
+                            "b2": (self.g2, ext("b_g2_query", "beta_g2", "delta_g2", r2, True)),
+                            "h": (self.g1, pk["h_query"]), "l": (self.g1, pk["l_query"])}, pk["delta_g1"], precompute)
         return self
 
-    def free(self):
-        for rb in self.keys.values():
-            rb.free()
+    def _init_queries(self, vectors, delta_g1, precompute):
+        """what both constructors end in: the five queries on the device and delta_g1 as 24 Montgomery limbs for the host-side
+        r * s * delta term (a GroupAffine::write record goes through the device converter, as one point)"""
+        if isinstance(delta_g1, bytes):
+            one = self.gl.ResidentBases.from_wire(self.g1, delta_g1)
+            try:
+                delta_g1 = one.download(0, 1)[0]
+            finally:
+                one.free()
+        self.delta_g1 = np.asarray(delta_g1, dtype=np.uint64).ravel()
+        self._upload(vectors, precompute)
 
     def prepare_rows(self, circuit_rows, d1, d2, d3):
         """The host side of create_proof up to the device boundary: the evaluated constraint rows (Python integers) as
         Montgomery / canonical limb arrays, the way the reference holds them before the witness map (r1cs_to_qap.rs:100-120).
         Separate from prove_prepared so that a caller (bench.py's `prover` object) can time the device stage alone."""
-        pairing = self.pairing
-        modulus = _MODULUS[pairing]
+        modulus = MODULUS[self.pairing]
         num_inputs, assignment, A, B, C = circuit_rows
         assert num_inputs == self.num_inputs
         n_con = len(A)
-        size = 1
-        while size < n_con + (num_inputs - 1) + 1:               # EvaluationDomain::new(num_constraints + num_inputs) (r1cs_to_qap.rs:100)
-            size <<= 1
+        size = domain_size(n_con + num_inputs)                   # EvaluationDomain::new(num_constraints + num_inputs) (r1cs_to_qap.rs:100)
         a = np.zeros((size, 12), dtype=np.uint64)
         b = np.zeros((size, 12), dtype=np.uint64)
         c = np.zeros((size, 12), dtype=np.uint64)
-        a[:n_con] = _mont_rows(A, modulus)
-        b[:n_con] = _mont_rows(B, modulus)
-        c[:n_con] = _mont_rows(C, modulus)
-        a[n_con:n_con + num_inputs] = _mont_rows([1] + list(assignment[1:num_inputs]), modulus)     # :116-118
-        return {"size": size, "a": a, "b": b, "c": c, "dd": _mont_rows([d1, d2, d3], modulus), "scal": _canon_rows(assignment)}
+        a[:n_con] = mont_rows(A, modulus)
+        b[:n_con] = mont_rows(B, modulus)
+        c[:n_con] = mont_rows(C, modulus)
+        a[n_con:n_con + num_inputs] = mont_rows([1] + list(assignment[1:num_inputs]), modulus)     # :116-118
+        return {"size": size, "a": a, "b": b, "c": c, "dd": mont_rows([d1, d2, d3], modulus), "scal": canon_rows(assignment)}
 
     def prove_prepared(self, prep, r, s, timing=None):
         """create_proof (prover.rs:201-345) from prepare_rows' arrays: rows to the device, gh_witness_map_dev, into_repr on the
         device, the five MSMs over the resident key, Proof::write bytes.  timing (a dict) receives wall-clock ms per stage."""
-        import time
-        gl, pairing = self.gl, self.pairing
+        gl = self.gl
         size, num_inputs = prep["size"], self.num_inputs
         log_n = size.bit_length() - 1
-        field = "mnt4753_fr" if pairing == "mnt4753" else "mnt6753_fr"
+        field = FR_FIELD[self.pairing]
         dd, scal = prep["dd"], prep["scal"]
         lib = gl.load_library()
         t0 = time.perf_counter()
-        bufs = [gl.DeviceBuffer(size * 96 + 96) for _ in range(4)]
-        try:
+        with contextlib.ExitStack() as stack:
+            bufs = [stack.enter_context(gl.DeviceBuffer(size * 96 + 96)) for _ in range(4)]
             for buf, arr in zip(bufs, (prep["a"], prep["b"], prep["c"])):
                 buf.upload(arr)
             lib.gh_dev_sync()
             t1 = time.perf_counter()
             gl._check(lib.gh_witness_map_dev(gl.FIELDS[field], bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, log_n, gl._ptr(dd[0]), gl._ptr(dd[1]),
                                              gl._ptr(dd[2]), bufs[3].ptr))
-            one_plain = np.zeros(12, dtype=np.uint64)
-            one_plain[0] = 1
-            gl._check(lib.gh_vec_scale_dev(gl.FIELDS[field], bufs[3].ptr, gl._ptr(one_plain), size + 1))      # into_repr of h (:256-267)
+            into_repr(gl, field, bufs[3], size + 1)                                                             # h (:256-267)
             lib.gh_dev_sync()
             t2 = time.perf_counter()
-            self.pk = dict(self.pk, delta_g1=self.pk_delta_g1)
-            A_, B_, C_ = self.create_proof_msms(scal[1:num_inputs], scal[num_inputs:], None, None, _canon_rows([r])[0], _canon_rows([s])[0],
-                                                h_dev=(bufs[3], self.keys["h"].n))
+            proof = self.create_proof_msms(scal[1:num_inputs], scal[num_inputs:], None, None, canon_rows([r])[0], canon_rows([s])[0],
+                                           h_dev=(bufs[3], self.keys["h"].n))
             t3 = time.perf_counter()
-        finally:
-            for buf in bufs:
-                buf.free()
         if timing is not None:
             timing.update(rows_upload_ms=(t1 - t0) * 1e3, witness_map_ms=(t2 - t1) * 1e3, msm_stage_ms=(t3 - t2) * 1e3)
-        return affine_to_wire(pairing, "g1", *A_) + affine_to_wire(pairing, "g2", *B_) + affine_to_wire(pairing, "g1", *C_)
+        return self._proof_bytes(proof)
+
+    def _proof_bytes(self, proof):
+        """Proof::write (mod.rs:35-42) of create_proof_msms' three points"""
+        return b"".join(affine_to_wire(self.pairing, group, *pt) for group, pt in zip(("g1", "g2", "g1"), proof))
 
     def create_proof(self, circuit_rows, d1, d2, d3, r, s):
         """create_proof (prover.rs:201-345) for evaluated constraint rows: circuit_rows = (num_inputs, assignment, A, B, C) as
@@ -441,101 +360,52 @@ class ResidentProvingKey:
         scalars_dev = (DeviceBuffer of at least n + 4 rows, n), with h_dev: input || aux already on the device as canonical
         scalars in the buffer's first n rows (gh_r1cs_witness_map_dev's d_scalars); the four rows after them are written
         here, the buffer stays the caller's, and input_assignment / aux_assignment are ignored."""
-        if scalars_dev is not None:
-            return self._msms_from_device(scalars_dev, h_dev, r, s)
-        gl, pk, ni = self.gl, self.pk, self.num_inputs
-        g1, g2 = self.g1, self.g2
-        add, mul = gl.proj_add, gl.proj_mul
-        inp = np.ascontiguousarray(input_assignment, dtype=np.uint64).reshape(-1, 12)
-        aux = np.ascontiguousarray(aux_assignment, dtype=np.uint64).reshape(-1, 12)
-        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(1, 12)
-        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(1, 12)
-        assert len(inp) == ni - 1
-        one = np.zeros((1, 12), dtype=np.uint64)
-        one[0, 0] = 1
+        gl, ni, k = self.gl, self.num_inputs, self.keys
         # the variable part must line up with the query: len(a_query) - 1 scalars (a real key has exactly
         # len(input) + len(aux) of them; a longer aux vector is cut where the reference's zip cuts it, :36)
-        n_var = self.keys["a"].n - 4
-        assert self.keys["b1"].n - 4 == n_var and self.keys["b2"].n - 4 == n_var and n_var >= len(inp)
-        aux_used = aux[:n_var - len(inp)]
-        pad = np.zeros((n_var - len(inp) - len(aux_used), 12), dtype=np.uint64)
-        # ONE scalar vector  input || aux || 1 || 1 || r || s  for the a, b_g1 and b_g2 queries (each key pairs the blinding scalar
-        # it does not use with an infinity base); the aux part alone is the l_query's vector.
-        # (uploaded piecewise: concatenating 100 MB host vectors first costs more than the MSM stage's sort)
-        import ctypes
-        lib = gl.load_library()
-        rows_total = n_var + 4
-        d_r = gl.DeviceBuffer(rows_total * 96)
-        row = 0
-        for part in (inp, aux_used, pad, np.concatenate([one, one, r, s])):
-            if len(part):
-                part = np.ascontiguousarray(part, dtype=np.uint64)
-                gl._check(lib.gh_dev_upload(ctypes.c_void_p(d_r.ptr.value + row * 96), gl._ptr(part), part.nbytes))
-                row += len(part)
-        assert row == rows_total
-        d_s = d_r
-
-        class _View:                          # aux_assignment inside d_r
-            def __init__(self, buf, row0):
-                import ctypes
-                self.ptr = ctypes.c_void_p(buf.ptr.value + row0 * 96)
-        if h_dev is not None:
-            d_h, n_h, own_h = h_dev[0], int(h_dev[1]), False
-        else:
-            h_all = np.concatenate([np.ascontiguousarray(h_input_assignment, dtype=np.uint64).reshape(-1, 12),
-                                    np.ascontiguousarray(h_aux_assignment, dtype=np.uint64).reshape(-1, 12)])
-            d_h, n_h, own_h = gl.DeviceBuffer(max(96, h_all.nbytes)).upload(h_all), len(h_all), True
-        # l_query pairs with the whole aux vector: normally the aux part of d_r, else (aux longer than the a / b
-        # queries use) its own upload
-        own_l = len(aux_used) != len(aux)
-        d_l = gl.DeviceBuffer(max(96, aux.nbytes)).upload(aux) if own_l else _View(d_r, ni - 1)
-        k = self.keys
-        g_a, g1_b, h_acc, l_acc = gl.msm_batch_dev([
-            (k["a"], d_r, n_var + 4), (k["b1"], d_s, n_var + 4), (k["h"], d_h, n_h), (k["l"], d_l, len(aux))])
-        g2_b = k["b2"].msm_dev(d_s, n_var + 4)
-        d_r.free()
-        if own_l:
-            d_l.free()
-        if own_h:
-            d_h.free()
-        # Compute C  (prover.rs:319-337):  s * g_a + r * g1_b - (r s) * delta_g1 + l + h
-        delta = np.zeros(36, dtype=np.uint64)
-        delta[:24] = np.asarray(pk["delta_g1"], dtype=np.uint64).ravel()
-        delta[24:] = gl.field_one(g1)
-        g_c = add(g1, mul(g1, g_a, s), mul(g1, g1_b, r))
-        g_c = add(g1, g_c, gl.proj_neg(g1, mul(g1, mul(g1, delta, r), s)))
-        g_c = add(g1, g_c, l_acc)
-        g_c = add(g1, g_c, h_acc)
-        return gl.proj_to_affine(g1, g_a), gl.proj_to_affine(g2, g2_b), gl.proj_to_affine(g1, g_c)
-
-    def _msms_from_device(self, scalars_dev, h_dev, r, s):
-        """create_proof_msms over input || aux already on the device: the same five MSMs over the same scalar vector
-        input || aux || 1 || 1 || r || s, of which only the last four rows come from the host; then C as there"""
-        import ctypes
-        gl, pk, ni = self.gl, self.pk, self.num_inputs
-        g1, g2 = self.g1, self.g2
-        add, mul = gl.proj_add, gl.proj_mul
-        d_r, n = scalars_dev[0], int(scalars_dev[1])
-        d_h, n_h = h_dev[0], int(h_dev[1])
-        n_var = self.keys["a"].n - 4
-        if n != n_var or self.keys["b1"].n - 4 != n_var or self.keys["b2"].n - 4 != n_var or d_r.nbytes < (n + 4) * 96:
-            raise ValueError("the scalar vector must hold one row per variable of the key's queries, and room for four more")
+        n_var = k["a"].n - 4
+        if k["b1"].n - 4 != n_var or k["b2"].n - 4 != n_var:
+            raise ValueError("the a, b_g1 and b_g2 queries of the key differ in length")
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(1, 12)
         s = np.ascontiguousarray(s, dtype=np.uint64).reshape(1, 12)
-        one = np.zeros((1, 12), dtype=np.uint64)
-        one[0, 0] = 1
-        tail = np.ascontiguousarray(np.concatenate([one, one, r, s]), dtype=np.uint64)
-        gl._check(gl.load_library().gh_dev_upload(ctypes.c_void_p(d_r.ptr.value + n * 96), gl._ptr(tail), tail.nbytes))
+        one = canon_rows([1])
+        tail = np.concatenate([one, one, r, s])
+        if scalars_dev is not None:
+            d_s, n = scalars_dev[0], int(scalars_dev[1])
+            if n != n_var or d_s.nbytes < (n + 4) * 96:
+                raise ValueError("the scalar vector must hold one row per variable of the key's queries, and room for four more")
+            upload_rows(gl, d_s, [tail], n)
+            return self._msm_stage(d_s, r, s, h_dev[0], int(h_dev[1]), RowView(d_s, ni - 1), n - (ni - 1))
+        inp = np.ascontiguousarray(input_assignment, dtype=np.uint64).reshape(-1, 12)
+        aux = np.ascontiguousarray(aux_assignment, dtype=np.uint64).reshape(-1, 12)
+        assert len(inp) == ni - 1 and n_var >= len(inp)
+        aux_used = aux[:n_var - len(inp)]
+        pad = np.zeros((n_var - len(inp) - len(aux_used), 12), dtype=np.uint64)
+        with contextlib.ExitStack() as stack:
+            alloc = lambda nbytes: stack.enter_context(gl.DeviceBuffer(nbytes))
+            d_s = alloc((n_var + 4) * 96)
+            assert upload_rows(gl, d_s, (inp, aux_used, pad, tail)) == n_var + 4
+            if h_dev is not None:
+                d_h, n_h = h_dev[0], int(h_dev[1])
+            else:
+                h_all = np.concatenate([np.ascontiguousarray(h_input_assignment, dtype=np.uint64).reshape(-1, 12),
+                                        np.ascontiguousarray(h_aux_assignment, dtype=np.uint64).reshape(-1, 12)])
+                d_h, n_h = alloc(max(96, h_all.nbytes)).upload(h_all), len(h_all)
+            # l_query pairs with the whole aux vector: normally the aux part of d_s, else (aux longer than the a / b
+            # queries use) its own upload
+            d_l = RowView(d_s, ni - 1) if len(aux_used) == len(aux) else alloc(max(96, aux.nbytes)).upload(aux)
+            return self._msm_stage(d_s, r, s, d_h, n_h, d_l, len(aux))
 
-        class _View:                          # aux_assignment inside d_r
-            ptr = ctypes.c_void_p(d_r.ptr.value + (ni - 1) * 96)
-        k = self.keys
-        g_a, g1_b, h_acc, l_acc = gl.msm_batch_dev([
-            (k["a"], d_r, n + 4), (k["b1"], d_r, n + 4), (k["h"], d_h, n_h), (k["l"], _View, n - (ni - 1))])
-        g2_b = k["b2"].msm_dev(d_r, n + 4)
-        delta = np.zeros(36, dtype=np.uint64)
-        delta[:24] = np.asarray(pk["delta_g1"], dtype=np.uint64).ravel()
-        delta[24:] = gl.field_one(g1)
+    def _msm_stage(self, d_s, r, s, d_h, n_h, d_l, n_l):
+        """The five MSMs and C.  d_s: ONE device scalar vector  input || aux || 1 || 1 || r || s  for the a, b_g1 and b_g2 queries
+        (each key pairs the blinding scalar it does not use with an infinity base); d_h, n_h: the coefficients of h; d_l, n_l:
+        the aux assignment for the l_query, a view into d_s or a buffer of its own.  All buffers stay the caller's."""
+        gl, g1, g2, k = self.gl, self.g1, self.g2, self.keys
+        add, mul = gl.proj_add, gl.proj_mul
+        g_a, g1_b, h_acc, l_acc = gl.msm_batch_dev([(k["a"], d_s, k["a"].n), (k["b1"], d_s, k["a"].n), (k["h"], d_h, n_h), (k["l"], d_l, n_l)])
+        g2_b = k["b2"].msm_dev(d_s, k["a"].n)
+        # Compute C  (prover.rs:319-337):  s * g_a + r * g1_b - (r s) * delta_g1 + l + h
+        delta = np.concatenate([self.delta_g1, gl.field_one(g1)])
         g_c = add(g1, mul(g1, g_a, s), mul(g1, g1_b, r))
         g_c = add(g1, g_c, gl.proj_neg(g1, mul(g1, mul(g1, delta, r), s)))
         g_c = add(g1, g_c, l_acc)
@@ -548,38 +418,30 @@ class ResidentProvingKey:
         gh_r1cs_witness_map_dev evaluates the constraint rows there, runs the witness map and leaves input || aux as
         canonical scalars for the five MSMs.  Returns Proof::write bytes: those of create_proof on the same circuit.
         timing (a dict) receives wall-clock ms per stage."""
-        import time
-        gl, pairing = self.gl, self.pairing
-        modulus = _MODULUS[pairing]
-        field = "mnt4753_fr" if pairing == "mnt4753" else "mnt6753_fr"
+        gl = self.gl
+        modulus = MODULUS[self.pairing]
         if r1cs.num_inputs != self.num_inputs:
             raise ValueError("the constraint system and the key disagree on the number of inputs")
-        z = assignment if isinstance(assignment, np.ndarray) else _mont_rows(list(assignment), modulus)
+        z = assignment if isinstance(assignment, np.ndarray) else mont_rows(list(assignment), modulus)
         z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 12)
         nv, size = r1cs.num_variables, r1cs.size
         if len(z) != nv:
             raise ValueError("the assignment must have one row per variable")
-        dd = _mont_rows([d1, d2, d3], modulus)
+        dd = mont_rows([d1, d2, d3], modulus)
         lib = gl.load_library()
         t0 = time.perf_counter()
-        d_z, d_h, d_s = gl.DeviceBuffer(nv * 96), gl.DeviceBuffer(size * 96 + 96), gl.DeviceBuffer((nv + 3) * 96)
-        try:
+        with contextlib.ExitStack() as stack:
+            d_z, d_h, d_s = (stack.enter_context(gl.DeviceBuffer(nbytes)) for nbytes in (nv * 96, size * 96 + 96, (nv + 3) * 96))
             d_z.upload(z)
             lib.gh_dev_sync()
             t1 = time.perf_counter()
             r1cs.witness_map_dev(d_z, dd, d_h, d_s)
-            one_plain = np.zeros(12, dtype=np.uint64)
-            one_plain[0] = 1
-            gl._check(lib.gh_vec_scale_dev(gl.FIELDS[field], d_h.ptr, gl._ptr(one_plain), size + 1))          # into_repr of h (:256-267)
+            into_repr(gl, FR_FIELD[self.pairing], d_h, size + 1)                                                # h (:256-267)
             lib.gh_dev_sync()
             t2 = time.perf_counter()
-            self.pk = dict(self.pk, delta_g1=self.pk_delta_g1)
-            A_, B_, C_ = self.create_proof_msms(None, None, None, None, _canon_rows([r])[0], _canon_rows([s])[0],
-                                                h_dev=(d_h, self.keys["h"].n), scalars_dev=(d_s, nv - 1))
+            proof = self.create_proof_msms(None, None, None, None, canon_rows([r])[0], canon_rows([s])[0],
+                                           h_dev=(d_h, self.keys["h"].n), scalars_dev=(d_s, nv - 1))
             t3 = time.perf_counter()
-        finally:
-            for buf in (d_z, d_h, d_s):
-                buf.free()
         if timing is not None:
             timing.update(assignment_upload_ms=(t1 - t0) * 1e3, witness_map_ms=(t2 - t1) * 1e3, msm_stage_ms=(t3 - t2) * 1e3)
-        return affine_to_wire(pairing, "g1", *A_) + affine_to_wire(pairing, "g2", *B_) + affine_to_wire(pairing, "g1", *C_)
+        return self._proof_bytes(proof)

@@ -22,7 +22,7 @@ c0.c1, c0.c2, c1.c0, c1.c1, c1.c2 (Fp6::write, 576 bytes), a G2 record 577 bytes
 import numpy as np
 
 from . import GingerHipError, _check, _ptr    # noqa: F401 (GingerHipError: re-exported)
-from . import _handles, groth16
+from . import _handles, groth16, limbs
 from ._handles import _bytes, _rows, ci, sz, vp
 
 _ARGTYPES = {"gh_pairing_product": [ci, vp, vp, vp, vp, sz, sz, vp],
@@ -41,9 +41,9 @@ class _Widths:
     """what an engine's layouts are made of: deg Fq coefficients per G2 coordinate and per half of a GT element"""
 
     def __init__(self, engine):
-        self.deg = groth16._G2_DEG[engine]
-        self.fq = groth16._MODULUS["mnt6753" if engine == "mnt4753" else "mnt4753"]     # the base field is the other curve's Fr
-        self.fr = groth16._MODULUS[engine]
+        self.deg = limbs.G2_DEG[engine]
+        self.fq = limbs.base_modulus(engine)
+        self.fr = limbs.MODULUS[engine]
         self.g2_words = self.gt_words = 24 * self.deg
         self.g2_rec = 192 * self.deg + 1
         self.gt_bytes = 192 * self.deg
@@ -86,7 +86,7 @@ def gt_to_bytes(gt, engine="mnt4753"):
     """one Fq4 row (48 Montgomery limbs) -> its Fp4::write bytes: 4 x 96 canonical little-endian; over MNT6-753 one Fq6 row
     (72 limbs) -> the 6 x 96 bytes of Fp6::write"""
     w = _WIDTHS[engine]
-    ints = groth16._ints_from_mont_rows(np.asarray(gt, dtype=np.uint64).reshape(2 * w.deg, 12), w.fq)
+    ints = limbs.ints_from_mont_rows(np.asarray(gt, dtype=np.uint64).reshape(2 * w.deg, 12), w.fq)
     return b"".join(int(v).to_bytes(96, "little") for v in ints)
 
 
@@ -105,7 +105,7 @@ def _wire_rows(data, rec, coeffs, engine="mnt4753"):
             if v >= fq:
                 raise ValueError("a coordinate is not below the modulus")
             vals.append(v)
-    return groth16._mont_rows(vals, fq).reshape(n, 12 * coeffs), inf
+    return limbs.mont_rows(vals, fq).reshape(n, 12 * coeffs), inf
 
 
 class PreparedVerifyingKey(_handles.Handle):
@@ -134,7 +134,7 @@ class PreparedVerifyingKey(_handles.Handle):
         if any(v >= w.fq for v in gt):
             raise ValueError("alpha_g1_beta_g2 is not an element of the target field (the filler of groth16.generate_parameters? "
                              "see parameters_with_pairing)")
-        gt = groth16._mont_rows(gt, w.fq)
+        gt = limbs.mont_rows(gt, w.fq)
         g, gi = _wire_rows(pk["vk_gamma_g2"], w.g2_rec, 2 * w.deg, pairing)
         d, di = _wire_rows(pk["vk_delta_g2"], w.g2_rec, 2 * w.deg, pairing)
         abc, ai = _wire_rows(pk["vk_gamma_abc_g1"], _G1_REC, 2, pairing)
@@ -187,7 +187,7 @@ def verify_proofs(pvk, proofs, inputs):
     flat = [int(v) for row in inputs for v in row]
     if any(v < 0 or v >= w.fr for v in flat):
         raise ValueError("a public input is not below the modulus")
-    x = groth16._mont_rows(flat, w.fr).reshape(n, pvk.num_inputs * 12)
+    x = limbs.mont_rows(flat, w.fr).reshape(n, pvk.num_inputs * 12)
     return pvk.verify(a, b, c, x)
 
 

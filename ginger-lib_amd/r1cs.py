@@ -17,11 +17,11 @@ import numpy as np
 
 from . import FIELDS, DeviceBuffer, GingerHipError, _check, _ptr    # noqa: F401 (GingerHipError: re-exported)
 from . import _handles
+from .limbs import FR_FIELD, MODULUS, mont_rows
 from ._handles import _rows, ci, sz, u32, vp
 
 MATRICES = ("A", "B", "C")
 CLASSES = ("zero", "one", "minus_one", "small", "minus_small", "general")
-_FIELD_OF = {"mnt4753": "mnt4753_fr", "mnt6753": "mnt6753_fr"}
 
 
 class Matrix(ctypes.Structure):
@@ -62,12 +62,7 @@ def flatten(rows, modulus):
             cols.append(ix)
             ids.append(values.setdefault(int(cf) % modulus, len(values)))
         row_ptr[i + 1] = len(cols)
-    mont = np.zeros((len(values), 12), dtype=np.uint64)
-    R = (1 << 768) % modulus
-    for v, k in values.items():
-        x = v * R % modulus
-        mont[k] = [(x >> (64 * j)) & 0xffffffffffffffff for j in range(12)]
-    return row_ptr, np.array(cols, dtype=np.uint32), np.array(ids, dtype=np.uint32), mont
+    return row_ptr, np.array(cols, dtype=np.uint32), np.array(ids, dtype=np.uint32), mont_rows(values, modulus)     # in order of first use
 
 
 def last_timing(max_phases=40):
@@ -80,44 +75,34 @@ class ResidentR1CS:
     """A, B, C of one circuit on the device, in both orientations.  segment_terms: 0 = the library's default."""
 
     def __init__(self, gl, pairing, lcs, segment_terms=0):
-        from .groth16 import _MODULUS
-        self.gl, self.pairing = gl, pairing
-        self.field = FIELDS[_FIELD_OF[pairing]]
-        self.modulus = _MODULUS[pairing]
-        self.num_inputs, self.num_aux, at, bt, ct = lcs
-        self.num_constraints = len(at)
+        num_inputs, num_aux, at, bt, ct = lcs
         if len(bt) != len(at) or len(ct) != len(at):
             raise ValueError("at, bt and ct must have one row per constraint")
-        self.num_variables = self.num_inputs + self.num_aux
-        keep = [flatten(rows, self.modulus) for rows in (at, bt, ct)]          # alive across the call
-        self.handle = None
-        self._upload(keep, segment_terms)
-        self.log_n = self.info()["log_n"]
-        self.size = 1 << self.log_n
+        self._init(gl, pairing, num_inputs, num_aux, len(at), [flatten(rows, MODULUS[pairing]) for rows in (at, bt, ct)], segment_terms)
 
-    def _upload(self, arrays, segment_terms):
+    def _init(self, gl, pairing, num_inputs, num_aux, num_constraints, arrays, segment_terms):
+        """arrays: three (row_ptr, col, coeff_id, coeff_values) tuples of contiguous arrays, alive across the call"""
+        self.gl, self.pairing = gl, pairing
+        self.field, self.modulus = FIELDS[FR_FIELD[pairing]], MODULUS[pairing]
+        self.num_inputs, self.num_aux, self.num_constraints = int(num_inputs), int(num_aux), int(num_constraints)
+        self.num_variables = self.num_inputs + self.num_aux
+        self.handle = None
         ms = (Matrix * 3)()
         for m, (row_ptr, col, ids, vals) in zip(ms, arrays):
             m.row_ptr, m.col, m.coeff_id, m.coeff_values, m.num_coeffs = _ptr(row_ptr), _ptr(col), _ptr(ids), _ptr(vals), len(vals)
         h = vp()
         _check(_lib().gh_r1cs_upload(self.field, self.num_inputs, self.num_aux, self.num_constraints, ms, segment_terms, ctypes.byref(h)))
         self.handle = h
+        self.log_n = self.info()["log_n"]
+        self.size = 1 << self.log_n
 
     @classmethod
     def from_csr(cls, gl, pairing, num_inputs, num_aux, num_constraints, matrices, segment_terms=0):
         """the same from three (row_ptr, col, coeff_id, coeff_values) tuples in the C ABI's form"""
-        from .groth16 import _MODULUS
         self = cls.__new__(cls)
-        self.gl, self.pairing = gl, pairing
-        self.field, self.modulus = FIELDS[_FIELD_OF[pairing]], _MODULUS[pairing]
-        self.num_inputs, self.num_aux, self.num_constraints = int(num_inputs), int(num_aux), int(num_constraints)
-        self.num_variables = self.num_inputs + self.num_aux
         keep = [(np.ascontiguousarray(p, dtype=np.uint64), np.ascontiguousarray(c, dtype=np.uint32), np.ascontiguousarray(k, dtype=np.uint32),
                  np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 12)) for p, c, k, v in matrices]
-        self.handle = None
-        self._upload(keep, segment_terms)
-        self.log_n = self.info()["log_n"]
-        self.size = 1 << self.log_n
+        self._init(gl, pairing, num_inputs, num_aux, num_constraints, keep, segment_terms)
         return self
 
     def free(self):

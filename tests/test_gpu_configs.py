@@ -431,12 +431,58 @@ def test_cfg5_benchmark_circuit_2p20_end_to_end(gpu):
     proofs = []
     for precompute in (True, False):
         key = groth16.ResidentProvingKey(gpu, pairing, pk, ni, precompute=precompute)
-        key.pairing, key.pk_delta_g1 = pairing, pk["delta_g1"]
         try:
             proofs.append(key.create_proof(rows, d1, d2, d3, r_, s_))
         finally:
             key.free()
     assert proofs[0] == proofs[1] and len(proofs[0]) == 193 + 385 + 193
+    gpu.dev_trim()
+
+
+@pytest.mark.parametrize("pairing", ["mnt4753", "mnt6753"])
+def test_cfg5_key_from_arrays_equals_key_from_stream(gpu, pairing):
+    """Both constructors of ResidentProvingKey give a whole key: the same points as limb arrays (__init__) and as a
+    Parameters::write stream (from_parameters) yield the same create_proof bytes with non-zero d1, d2, d3, and
+    create_proof_r1cs over the same circuit yields them too.  `Benchmark` circuit with 13 constraints (domain 16, three inputs).
+    The key is the synthetic chain-point key of test_groth16_stage.py, written out as a stream here: a key generated at this
+    size holds GroupAffine::zero() entries inside a_query (1) and the b queries (2), which the array form cannot express."""
+    import struct
+    import groth16_ref as G
+    groth16 = importlib.import_module("ginger_lib_amd.groth16")
+    r1cs = importlib.import_module("ginger_lib_amd.r1cs")
+    n_con = 13
+    rows = groth16.benchmark_circuit_rows(pairing, n_con)
+    ni, nv = rows[0], len(rows[1])
+    assert (ni, nv) == (3, 16)
+    C1, C2 = pyref.CURVES[pairing + "_g1"], pyref.CURVES[pairing + "_g2"]
+    rng = pyref.Rng(1300)
+    pool1, pool2 = S.chain_points(C1, 48, rng), S.chain_points(C2, 24, rng)
+    pts = {"a_query": [pool1[(5 * i + 1) % 48] for i in range(nv)], "b_g1_query": [pool1[(7 * i + 2) % 48] for i in range(nv)],
+           "b_g2_query": [pool2[(5 * i + 2) % 24] for i in range(nv)], "h_query": [pool1[(11 * i + 3) % 48] for i in range(15)],
+           "l_query": [pool1[(13 * i + 4) % 48] for i in range(nv - ni)],
+           "alpha_g1": [pool1[40]], "beta_g1": [pool1[41]], "delta_g1": [pool1[42]], "beta_g2": [pool2[3]], "delta_g2": [pool2[9]]}
+    curve_of = lambda name: C2 if name.endswith("g2") or name == "b_g2_query" else C1
+    pk = {name: S.bases_array(curve_of(name), p)[0] for name, p in pts.items()}
+    pk.update({name: pk[name][0] for name in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2")})
+    w = lambda name: b"".join(G.wire(curve_of(name), P) for P in pts[name])
+    vec = lambda data, n: struct.pack(">I", n) + data
+    blob = (bytes(96 * 2 * C2.deg) + w("beta_g2") + w("delta_g2") + vec(b"".join(G.wire(C1, P) for P in pool1[:ni]), ni) +
+            w("alpha_g1") + w("beta_g1") + w("beta_g2") + w("delta_g1") + w("delta_g2") +
+            b"".join(vec(w(q), len(pts[q])) for q in ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query")))
+    d1, d2, d3, r_, s_ = (rng.field_elem(C1.order) for _ in range(5))
+    assert d1 and d2 and d3
+    proofs = []
+    res = r1cs.ResidentR1CS(gpu, pairing, groth16.benchmark_circuit_lcs(n_con))
+    try:
+        for make in (lambda: groth16.ResidentProvingKey.from_parameters(gpu, pairing, blob, ni), lambda: groth16.ResidentProvingKey(gpu, pairing, pk, ni)):
+            with make() as key:
+                assert key.pairing == pairing and (key.delta_g1 == pk["delta_g1"]).all()
+                proofs.append(key.create_proof(rows, d1, d2, d3, r_, s_))
+                proofs.append(key.create_proof_r1cs(res, rows[1], d1, d2, d3, r_, s_))
+    finally:
+        res.free()
+    assert len(proofs[0]) == 193 + 192 * C2.deg + 1 + 193 and proofs[0][192] == 0 and proofs[0][-1] == 0        # finite A and C
+    assert proofs[1] == proofs[0] and proofs[2] == proofs[0] and proofs[3] == proofs[0]
     gpu.dev_trim()
 
 

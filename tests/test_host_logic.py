@@ -17,7 +17,7 @@ def mods(gl):
 @pytest.mark.parametrize("pairing,n_con", [("mnt4753", 30), ("mnt6753", 17)])
 def test_benchmark_lcs_agree_with_rows(mods, pairing, n_con):
     groth16, _ = mods
-    r = groth16._MODULUS[pairing]
+    r = importlib.import_module("ginger_lib_amd.limbs").MODULUS[pairing]
     ni, n_aux, at, bt, ct = groth16.benchmark_circuit_lcs(n_con)
     ni2, asg, A, B, C = groth16.benchmark_circuit_rows(pairing, n_con)
     assert ni == ni2 == 3 and len(asg) == ni + n_aux and len(at) == len(bt) == len(ct) == n_con

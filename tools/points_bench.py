@@ -78,7 +78,7 @@ def main():
     from __graft_entry__ import _load_pkg
     gl = _load_pkg()
     gl.init()
-    from ginger_lib_amd import groth16, pairing, points
+    from ginger_lib_amd import limbs, pairing, points
     peak = gl.measure_fpmul_peak()
     C = json.load(open(os.path.join(GOLDEN, "constants.json")))
     consts = json.load(open(os.path.join(GOLDEN, "pairing_constants.json" if eng == "mnt4753" else "pairing6_constants.json")))
@@ -87,7 +87,7 @@ def main():
     p, r = int(C["fields"]["p4"]["p"], 16), int(C["fields"]["p6"]["p"], 16)
     if eng == "mnt6753":
         p, r = r, p                                             # the cycle: MNT6-753's base field is MNT4-753's group order
-    mont = lambda vals: groth16._mont_rows(vals, p).reshape(-1)
+    mont = lambda vals: limbs.mont_rows(vals, p).reshape(-1)
     c1, c2 = C["curves"][eng + "_g1"], C["curves"][eng + "_g2"]
     deg = len(c2["gx"])
     g1_xyz = mont([int(c1["gx"][0], 16), int(c1["gy"][0], 16), 1])
@@ -108,7 +108,7 @@ def main():
     abc = g1(ks + [alpha])
     gt = pairing.pairing_product((abc[0][-1:], abc[1][-1:]), (vk2[0][2:], vk2[1][2:]), engine=eng)
     pvk = pairing.PreparedVerifyingKey(gt, vk2[0][0], vk2[0][1], abc[0][:-1], engine=eng)
-    X = groth16._mont_rows([u for xs in xv for u in xs], r).reshape(DISTINCT, N_INPUTS * 12)
+    X = limbs.mont_rows([u for xs in xv for u in xs], r).reshape(DISTINCT, N_INPUTS * 12)
     t1.free()
     t2.free()
     n1, n2 = eng + "_g1", eng + "_g2"

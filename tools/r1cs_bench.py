@@ -43,9 +43,10 @@ def rehearse(args):
     from __graft_entry__ import _load_pkg
     _load_pkg()
     groth16 = importlib.import_module("ginger_lib_amd.groth16")
+    limbs = importlib.import_module("ginger_lib_amd.limbs")
     r1cs = importlib.import_module("ginger_lib_amd.r1cs")
     pairing, n = "mnt4753", 61
-    r = groth16._MODULUS[pairing]
+    r = limbs.MODULUS[pairing]
     lcs = groth16.benchmark_circuit_lcs(n)
     num_inputs, assignment, A, B, C = groth16.benchmark_circuit_rows(pairing, n)
     a, b, c = ref.evaluate(lcs, assignment, r)
@@ -74,6 +75,7 @@ def main():
     gl = _load_pkg()
     gl.init()
     groth16 = importlib.import_module("ginger_lib_amd.groth16")
+    limbs = importlib.import_module("ginger_lib_amd.limbs")
     r1cs = importlib.import_module("ginger_lib_amd.r1cs")
     pairing = "mnt4753"
     field = gl.FIELDS["mnt4753_fr"]
@@ -109,7 +111,7 @@ def main():
         t0 = time.perf_counter()
         prep = key.prepare_rows(rows, 0, 0, 0)                 # outside the clock of path (a)
         out["host_prepare_rows_s"] = time.perf_counter() - t0
-        zm = groth16._mont_rows(rows[1], rr)                   # outside the clock of path (b)
+        zm = limbs.mont_rows(rows[1], rr)                   # outside the clock of path (b)
         del rows
         proof_a = key.prove_prepared(prep, r_, s_)             # warm both paths: pools, pipeline slots, domain tables
         proof_b = key.create_proof_r1cs(res, zm, 0, 0, 0, r_, s_)
@@ -141,7 +143,7 @@ def main():
             for _ in range(3):
                 res.evaluate_dev(d_z, *bufs)
                 ev.append(r1cs.last_timing())
-            tau_m = groth16._mont_rows([tau], rr)[0]
+            tau_m = limbs.mont_rows([tau], rr)[0]
             gl._check(gl.load_library().gh_lagrange_coefficients_dev(field, args.log_n, gl._ptr(tau_m), d_u.ptr))
             for _ in range(3):
                 res.instance_map_dev(d_u, *vouts)
