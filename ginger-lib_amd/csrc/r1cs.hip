@@ -1,8 +1,9 @@
 // r1cs.hip -- the C ABI of include/ginger_hip_r1cs.h: the three constraint matrices of an R1CS instance resident on the
 // device, in both orientations, and the sparse products over them.  The schedule of a product is designed on the host
 // (r1cs_plan.h: validation, dictionary classes, transposition, level builder -- all of it host-tested); here are the handle
-// that keeps its arrays on the device, the kernels that execute it and the reference-shaped calls above the products.
-// DESIGN.md section 16.
+// that keeps its arrays on the device, the kernels that execute it and the reference-shaped calls above the products: the QAP
+// maps of Groth16 and, over the same handle and launch helpers, the SAP maps of GM17 (include/ginger_hip_sap.h, sap_rows.h).
+// DESIGN.md sections 16 and 16a.
 //
 // One product: the input vector is converted once to the internal 26 x 29-bit form (r1cs_convert_kernel), level 0 gathers it
 // (one lane per segment, r1cs_term per term), the levels above sum partials; the lane that closes a row writes the ABI row.
@@ -12,7 +13,8 @@
 #include <memory>
 #include "runtime.h"
 #include "r1cs_plan.h"
-#include "../../include/ginger_hip_r1cs.h"
+#include "sap_rows.h"
+#include "../../include/ginger_hip_sap.h"
 
 namespace {
 
@@ -25,18 +27,23 @@ constexpr int BLOCK = 128;
 inline unsigned blocks(size_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 // ---------------------------------------------------------------------------------------------------- kernels
-// xs[i] = x[i] in internal form; scalars (nullable): row i - 1 = the integer x[i] itself (into_repr), i >= 1
+// xs[i] = x[i] in internal form; scalars (nullable): row i - 1 = the integer x[i] itself (into_repr), i >= 1; aux (nullable):
+// the same integer a second time, row i - aux_first, i >= aux_first (the SAP prover's second copy of the aux part)
 template <class P>
 __global__ void __launch_bounds__(BLOCK)
-r1cs_convert_kernel(const uint32_t* __restrict__ x, size_t n, Fp* __restrict__ xs, uint32_t* __restrict__ scalars) {
+r1cs_convert_kernel(const uint32_t* __restrict__ x, size_t n, Fp* __restrict__ xs, uint32_t* __restrict__ scalars, uint32_t* __restrict__ aux,
+                    size_t aux_first) {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const Fp v = fp_from_abi<P>(x + i * 24);
     xs[i] = v;
-    if (scalars && i) {
+    const bool to_aux = aux && i >= aux_first;
+    if ((scalars && i) || to_aux) {
         Fp one = fp_zero();
         one.l[0] = 1;
-        fp_pack(scalars + (i - 1) * 24, fp_mul<P>(v, one));
+        const Fp repr = fp_mul<P>(v, one);
+        if (scalars && i) fp_pack(scalars + (i - 1) * 24, repr);
+        if (to_aux) fp_pack(aux + (i - aux_first) * 24, repr);
     }
 }
 
@@ -89,6 +96,39 @@ r1cs_add_inputs_kernel(const uint32_t* __restrict__ u, size_t nc, size_t ni, uin
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= ni) return;
     fp_pack(a + i * 24, fp_add<P>(fp_unpack(a + i * 24), fp_unpack(u + (nc + i) * 24)));
+}
+
+// ---- GM17's R1CS -> SAP maps (include/ginger_hip_sap.h): the lanes are sap_rows.h's, which the CPU tests run on the host
+// witness rows: one lane per constraint, then one per input (the row of ones first), then one per padding row
+template <class P>
+__global__ void __launch_bounds__(BLOCK)
+sap_rows_kernel(SapShape sh, const uint32_t* __restrict__ az, const uint32_t* __restrict__ bz, const uint32_t* __restrict__ cz,
+                const uint32_t* __restrict__ z, uint32_t* __restrict__ a, uint32_t* __restrict__ c, uint32_t* __restrict__ scalars,
+                uint32_t* __restrict__ aux, uint32_t* __restrict__ full) {
+    const uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (t < sh.rows_lanes()) sap_rows_lane<P>(sh, t, az, bz, cz, z, a, c, scalars, aux, full);
+}
+
+// u -> p, m, q in the internal form, the inputs of the three transposed products: xs[i], xs[nc + i], xs[2 nc + i]
+template <class P>
+__global__ void __launch_bounds__(BLOCK)
+sap_split_kernel(const uint32_t* __restrict__ u, uint64_t nc, Fp* __restrict__ xs) {
+    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= nc) return;
+    Fp p, m, q;
+    sap_split<P>(u, i, p, m, q);
+    xs[i] = p;
+    xs[nc + i] = m;
+    xs[2 * nc + i] = q;
+}
+
+// one lane per row of the instance map's a and c
+template <class P>
+__global__ void __launch_bounds__(BLOCK)
+sap_instance_finish_kernel(SapShape sh, const uint32_t* __restrict__ at_p, const uint32_t* __restrict__ bt_m, const uint32_t* __restrict__ ct_q,
+                           const uint32_t* __restrict__ u, uint32_t* __restrict__ a, uint32_t* __restrict__ c) {
+    const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j < sh.full_rows()) sap_instance_row<P>(sh, j, at_p, bt_m, ct_q, u, a, c);
 }
 
 // ---------------------------------------------------------------------------------------------------- the handle
@@ -249,16 +289,18 @@ struct Scratch {
     Fp* xs = nullptr;
     Fp* part = nullptr;
 };
-int get_scratch(const gh_r1cs* h, Scratch& s) {
-    const size_t n = std::max<size_t>(std::max(h->ni + h->na, h->nc), 1);
+// xs_rows: the converted input vector(s) of the call; 0 = one vector of either orientation
+int get_scratch(const gh_r1cs* h, Scratch& s, size_t xs_rows = 0) {
+    const size_t n = std::max<size_t>(std::max(std::max(h->ni + h->na, h->nc), xs_rows), 1);
     int rc;
     if ((rc = gh_rt::pool_get("r1cs_x", n * sizeof(Fp), (void**)&s.xs))) return rc;
     return gh_rt::pool_get("r1cs_part", std::max<size_t>(h->max_partials, 1) * sizeof(Fp), (void**)&s.part);
 }
 
-template <class P> int convert(const void* d_x, size_t n, const Scratch& s, void* d_scalars) {
+template <class P> int convert(const void* d_x, size_t n, const Scratch& s, void* d_scalars, void* d_aux = nullptr, size_t aux_first = 0) {
     if (!n) return tm_mark(0);
-    GH_LAUNCH((r1cs_convert_kernel<P>), dim3(blocks(n)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_x, n, s.xs, (uint32_t*)d_scalars);
+    GH_LAUNCH((r1cs_convert_kernel<P>), dim3(blocks(n)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_x, n, s.xs, (uint32_t*)d_scalars,
+              (uint32_t*)d_aux, aux_first);
     return tm_mark(0);
 }
 
@@ -324,6 +366,72 @@ template <class P> int instance_map_launch(const gh_r1cs* h, const void* d_u, vo
     GH_LAUNCH((r1cs_add_inputs_kernel<P>), dim3(blocks(h->ni)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_u, h->nc, h->ni, (uint32_t*)d_a);
     HIPCHK(hipGetLastError());
     return tm_mark(h->max_levels + 1);
+}
+
+// ---- GM17's R1CS -> SAP maps: the same conversion, products and marks, then one SAP kernel
+// the shape, or GH_E_UNSUPPORTED where EvaluationDomain::new(2 nc + 2 (ni - 1) + 1) would be None; no device call
+template <class P> int sap_shape_of(const gh_r1cs* h, SapShape* sh, uint32_t* log_n) {
+    sh->ni = h->ni;
+    sh->nc = h->nc;
+    sh->nv = h->ni + h->na;
+    if (!r1cs_domain<P>(sh->domain_arg(), log_n)) { g_err = "the SAP domain exceeds the field's 2-adicity"; return GH_E_UNSUPPORTED; }
+    sh->N = (uint64_t)1 << *log_n;
+    return GH_OK;
+}
+int sap_shape(const gh_r1cs* h, SapShape* sh, uint32_t* log_n) {
+    return h->field == GH_MNT4753_FR ? sap_shape_of<P6>(h, sh, log_n) : sap_shape_of<P4>(h, sh, log_n);
+}
+
+// the three product vectors of a SAP call, in the ABI's form: rows of the longer orientation each
+int get_sap_products(const gh_r1cs* h, uint32_t* out[3]) {
+    const size_t rows = std::max<size_t>(std::max(h->ni + h->na, h->nc), 1);
+    uint32_t* base;
+    if (int rc = gh_rt::pool_get("sap_prod", 3 * rows * 96, (void**)&base)) return rc;
+    for (int k = 0; k < 3; k++) out[k] = base + (size_t)k * rows * 24;
+    return GH_OK;
+}
+
+// r1cs_to_sap.rs:125-189, :206-232, no wait.  d_full: null, or full_rows() rows whose first nv the caller has filled.
+template <class P>
+int sap_rows_launch(const gh_r1cs* h, const SapShape& sh, const void* d_z, void* d_a, void* d_c, void* d_scalars, void* d_aux, void* d_full) {
+    Scratch s;
+    uint32_t* prod[3];
+    int rc;
+    if ((rc = get_scratch(h, s)) || (rc = get_sap_products(h, prod)) || (rc = tm_begin()) || (rc = tm_mark(0))) return rc;
+    if ((rc = convert<P>(d_z, sh.nv, s, d_scalars, d_aux, sh.ni))) return rc;
+    for (int k = 0; k < 3; k++)
+        if ((rc = product<P>(h, k, 0, s, prod[k]))) return rc;
+    GH_LAUNCH((sap_rows_kernel<P>), dim3(blocks(sh.rows_lanes())), dim3(BLOCK), 0, g.stream, sh, (const uint32_t*)prod[0], (const uint32_t*)prod[1],
+              (const uint32_t*)prod[2], (const uint32_t*)d_z, (uint32_t*)d_a, (uint32_t*)d_c, (uint32_t*)d_scalars, (uint32_t*)d_aux, (uint32_t*)d_full);
+    HIPCHK(hipGetLastError());
+    return tm_mark(h->max_levels + 1);
+}
+
+// r1cs_to_sap.rs:37-94, no wait: p, m, q side by side in the conversion scratch, one transposed product over each
+template <class P> int sap_instance_launch(const gh_r1cs* h, const SapShape& sh, const void* d_u, void* d_a, void* d_c) {
+    Scratch s;
+    uint32_t* prod[3];
+    int rc;
+    if ((rc = get_scratch(h, s, 3 * sh.nc)) || (rc = get_sap_products(h, prod)) || (rc = tm_begin()) || (rc = tm_mark(0))) return rc;
+    if (sh.nc) GH_LAUNCH((sap_split_kernel<P>), dim3(blocks(sh.nc)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_u, sh.nc, s.xs);
+    if ((rc = tm_mark(0))) return rc;
+    for (int k = 0; k < 3; k++) {
+        Scratch sk = s;
+        sk.xs = s.xs + (size_t)k * sh.nc;
+        if ((rc = product<P>(h, k, 1, sk, prod[k]))) return rc;
+    }
+    GH_LAUNCH((sap_instance_finish_kernel<P>), dim3(blocks(sh.full_rows())), dim3(BLOCK), 0, g.stream, sh, (const uint32_t*)prod[0],
+              (const uint32_t*)prod[1], (const uint32_t*)prod[2], (const uint32_t*)d_u, (uint32_t*)d_a, (uint32_t*)d_c);
+    HIPCHK(hipGetLastError());
+    return tm_mark(h->max_levels + 1);
+}
+
+int last_timing(float* phase_ms, int max_phases, float* total_ms) {
+    if ((!phase_ms && max_phases > 0) || max_phases < 0) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    const int cnt = std::min(max_phases, (int)g_tm.ms.size());
+    for (int i = 0; i < cnt; i++) phase_ms[i] = g_tm.ms[(size_t)i];
+    if (total_ms) *total_ms = g_tm.total_ms;
+    return cnt;
 }
 
 #define R1CS_FIELD_DISPATCH(field, fn, ...) ((field) == GH_MNT4753_FR ? fn<P6>(__VA_ARGS__) : fn<P4>(__VA_ARGS__))
@@ -493,11 +601,111 @@ int gh_r1cs_instance_map(gh_r1cs_t handle, const uint64_t* u, uint64_t* a, uint6
 
 int gh_r1cs_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if ((!phase_ms && max_phases > 0) || max_phases < 0) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    const int cnt = std::min(max_phases, (int)g_tm.ms.size());
-    for (int i = 0; i < cnt; i++) phase_ms[i] = g_tm.ms[(size_t)i];
-    if (total_ms) *total_ms = g_tm.total_ms;
-    return cnt;
+    return last_timing(phase_ms, max_phases, total_ms);
+} catch (...) { return gh_rt::api_exception(); }
+
+// ---- include/ginger_hip_sap.h
+int gh_sap_info(gh_r1cs_t handle, gh_sap_info_t* out) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    const gh_r1cs* h = checked(handle);
+    if (!h) return GH_E_BAD_HANDLE;
+    if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    SapShape sh;
+    uint32_t log_n;
+    if (int rc = sap_shape(h, &sh, &log_n)) return rc;
+    memset(out, 0, sizeof *out);
+    out->sap_log_n = log_n;
+    out->sap_num_variables = sh.sap_nv();
+    const size_t longer = std::max<size_t>(std::max<size_t>(sh.nv, sh.nc), 1);
+    out->scratch_bytes = std::max<size_t>(longer, 3 * sh.nc) * sizeof(Fp) + std::max<size_t>(h->max_partials, 1) * sizeof(Fp) + 3 * longer * 96 +
+                         2 * sh.N * 96;
+    return GH_OK;
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_sap_rows_dev(gh_r1cs_t handle, const void* d_assignment, void* d_a, void* d_c, void* d_scalars, void* d_aux_scalars) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    const gh_r1cs* h = checked(handle);
+    if (!h) return GH_E_BAD_HANDLE;
+    if (!d_assignment || !d_a || !d_c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    SapShape sh;
+    uint32_t log_n;
+    if (int rc = sap_shape(h, &sh, &log_n)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (int rc = R1CS_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, d_assignment, d_a, d_c, d_scalars, d_aux_scalars, nullptr)) return rc;
+    return finish(h);
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_sap_rows(gh_r1cs_t handle, const uint64_t* assignment, uint64_t* a, uint64_t* c, uint64_t* full) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    const gh_r1cs* h = checked(handle);
+    if (!h) return GH_E_BAD_HANDLE;
+    if (!assignment || !a || !c || !full) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    SapShape sh;
+    uint32_t log_n;
+    if (int rc = sap_shape(h, &sh, &log_n)) return rc;
+    if (int rc = ensure_init()) return rc;
+    const size_t zb = sh.nv * 96, ob = sh.N * 96, fb = sh.full_rows() * 96;
+    DevMem dz, da, dc, df;
+    int rc;
+    if ((rc = dz.alloc(zb)) || (rc = da.alloc(ob)) || (rc = dc.alloc(ob)) || (rc = df.alloc(fb))) return rc;
+    if ((rc = to_device(dz.get(), assignment, zb)) || (rc = to_device(df.get(), assignment, zb))) return rc;      // full = z || e || f
+    if ((rc = R1CS_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, dz.get(), da.get(), dc.get(), nullptr, nullptr, df.get()))) return rc;
+    if ((rc = to_host(a, da.get(), ob)) || (rc = to_host(c, dc.get(), ob)) || (rc = to_host(full, df.get(), fb))) return rc;
+    return finish(h);
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_sap_r1cs_witness_map_dev(gh_r1cs_t handle, const void* d_assignment, const uint64_t* d1, const uint64_t* d2, void* d_h, void* d_scalars,
+                                void* d_aux_scalars) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    const gh_r1cs* h = checked(handle);
+    if (!h) return GH_E_BAD_HANDLE;
+    if (!d_assignment || !d1 || !d2 || !d_h) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    SapShape sh;
+    uint32_t log_n;
+    if (int rc = sap_shape(h, &sh, &log_n)) return rc;
+    if (int rc = ensure_init()) return rc;
+    void *da, *dc;
+    int rc;
+    if ((rc = pool_get("sap_a", sh.N * 96, &da)) || (rc = pool_get("sap_c", sh.N * 96, &dc))) return rc;
+    if ((rc = R1CS_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, d_assignment, da, dc, d_scalars, d_aux_scalars, nullptr))) return rc;
+    if ((rc = sap_witness_map(h->field, da, dc, log_n, d1, d2, d_h))) return rc;                  // waits for the stream at its end
+    return tm_finish(h->max_levels + 2);
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_sap_instance_map_dev(gh_r1cs_t handle, const void* d_u, void* d_a, void* d_c) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    const gh_r1cs* h = checked(handle);
+    if (!h) return GH_E_BAD_HANDLE;
+    if (!d_u || !d_a || !d_c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    SapShape sh;
+    uint32_t log_n;
+    if (int rc = sap_shape(h, &sh, &log_n)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (int rc = R1CS_FIELD_DISPATCH(h->field, sap_instance_launch, h, sh, d_u, d_a, d_c)) return rc;
+    return finish(h);
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_sap_instance_map(gh_r1cs_t handle, const uint64_t* u, uint64_t* a, uint64_t* c) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    const gh_r1cs* h = checked(handle);
+    if (!h) return GH_E_BAD_HANDLE;
+    if (!u || !a || !c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    SapShape sh;
+    uint32_t log_n;
+    if (int rc = sap_shape(h, &sh, &log_n)) return rc;
+    if (int rc = ensure_init()) return rc;
+    const size_t ub = sh.N * 96, ob = sh.full_rows() * 96;
+    DevMem du, da, dc;
+    int rc;
+    if ((rc = du.alloc(ub)) || (rc = da.alloc(ob)) || (rc = dc.alloc(ob)) || (rc = to_device(du.get(), u, ub))) return rc;
+    if ((rc = R1CS_FIELD_DISPATCH(h->field, sap_instance_launch, h, sh, du.get(), da.get(), dc.get()))) return rc;
+    if ((rc = to_host(a, da.get(), ob)) || (rc = to_host(c, dc.get(), ob))) return rc;
+    return finish(h);
+} catch (...) { return gh_rt::api_exception(); }
+
+int gh_sap_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
+    std::lock_guard<std::mutex> lk(api_mutex());
+    return last_timing(phase_ms, max_phases, total_ms);
 } catch (...) { return gh_rt::api_exception(); }
 
 }  // extern "C"

@@ -19,10 +19,12 @@ proof is returned as three affine points in the C ABI's form; `proof_bytes` writ
 would (short_weierstrass_projective.rs:185-192), which is what the parity tests compare.
 """
 import contextlib
+import time
 
 import numpy as np
 
-from .limbs import FR_FIELD, MODULUS, affine_to_wire, canon_rows, domain_size, ints_from_mont_rows, mont_rows
+from . import sap
+from .limbs import FR_FIELD, MODULUS, affine_to_wire, canon_rows, domain_size, ints_from_canon_rows, ints_from_mont_rows, mont_rows
 from .prover import ResidentQueries, into_repr, upload_rows
 
 
@@ -85,33 +87,45 @@ class ResidentGm17Key(ResidentQueries):
             "g": (self.g1, cat(pk["g_gamma2_z_t"], row(pk["g_gamma2_z_t"][0])), None),
         }, precompute)
 
-    def create_proof_msms(self, input_assignment, aux_assignment, h, d1, d2, r, h_dev=None):
+    def create_proof_msms(self, input_assignment, aux_assignment, h, d1, d2, r, h_dev=None, scalars_dev=None):
         """prover.rs:267-352 after the witness map.  input_assignment: num_inputs - 1 rows, aux_assignment: the rest of
         the EXTENDED assignment (aux, then the extra SAP variables), h: its coefficients -- all canonical 12-u64 rows
         (into_repr, :224-252); d1, d2, r: Python integers.  h_dev = (DeviceBuffer, rows): h already on the device as canonical
-        scalars.  Returns (A, B, C) as (xy, is_infinity) pairs."""
+        scalars.  scalars_dev = (d_s, d_c1, n), with h_dev: the extended assignment already on the device as canonical scalars
+        (gh_sap_r1cs_witness_map_dev's d_scalars and d_aux_scalars): d_s holds input || aux in its first n rows and has room for
+        two more, d_c1 holds the aux part in its first n - (num_inputs - 1) rows and has room for two more; the tail rows are
+        written here, the buffers stay the caller's, and input_assignment / aux_assignment are ignored.
+        Returns (A, B, C) as (xy, is_infinity) pairs."""
         gl, ni = self.gl, self.num_inputs
         g1, g2 = self.g1, self.g2
         mod = MODULUS[self.pairing]
-        inp = np.ascontiguousarray(input_assignment, dtype=np.uint64).reshape(-1, 12)
-        aux = np.ascontiguousarray(aux_assignment, dtype=np.uint64).reshape(-1, 12)
-        assert len(inp) == ni - 1
         k = self.keys
-        n_var = k["a"].n - 2                                    # variables the a / b / c_2 queries pair with: input || aux
+        n_var = k["a"].n - 2                                 # variables the a / b / c_2 queries pair with: input || aux
         assert k["b"].n - 2 == n_var and k["c2"].n - 1 == n_var and k["c1"].n - 2 == n_var - (ni - 1)
-        aux_used = aux[:n_var - len(inp)]                        # the reference's zip cuts a longer vector here (variable_base.rs:36)
-        pad = np.zeros((n_var - len(inp) - len(aux_used), 12), dtype=np.uint64)
-        r_d1 = canon_rows([(r + d1) % mod])
-        c1_tail = canon_rows([(r * r + 2 * r * d1) % mod, (r + d1) % mod])
+        n_aux = n_var - (ni - 1)
+        s_tail = [canon_rows([1]), canon_rows([(r + d1) % mod])]
+        c1_tail = [canon_rows([(r * r + 2 * r * d1) % mod, (r + d1) % mod])]
         row_d2 = canon_rows([d2 % mod])
         # ONE device vector  input || aux || 1 || (r + d1) || (r^2 + 2 r d1) || (r + d1):
         #   a / b keys take rows [0, n_var + 2), c_2 rows [0, n_var + 1), c_1 rows [ni - 1, n_var) followed by its own two
         # -- c_1's tail is not contiguous with the aux part, so c_1 gets the aux rows again behind the shared vector
         with contextlib.ExitStack() as stack:
-            d_s = stack.enter_context(gl.DeviceBuffer((n_var + 2) * 96))
-            d_c1 = stack.enter_context(gl.DeviceBuffer((n_var - (ni - 1) + 2) * 96))
-            assert upload_rows(gl, d_s, [inp, aux_used, pad, canon_rows([1]), r_d1]) == n_var + 2
-            assert upload_rows(gl, d_c1, [aux_used, pad, c1_tail]) == n_var - (ni - 1) + 2
+            if scalars_dev is not None:
+                d_s, d_c1, n = scalars_dev[0], scalars_dev[1], int(scalars_dev[2])
+                if n != n_var or d_s.nbytes < (n + 2) * 96 or d_c1.nbytes < (n_aux + 2) * 96:
+                    raise ValueError("the scalar vectors must hold one row per variable of the key's queries, and room for two more each")
+                upload_rows(gl, d_s, s_tail, n_var)
+                upload_rows(gl, d_c1, c1_tail, n_aux)
+            else:
+                inp = np.ascontiguousarray(input_assignment, dtype=np.uint64).reshape(-1, 12)
+                aux = np.ascontiguousarray(aux_assignment, dtype=np.uint64).reshape(-1, 12)
+                assert len(inp) == ni - 1
+                aux_used = aux[:n_aux]                               # the reference's zip cuts a longer vector here (variable_base.rs:36)
+                pad = np.zeros((n_aux - len(aux_used), 12), dtype=np.uint64)
+                d_s = stack.enter_context(gl.DeviceBuffer((n_var + 2) * 96))
+                d_c1 = stack.enter_context(gl.DeviceBuffer((n_aux + 2) * 96))
+                assert upload_rows(gl, d_s, [inp, aux_used, pad] + s_tail) == n_var + 2
+                assert upload_rows(gl, d_c1, [aux_used, pad] + c1_tail) == n_aux + 2
             if h_dev is None:
                 h_all = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 12)
                 n_h = min(len(h_all), k["g"].n - 1)
@@ -128,54 +142,95 @@ class ResidentGm17Key(ResidentQueries):
         g_c = gl.proj_add(g1, g_c, g_acc)
         return gl.proj_to_affine(g1, g_a), gl.proj_to_affine(g2, g_b), gl.proj_to_affine(g1, g_c)
 
-    def create_proof(self, circuit_rows, d1, d2, r):
-        """create_proof (prover.rs:201-352) for evaluated constraint rows (groth16.benchmark_circuit_rows form): the host part
-        of the SAP witness map, its transforms on the device (gh_sap_witness_map_dev), into_repr on the device, the MSM stage."""
-        gl, pairing = self.gl, self.pairing
-        mod = MODULUS[pairing]
+    def prepare_rows(self, circuit_rows, d1, d2):
+        """The host side of create_proof up to the device boundary: the host part of the SAP witness map on the evaluated
+        constraint rows (Python integers) and its results as Montgomery / canonical limb arrays.  Separate from prove_prepared
+        so that a caller (tools/r1cs_bench.py) can time the device stage alone."""
+        mod = MODULUS[self.pairing]
         num_inputs, assignment, A, B, C = circuit_rows
         assert num_inputs == self.num_inputs
-        full, a, c, log_n = sap_rows_from_r1cs(pairing, num_inputs, assignment, A, B, C)
-        size = 1 << log_n
-        field = FR_FIELD[pairing]
-        dd = mont_rows([d1, d2], mod)
+        full, a, c, log_n = sap_rows_from_r1cs(self.pairing, num_inputs, assignment, A, B, C)
+        return {"size": 1 << log_n, "a": mont_rows(a, mod), "c": mont_rows(c, mod), "dd": mont_rows([d1, d2], mod), "scal": canon_rows(full),
+                "d1": d1, "d2": d2}
+
+    def prove_prepared(self, prep, r, timing=None):
+        """create_proof (prover.rs:201-352) from prepare_rows' arrays: the two vectors to the device, their transforms
+        (gh_sap_witness_map_dev), into_repr on the device, the MSM stage.  timing (a dict) receives wall-clock ms per stage."""
+        gl, num_inputs = self.gl, self.num_inputs
+        size, dd, scal = prep["size"], prep["dd"], prep["scal"]
+        log_n = size.bit_length() - 1
+        field = FR_FIELD[self.pairing]
+        lib = gl.load_library()
+        t0 = time.perf_counter()
         with contextlib.ExitStack() as stack:
             bufs = [stack.enter_context(gl.DeviceBuffer(size * 96 + 192)) for _ in range(3)]
-            bufs[0].upload(mont_rows(a, mod))
-            bufs[1].upload(mont_rows(c, mod))
-            lib = gl.load_library()
+            bufs[0].upload(prep["a"])
+            bufs[1].upload(prep["c"])
+            lib.gh_dev_sync()
+            t1 = time.perf_counter()
             gl._check(lib.gh_sap_witness_map_dev(gl.FIELDS[field], bufs[0].ptr, bufs[1].ptr, log_n, gl._ptr(dd[0]), gl._ptr(dd[1]), bufs[2].ptr))
             into_repr(gl, field, bufs[2], size + 1)                                                             # h (:237-252)
-            scal = canon_rows(full)
+            lib.gh_dev_sync()
+            t2 = time.perf_counter()
             n_h = self.keys["g"].n - 1
             assert n_h <= size + 1
-            return self.create_proof_msms(scal[1:num_inputs], scal[num_inputs:], None, d1, d2, r, h_dev=(bufs[2], n_h))
+            proof = self.create_proof_msms(scal[1:num_inputs], scal[num_inputs:], None, prep["d1"], prep["d2"], r, h_dev=(bufs[2], n_h))
+            t3 = time.perf_counter()
+        if timing is not None:
+            timing.update(rows_upload_ms=(t1 - t0) * 1e3, witness_map_ms=(t2 - t1) * 1e3, msm_stage_ms=(t3 - t2) * 1e3)
+        return proof
+
+    def create_proof(self, circuit_rows, d1, d2, r):
+        """create_proof (prover.rs:201-352) for evaluated constraint rows (groth16.benchmark_circuit_rows form): the host part
+        of the SAP witness map, its transforms on the device, into_repr on the device, the MSM stage."""
+        return self.prove_prepared(self.prepare_rows(circuit_rows, d1, d2), r)
+
+    def create_proof_r1cs(self, r1cs, assignment, d1, d2, r, timing=None):
+        """create_proof (prover.rs:201-352) over resident constraint matrices (r1cs.ResidentR1CS): the assignment goes to the
+        device once, as Montgomery rows ((n, 12) uint64, or Python integers that are converted first);
+        gh_sap_r1cs_witness_map_dev forms the SAP rows there, runs the witness map and leaves the extended assignment as
+        canonical scalars for the five MSMs, so the MSM stage uploads its few tail rows only.  Returns the (A, B, C) of
+        create_proof on the same circuit.  timing (a dict) receives wall-clock ms per stage."""
+        gl = self.gl
+        mod = MODULUS[self.pairing]
+        if r1cs.num_inputs != self.num_inputs:
+            raise ValueError("the constraint system and the key disagree on the number of inputs")
+        z = assignment if isinstance(assignment, np.ndarray) else mont_rows(list(assignment), mod)
+        z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 12)
+        nv = r1cs.num_variables
+        if len(z) != nv:
+            raise ValueError("the assignment must have one row per variable")
+        info = sap.sap_info(r1cs)
+        size, sap_nv = info["size"], info["sap_num_variables"]
+        n_aux = sap_nv - (self.num_inputs - 1)
+        n_h = self.keys["g"].n - 1
+        if n_h > size + 1:
+            raise ValueError("the key's g_gamma2_z_t query is longer than h")
+        dd = mont_rows([d1, d2], mod)
+        lib = gl.load_library()
+        t0 = time.perf_counter()
+        with contextlib.ExitStack() as stack:
+            d_z, d_h, d_s, d_c1 = (stack.enter_context(gl.DeviceBuffer(rows * 96)) for rows in (nv, size + 2, sap_nv + 2, n_aux + 2))
+            d_z.upload(z)
+            lib.gh_dev_sync()
+            t1 = time.perf_counter()
+            sap.sap_witness_map_dev(r1cs, d_z, dd, d_h, d_s, d_c1)
+            into_repr(gl, FR_FIELD[self.pairing], d_h, size + 1)                                                # h (:237-252)
+            lib.gh_dev_sync()
+            t2 = time.perf_counter()
+            proof = self.create_proof_msms(None, None, None, d1, d2, r, h_dev=(d_h, n_h), scalars_dev=(d_s, d_c1, sap_nv))
+            t3 = time.perf_counter()
+        if timing is not None:
+            timing.update(assignment_upload_ms=(t1 - t0) * 1e3, witness_map_ms=(t2 - t1) * 1e3, msm_stage_ms=(t3 - t2) * 1e3)
+        return proof
 
 
-def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, t, g1_xyz, g2_xyz):
-    """generate_parameters (proof-systems/src/gm17/generator.rs:146-335) above the C ABI, for a constraint system given as linear
-    combinations (groth16.benchmark_circuit_lcs form); the toxic waste alpha, beta, gamma, the evaluation point t
-    (sample_element_outside_domain, :183) and the generators g, h (`rand`, :41-42) are arguments instead of RNG draws.
-      * Lagrange coefficients at t on the device (gh_lagrange_coefficients = evaluate_all_lagrange_coefficients, domain.rs:183-219);
-      * R1CStoSAP::instance_map_with_evaluation (r1cs_to_sap.rs:14-96): host integers, as in the reference;
-      * the FIVE FixedBaseMSM::multi_scalar_mul calls (:222-229 a_query, :245-254 g_gamma2_z_t, :259-270 verifier query ||
-        c_query_1, :274-285 c_query_2, :297-302 b_query on h^gamma) with the reference's window rule (:198-213, :290) followed
-        by batch_normalization + into_affine (:323-333): gh_fixed_base_msm_affine;
-      * the single points (:233-241) by host-side scalar multiplications (gh_proj_mul).
-    Returns (pk, info): pk in ResidentGm17Key's form (Montgomery x || y rows + `<query>_inf` flags; GM17's Parameters::write is
-    unimplemented upstream, gm17/mod.rs:186-196), info = the SAP evaluations a, c, Z(t) for a check in the exponent."""
-    r = MODULUS[pairing]
-    field = FR_FIELD[pairing]
-    g1c, g2c = pairing + "_g1", pairing + "_g2"
+def sap_instance_map_host(lcs, u, r):
+    """The loops of R1CStoSAP::instance_map_with_evaluation (r1cs_to_sap.rs:37-94) on host integers, as in the reference: u, the
+    Lagrange coefficients at t over the SAP domain -> (a, c), each with sap_num_variables + 1 entries"""
     num_inputs, num_aux, at, bt, ct = lcs
     n_con = len(at)
     ni1 = num_inputs - 1
-    size = domain_size(2 * n_con + 2 * ni1 + 1)                                    # r1cs_to_sap.rs:18-21
-    log_n = size.bit_length() - 1
-    zt = (pow(t, size, r) - 1) % r
-    u_rows = np.zeros((size, 12), dtype=np.uint64)
-    gl._check(gl.load_library().gh_lagrange_coefficients(gl.FIELDS[field], log_n, gl._ptr(mont_rows([t], r)[0]), gl._ptr(u_rows)))
-    u = ints_from_mont_rows(u_rows, r)
     sap_nv = 2 * ni1 + num_aux + n_con                                             # :30-31
     xvo, xco, xvo2 = ni1 + num_aux + 1, 2 * n_con, ni1 + num_aux + n_con           # :32-35
     a, c = [0] * (sap_nv + 1), [0] * (sap_nv + 1)
@@ -197,6 +252,60 @@ def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, t, g1_xyz, g2_xyz)
         a[0] = (a[0] + uo - ue) % r
         c[i] = (c[i] + 4 * uo) % r
         c[xvo2 + i] = (c[xvo2 + i] + uo + ue) % r
+    return a, c
+
+
+def _instance_map_on_device(gl, field, r1cs, shape, tau):
+    """the same with u left on the device (gh_lagrange_coefficients_dev) and the three transposed products there
+    (gh_sap_instance_map_dev); into_repr on the device as well, so the host only reads limbs -> a, c as integers"""
+    num_inputs, num_aux, n_con, log_n = shape
+    if (r1cs.num_inputs, r1cs.num_aux, r1cs.num_constraints) != shape[:3] or sap.sap_info(r1cs)["sap_log_n"] != log_n:
+        raise ValueError("the resident constraint system is not the one of lcs")
+    rows = 2 * (num_inputs - 1) + num_aux + n_con + 1
+    with contextlib.ExitStack() as stack:
+        d_u = stack.enter_context(gl.DeviceBuffer(96 << log_n))
+        outs = [stack.enter_context(gl.DeviceBuffer(rows * 96)) for _ in range(2)]
+        gl._check(gl.load_library().gh_lagrange_coefficients_dev(gl.FIELDS[field], log_n, gl._ptr(tau), d_u.ptr))
+        sap.sap_instance_map_dev(r1cs, d_u, *outs)
+        res = []
+        for o in outs:
+            into_repr(gl, field, o, rows)
+            res.append(ints_from_canon_rows(o.download()[:rows * 12]))
+        return tuple(res)
+
+
+def generate_parameters(gl, pairing, lcs, alpha, beta, gamma, t, g1_xyz, g2_xyz, r1cs=None):
+    """generate_parameters (proof-systems/src/gm17/generator.rs:146-335) above the C ABI, for a constraint system given as linear
+    combinations (groth16.benchmark_circuit_lcs form); the toxic waste alpha, beta, gamma, the evaluation point t
+    (sample_element_outside_domain, :183) and the generators g, h (`rand`, :41-42) are arguments instead of RNG draws.
+      * Lagrange coefficients at t on the device (gh_lagrange_coefficients = evaluate_all_lagrange_coefficients, domain.rs:183-219);
+      * R1CStoSAP::instance_map_with_evaluation (r1cs_to_sap.rs:14-96): host integers, as in the reference
+        (sap_instance_map_host);
+      * the FIVE FixedBaseMSM::multi_scalar_mul calls (:222-229 a_query, :245-254 g_gamma2_z_t, :259-270 verifier query ||
+        c_query_1, :274-285 c_query_2, :297-302 b_query on h^gamma) with the reference's window rule (:198-213, :290) followed
+        by batch_normalization + into_affine (:323-333): gh_fixed_base_msm_affine;
+      * the single points (:233-241) by host-side scalar multiplications (gh_proj_mul).
+    Returns (pk, info): pk in ResidentGm17Key's form (Montgomery x || y rows + `<query>_inf` flags; GM17's Parameters::write is
+    unimplemented upstream, gm17/mod.rs:186-196), info = the SAP evaluations a, c, Z(t) for a check in the exponent.
+      * r1cs (an r1cs.ResidentR1CS of the same lcs): the Lagrange coefficients stay on the device
+        (gh_lagrange_coefficients_dev) and gh_sap_instance_map_dev takes the place of the host loops -- same pk and info."""
+    r = MODULUS[pairing]
+    field = FR_FIELD[pairing]
+    g1c, g2c = pairing + "_g1", pairing + "_g2"
+    num_inputs, num_aux, at, bt, ct = lcs
+    n_con = len(at)
+    ni1 = num_inputs - 1
+    size = domain_size(2 * n_con + 2 * ni1 + 1)                                    # r1cs_to_sap.rs:18-21
+    log_n = size.bit_length() - 1
+    zt = (pow(t, size, r) - 1) % r
+    tau = mont_rows([t], r)[0]
+    sap_nv = 2 * ni1 + num_aux + n_con                                             # :30-31
+    if r1cs is not None:
+        a, c = _instance_map_on_device(gl, field, r1cs, (num_inputs, num_aux, n_con, log_n), tau)
+    else:
+        u_rows = np.zeros((size, 12), dtype=np.uint64)
+        gl._check(gl.load_library().gh_lagrange_coefficients(gl.FIELDS[field], log_n, gl._ptr(tau), gl._ptr(u_rows)))
+        a, c = sap_instance_map_host(lcs, ints_from_mont_rows(u_rows, r), r)
     non_zero_a = sum(1 for v in a[:sap_nv] if v)                                   # generator.rs:191-195
     m_raw = size
     FB = gl.FixedBaseMSM

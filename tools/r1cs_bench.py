@@ -12,9 +12,15 @@ reduction chain: level 0 is the gather, the levels above sum its partials), term
 shapes, and one timing of generate_parameters with and without the resident matrices (same bytes).  The spread of each path
 (max - min over its proofs) is printed next to the difference of the means.
 
+--scheme gm17 measures GM17's create_proof the same way: (a) is gm17's prove_prepared on SAP rows
+formed and converted outside the clock (sap_rows_from_r1cs and the conversions are timed separately), (b) its
+create_proof_r1cs; next to them gh_sap_rows_dev and gh_sap_instance_map_dev alone by events and per phase, and
+generate_parameters with and without the resident matrices.  --log-n is still the R1CS size 2^k - 3; the SAP domain is 2^(k+1).
+Its default output is profiles/sap_bench.json.
+
 Prints one JSON document and writes it to --out.  --rehearse runs without a device: argument parsing, the circuit, the
 flattening and the referee of tests/r1cs_ref.py on a small size.
-Usage: timeout -k 10 900 python tools/r1cs_bench.py [--log-n 20] [--proofs 5] [--out profiles/r1cs_bench.json]"""
+Usage: timeout -k 10 900 python tools/r1cs_bench.py [--scheme groth16|gm17] [--log-n 20] [--proofs 5] [--out profiles/r1cs_bench.json]"""
 import argparse
 import importlib
 import json
@@ -53,21 +59,142 @@ def rehearse(args):
     assert a[:n] == A and b[:n] == B and c[:n] == C
     flat = [r1cs.flatten(rows, r) for rows in lcs[2:]]
     assert all(int(f[0][-1]) == len(f[1]) == len(f[2]) for f in flat) and all(len(f[3]) == 1 for f in flat)
-    out = {"rehearsal": True, "log_n": args.log_n, "proofs": args.proofs, "shapes_at_61": shapes(lcs), "measured": "not measured: no device"}
+    if args.scheme == "gm17":
+        import sap_ref
+        gm17 = importlib.import_module("ginger_lib_amd.gm17")
+        full, sa, sc, log_n = gm17.sap_rows_from_r1cs(pairing, num_inputs, assignment, A, B, C)
+        assert (full, sa, sc) == sap_ref.rows(lcs, assignment, r) and 1 << log_n == sap_ref.domain_size(n, num_inputs)
+    out = {"rehearsal": True, "scheme": args.scheme, "log_n": args.log_n, "proofs": args.proofs, "shapes_at_61": shapes(lcs), "measured": "not measured: no device"}
     print(json.dumps(out))
     return 0
 
 
+def alternate(run_a, run_b, proofs, same):
+    """the two paths alternated, `proofs` each: run_x(timing) -> proof; same(proof) -> bool.  -> (paths report, all proofs equal)"""
+    ta, tb, ok = [], [], True
+    for _ in range(proofs):
+        last_a, last_b = {}, {}
+        ok = same(run_a(last_a)) and ok
+        ta.append(sum(last_a.values()))
+        ok = same(run_b(last_b)) and ok
+        tb.append(sum(last_b.values()))
+    spread = max(max(ta) - min(ta), max(tb) - min(tb))
+    diff = float(np.mean(ta) - np.mean(tb))
+    return {"a_prove_prepared_ms": ta, "b_create_proof_r1cs_ms": tb, "a_mean_ms": float(np.mean(ta)), "b_mean_ms": float(np.mean(tb)),
+            "a_spread_ms": max(ta) - min(ta), "b_spread_ms": max(tb) - min(tb), "difference_ms": diff,
+            "difference_in_spreads": diff / spread if spread else None, "a_last_stages": last_a, "b_last_stages": last_b}, ok
+
+
+def main_gm17(args):
+    import pyref
+    import support as S
+    from __graft_entry__ import _load_pkg
+    gl = _load_pkg()
+    gl.init()
+    groth16 = importlib.import_module("ginger_lib_amd.groth16")
+    gm17 = importlib.import_module("ginger_lib_amd.gm17")
+    limbs = importlib.import_module("ginger_lib_amd.limbs")
+    r1cs = importlib.import_module("ginger_lib_amd.r1cs")
+    sap = importlib.import_module("ginger_lib_amd.sap")
+    pairing = "mnt4753"
+    field = gl.FIELDS["mnt4753_fr"]
+    C1, C2 = pyref.CURVES[pairing + "_g1"], pyref.CURVES[pairing + "_g2"]
+    rr = C1.order
+    n_con = (1 << args.log_n) - 3
+    prng = pyref.Rng(2027)
+    alpha, beta, gamma, tau, r_, d1, d2 = (prng.field_elem(rr) for _ in range(7))
+    g1, g2 = C1.mul(prng.next_u64() | 1, C1.G), C2.mul(prng.next_u64() | 1, C2.G)
+    gen_args = (alpha, beta, gamma, tau, S.proj_array(C1, g1), S.proj_array(C2, g2))
+    out = {"device": gl.device_name(), "scheme": "gm17", "pairing": pairing, "log_n": args.log_n, "constraints": n_con}
+    lcs = groth16.benchmark_circuit_lcs(n_con)
+    out["shapes"] = shapes(lcs)
+    t0 = time.perf_counter()
+    res = r1cs.ResidentR1CS(gl, pairing, lcs)
+    out["r1cs_upload_s"] = time.perf_counter() - t0
+    info = res.info()
+    out["r1cs_info"] = info
+    out["sap_info"] = sinfo = sap.sap_info(res)
+    t0 = time.perf_counter()
+    pk, ginfo = gm17.generate_parameters(gl, pairing, lcs, *gen_args)
+    out["generate_parameters_s"] = time.perf_counter() - t0
+    if not args.no_generator:
+        t0 = time.perf_counter()
+        pk_r, ginfo_r = gm17.generate_parameters(gl, pairing, lcs, *gen_args, r1cs=res)
+        out["generate_parameters_r1cs_s"] = time.perf_counter() - t0
+        out["generate_parameters_same_key"] = bool(sorted(pk) == sorted(pk_r) and all((np.asarray(pk[k]) == np.asarray(pk_r[k])).all() for k in pk)
+                                                   and ginfo == ginfo_r)
+        del pk_r, ginfo_r
+    del ginfo
+    key = gm17.ResidentGm17Key(gl, pairing, pk, 3)
+    del pk
+    try:
+        rows = groth16.benchmark_circuit_rows(pairing, n_con)          # outside every clock
+        t0 = time.perf_counter()
+        full, a, c, _ = gm17.sap_rows_from_r1cs(pairing, *rows)
+        t1 = time.perf_counter()
+        limbs.canon_rows(full), limbs.mont_rows(a, rr), limbs.mont_rows(c, rr)
+        t2 = time.perf_counter()
+        out["host_sap_rows_from_r1cs_s"], out["host_conversions_s"] = t1 - t0, t2 - t1      # what leaves the caller
+        del full, a, c
+        prep = key.prepare_rows(rows, d1, d2)                          # outside the clock of path (a)
+        zm = limbs.mont_rows(rows[1], rr)                              # outside the clock of path (b)
+        del rows
+        pb = lambda proof: gm17.proof_bytes(pairing, proof)
+        proof_a = pb(key.prove_prepared(prep, r_))                     # warm both paths: pools, pipeline slots, domain tables
+        out["same_proof_bytes"] = bool(proof_a == pb(key.create_proof_r1cs(res, zm, d1, d2, r_)))
+        out["paths"], same = alternate(lambda tm: key.prove_prepared(prep, r_, timing=tm), lambda tm: key.create_proof_r1cs(res, zm, d1, d2, r_, timing=tm),
+                                       args.proofs, lambda proof: pb(proof) == proof_a)
+        out["same_proof_bytes"] = out["same_proof_bytes"] and same
+        # the device stages alone, by events
+        nv, size, sap_nv = res.num_variables, sinfo["size"], sinfo["sap_num_variables"]
+        d_z = gl.DeviceBuffer(nv * 96).upload(zm)
+        bufs = [gl.DeviceBuffer(rows_ * 96) for rows_ in (size, size, sap_nv, sap_nv - 2, size, sap_nv + 1, sap_nv + 1)]
+        d_a, d_c, d_s, d_x, d_u, v_a, v_c = bufs
+        try:
+            rw, rs, im = [], [], []
+            for _ in range(3):
+                sap.sap_rows_dev(res, d_z, d_a, d_c)
+                rw.append(sap.last_timing())
+            for _ in range(3):
+                sap.sap_rows_dev(res, d_z, d_a, d_c, d_s, d_x)
+                rs.append(sap.last_timing())
+            tau_m = limbs.mont_rows([tau], rr)[0]
+            gl._check(gl.load_library().gh_lagrange_coefficients_dev(field, sinfo["sap_log_n"], gl._ptr(tau_m), d_u.ptr))
+            for _ in range(3):
+                sap.sap_instance_map_dev(res, d_u, v_a, v_c)
+                im.append(sap.last_timing())
+        finally:
+            for buf in [d_z] + bufs:
+                buf.free()
+        best = lambda runs: min(runs, key=lambda t: t[1])
+        terms = out["shapes"]["terms"]
+        n_ph = max(max(info["levels"][m]) for m in "ABC") + 2
+        for name, runs in (("sap_rows_dev", rw), ("sap_rows_dev_with_scalars", rs), ("sap_instance_map_dev", im)):
+            ph, tot = best(runs)
+            out[name] = {"total_ms": tot, "phases_ms": ph[:n_ph], "runs_total_ms": [t for _, t in runs], "terms_per_s": terms / (tot * 1e-3) if tot else None,
+                         "phases": "conversion or split, levels 0 .. of the three products, the SAP kernel (last entry)"}
+    finally:
+        key.free()
+        res.free()
+        gl.dev_trim()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--scheme", choices=("groth16", "gm17"), default="groth16")
     ap.add_argument("--log-n", type=int, default=20, help="the QAP domain: 2^k - 3 constraints")
     ap.add_argument("--proofs", type=int, default=5, help="timed proofs per path (at least 5 for the published numbers)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r1cs_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/r1cs_bench.json, or profiles/sap_bench.json with --scheme gm17")
     ap.add_argument("--rehearse", action="store_true", help="no device: parse, build the circuit, run the referee on a small size")
     ap.add_argument("--no-generator", action="store_true", help="skip the second generate_parameters (with the resident matrices)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sap_bench.json" if args.scheme == "gm17" else "r1cs_bench.json")
     if args.rehearse:
         return rehearse(args)
+    if args.scheme == "gm17":
+        return report(main_gm17(args), args)
 
     import pyref
     import support as S
@@ -116,22 +243,9 @@ def main():
         proof_a = key.prove_prepared(prep, r_, s_)             # warm both paths: pools, pipeline slots, domain tables
         proof_b = key.create_proof_r1cs(res, zm, 0, 0, 0, r_, s_)
         out["same_proof_bytes"] = bool(proof_a == proof_b)
-        ta, tb = [], []
-        for _ in range(args.proofs):                           # alternated
-            tm = {}
-            pa = key.prove_prepared(prep, r_, s_, timing=tm)
-            ta.append(tm["rows_upload_ms"] + tm["witness_map_ms"] + tm["msm_stage_ms"])
-            last_a = tm
-            tm = {}
-            pb = key.create_proof_r1cs(res, zm, 0, 0, 0, r_, s_, timing=tm)
-            tb.append(tm["assignment_upload_ms"] + tm["witness_map_ms"] + tm["msm_stage_ms"])
-            last_b = tm
-            out["same_proof_bytes"] = out["same_proof_bytes"] and pa == proof_a and pb == proof_a
-        spread = max(max(ta) - min(ta), max(tb) - min(tb))
-        diff = float(np.mean(ta) - np.mean(tb))
-        out["paths"] = {"a_prove_prepared_ms": ta, "b_create_proof_r1cs_ms": tb, "a_mean_ms": float(np.mean(ta)), "b_mean_ms": float(np.mean(tb)),
-                        "a_spread_ms": max(ta) - min(ta), "b_spread_ms": max(tb) - min(tb), "difference_ms": diff,
-                        "difference_in_spreads": diff / spread if spread else None, "a_last_stages": last_a, "b_last_stages": last_b}
+        out["paths"], same = alternate(lambda tm: key.prove_prepared(prep, r_, s_, timing=tm),
+                                       lambda tm: key.create_proof_r1cs(res, zm, 0, 0, 0, r_, s_, timing=tm), args.proofs, lambda proof: proof == proof_a)
+        out["same_proof_bytes"] = out["same_proof_bytes"] and same
         # the device stages alone, by events
         nv, size = res.num_variables, res.size
         d_z = gl.DeviceBuffer(nv * 96).upload(zm)
@@ -171,6 +285,10 @@ def main():
         key.free()
         res.free()
         gl.dev_trim()
+    return report(out, args)
+
+
+def report(out, args):
     text = json.dumps(out, indent=1)
     print(text)
     if args.out:
