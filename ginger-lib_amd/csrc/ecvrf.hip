@@ -438,15 +438,6 @@ template <class C> int run_proof_to_hash(gh_ecvrf* h, const uint64_t* pk_xy, con
     return ph.finish();
 }
 
-// y^2 == x^3 + a x + b on the host (the generators of gh_bh_create)
-template <class C> bool on_curve_host(const uint64_t* xy) {
-    typedef typename Scheme<C>::PF PF;
-    typedef F1<PF, true> F;
-    const Fp x = fp_from_abi<PF>((const uint32_t*)xy), y = fp_from_abi<PF>((const uint32_t*)(xy + 12));
-    const Fp rhs = F::add(F::add(F::mul(F::sqr(x), x), C::mul_by_a(x)), curve_b<C>());
-    return F::eq(F::sqr(y), rhs);
-}
-
 // the checks prove / proof_to_hash share: sizes, the group hash's capacity, the moduli of pk and the message
 template <class C> int check_common(const gh_ecvrf* h, const uint64_t* pk_xy, const uint64_t* msg, size_t n, size_t len) {
     if (len > h->bh->num_windows * h->bh->window_size / 256) {

@@ -287,6 +287,14 @@ template <class C> Fp curve_b() {
     static const uint64_t b4[12] = GH_MNT4753_G1_B0_M_64, b6[12] = GH_MNT6753_G1_B0_M_64;
     return fp_from_abi<typename Scheme<C>::PF>((const uint32_t*)(std::is_same<C, Mnt6G1>::value ? b6 : b4));
 }
+// y^2 == x^3 + a x + b on the host (the generators of gh_bh_create and gh_pedersen_create)
+template <class C> bool on_curve_host(const uint64_t* xy) {
+    typedef typename Scheme<C>::PF PF;
+    typedef F1<PF, true> F;
+    const Fp x = fp_from_abi<PF>((const uint32_t*)xy), y = fp_from_abi<PF>((const uint32_t*)(xy + 12));
+    const Fp rhs = F::add(F::add(F::mul(F::sqr(x), x), C::mul_by_a(x)), curve_b<C>());
+    return F::eq(F::sqr(y), rhs);
+}
 template <class C> void generator_xyz(uint64_t* g_xyz) {
     const bool m6 = std::is_same<C, Mnt6G1>::value;
     static const uint64_t gx4[12] = GH_MNT4753_G1_GX0_M_64, gy4[12] = GH_MNT4753_G1_GY0_M_64, one4[12] = GH_P4_R_64;
