@@ -73,6 +73,8 @@ def build(outdir):
         infos[p.name]["instructions"] = p.count()
         infos[p.name]["lds_bytes"] = p.lds_bytes
         infos[p.name]["scratch_bytes_per_lane"] = 0
+        if getattr(p, "loop_labels", None):         # the G1 accumulation: one bucket update, counted from the emitted text
+            infos[p.name].update(g1_xyzz.update_counts(p))
     with open(os.path.join(outdir, "gh_asm.json"), "w") as f:
         json.dump(infos, f, indent=1, sort_keys=True)
     return co_path, infos

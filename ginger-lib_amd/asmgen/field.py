@@ -14,6 +14,11 @@ measurement that said otherwise, tools/microbench/lone_wave.hip, had one wave on
 accumulator pair, two temporaries, a dummy carry-out pair for the mads and a carry pair for borrow chains (VCC is never
 used inside a routine, so two interleaved chains cannot disturb each other).
 
+The G1 bucket update (g1_xyzz.py) uses the lazy forms further down instead: mul27 / sqr27 / dual27 (a 27-digit reduction whose
+result is below p + 2^733 for any operands the bound checker admits), lazy_diff and zero_or_p_mask (fp29.h fp_mul27, fp_sqr27,
+fp_mul2s27, fp_lazy_sub, fp_lazy_x3, fp_is_zero_or_p).  The routines above them are unchanged: the bucket reduction, the G2
+rounds and the NTT passes keep every value in [0, p).
+
 gfx9 constant-bus rule (ONE SGPR or literal per VALU instruction, an SGPR carry-in included) shapes the sequences: a
 borrow chain cannot take p_i from an SGPR, so the conditional subtraction runs on signed limbs with the borrow in a VGPR.
 """
@@ -22,6 +27,35 @@ from .isa import Reg, V, S
 NL = 26
 LB = 29
 LM = (1 << LB) - 1
+
+
+ND = NL + 1                     # digits of the 27-digit reduction (REDC27: radix 2^783)
+TOP_SHIFT = LB * (NL - 1)       # weight of the top limb
+
+
+class BoundError(ValueError):
+    """a lazy routine was asked for operands whose columns, top limb or doubled limb do not fit the registers"""
+
+
+class Bound:
+    """inclusive upper bound k p + slack of a value held as 25 limbs of 29 bits and a top limb of up to 32"""
+
+    def __init__(self, k, slack=0):
+        self.k, self.slack = k, slack
+
+    def value(self, p):
+        return self.k * p + self.slack
+
+    def __repr__(self):
+        return "Bound(%d p + 2^%.1f)" % (self.k, _log2(self.slack)) if self.slack else "Bound(%d p)" % self.k
+
+
+def _bound(b):
+    return b if isinstance(b, Bound) else Bound(*b) if isinstance(b, tuple) else Bound(b)
+
+
+def _log2(x):
+    return x.bit_length() - 1 + (x >> max(0, x.bit_length() - 53)) / (1 << min(52, x.bit_length() - 1)) - 1 if x > 0 else 0.0
 
 
 def limbs(x, n=NL):
@@ -364,6 +398,193 @@ class FieldGen:
             yield
         g.v_cmp_eq_u32(smask, 0, t); yield
 
+    # ------------------------------------------------------------------ lazy forms: 27-digit reduction, no conditional subtraction
+    # REDC27(a, b) = (a b + m p) / 2^783 with 27 digits m_0 .. m_26: a b 2^-783 mod p, below a b / 2^783 + p -- "almost reduced"
+    # (below p + 2^733) for ANY operands below 2^758, so a product never needs a conditional subtraction and may take the
+    # carry-normalised differences a - b + 2^s p (25 limbs of 29 bits, the excess in an unmasked top limb) as they are.
+    # Every routine takes the bound of each operand (Bound: k p + slack, inclusive), checks with the real limbs of p and the
+    # carries that no column reaches 2^64 and no top limb or doubled limb 2^32 (BoundError at build time), and returns the
+    # bound of its result.  fp29.h fp_mul27 / fp_sqr27 / fp_mul2s27 / fp_lazy_sub / fp_lazy_x3 restate them limb for limb.
+    def _caps(self, bd):
+        """the largest value of each limb of an operand bounded by bd"""
+        top = _bound(bd).value(self.p) >> TOP_SHIFT
+        if top >> 32:
+            raise BoundError("top limb of an operand can reach 2^32 (bound %r)" % (bd,))
+        return [LM] * (NL - 1) + [top]
+
+    def _md(self, ch, m, i):
+        """home of the digit m_i: the slot m, the 27th in the chain's second temporary"""
+        return m.sub(i) if i < NL else ch.t1
+
+    def plan27(self, groups, value_sum, allow_split=True):
+        """groups: term functions k -> [(x, y, cap)] of the summed integer products; value_sum: bound of their sum.
+        -> (set of columns closed in two parts, Bound of the result).  A column is split only where the single chain can
+        reach 2^64: the first group (+ carry-in) stays on the chain, the others and m p go to a second accumulator."""
+        split, carry = set(), 0
+        for k in range(2 * NL):
+            sums = [sum(cap for _, _, cap in terms(k)) for terms in groups]
+            mp = sum(LM * self.pl[k - i] for i in range(max(0, k - NL + 1), min(k, ND - 1) + 1))     # m_k p_0 of the close included
+            total = carry + sum(sums) + mp
+            if total >> 64 == 0:
+                carry = total >> LB
+                continue
+            part1, part2 = carry + sums[0], LM + sum(sums[1:]) + mp
+            if len(groups) < 2 or not allow_split or part1 >> 64 or part2 >> 64:
+                raise BoundError("column %d of a 27-digit product can reach 2^%.2f" % (k, _log2(total)))
+            split.add(k)
+            carry = (part1 >> LB) + (part2 >> LB)
+        res = Bound(1, value_sum >> (LB * ND))
+        self._caps(res)
+        return split, res
+
+    def mont_columns27(self, ch, groups, split, m, r, ch2=None):
+        """The 52 columns of REDC27.  Digits m_0 .. m_25 in the slot m, m_26 in ch.t1; result limb j is column 27 + j (limbs
+        0 .. 24) and the last carry (limb 25); r may be m or an operand's slot (r_j is written after the last use of m_j, a_j,
+        b_j).  split: the columns plan27 closes in two parts, on ch2's accumulator."""
+        g = self.g
+        X = ch.acc
+        first = True
+        for k in range(2 * NL):
+            acc = X
+            for n, terms in enumerate(groups):
+                if n == 1 and k in split:
+                    # the chain keeps (carry-in + first group) >> 29; its low limb opens the second accumulator, which takes the
+                    # other products and m p and closes the column as a single chain does (cf. triple)
+                    acc = ch2.acc
+                    g.v_and_b32(acc.lo(), S(self.s_lm), X.lo()); yield
+                    g.v_mov_b32(acc.hi(), 0); yield
+                    g.v_lshrrev_b64(X, LB, X); yield
+                for (x, y, _) in terms(k):
+                    g.v_mad_u64_u32(acc, ch.sdum, x, y, 0 if first else acc); first = False; yield
+            for i in range(max(0, k - NL + 1), min(k - 1, ND - 1) + 1):
+                g.v_mad_u64_u32(acc, ch.sdum, self._md(ch, m, i), self.sP(k - i), acc); yield
+            if k < ND:
+                mk = self._md(ch, m, k)
+                g.v_mul_lo_u32(ch.t0, acc.lo(), S(self.s_inv)); yield
+                g.v_and_b32(mk, S(self.s_lm), ch.t0); yield
+                g.v_mad_u64_u32(acc, ch.sdum, mk, self.sP(0), acc); yield
+                g.v_lshrrev_b64(acc, LB, acc); yield
+            elif k < 2 * NL - 1:
+                g.v_and_b32(r.sub(k - ND), S(self.s_lm), acc.lo()); yield
+                g.v_lshrrev_b64(acc, LB, acc); yield
+            else:
+                assert acc is X
+                g.v_and_b32(r.sub(NL - 2), S(self.s_lm), X.lo()); yield
+                g.v_alignbit_b32(r.sub(NL - 1), X.hi(), X.lo(), LB); yield
+            if acc is not X:
+                g.v_lshl_add_u64(X, acc, 0, X); yield
+
+    def _terms27(self, a, b, ca, cb):
+        def terms(k):
+            return [(a.sub(i), b.sub(k - i), ca[i] * cb[k - i]) for i in range(max(0, k - NL + 1), min(k, NL - 1) + 1)]
+        return terms
+
+    def mul27(self, ch, a, b, m, ba, bb, r=None):
+        """r (default m) = REDC27(a, b); generator, its return value (`yield from`, or run27) is the result's Bound"""
+        ba, bb = _bound(ba), _bound(bb)
+        groups = [self._terms27(a, b, self._caps(ba), self._caps(bb))]
+        split, res = self.plan27(groups, ba.value(self.p) * bb.value(self.p))
+        yield from self.mont_columns27(ch, groups, split, m, m if r is None else r)
+        return res
+
+    def sqr27(self, ch, a, a2, m, ba, r=None):
+        """r (default m) = REDC27(a, a).  a2: free slot for the doubled operand (every doubled limb must fit 32 bits)."""
+        ba = _bound(ba)
+        ca = self._caps(ba)
+        if (2 * ca[NL - 1]) >> 32:
+            raise BoundError("doubled top limb of a squaring operand can reach 2^32 (bound %r)" % (ba,))
+
+        def terms(k):
+            t = [(a.sub(i), a2.sub(k - i), 2 * ca[i] * ca[k - i]) for i in range(max(0, k - NL + 1), NL) if 2 * i < k and k - i < NL]
+            if k % 2 == 0 and k // 2 < NL:
+                t.append((a.sub(k // 2), a.sub(k // 2), ca[k // 2] ** 2))
+            return t
+        split, res = self.plan27([terms], ba.value(self.p) ** 2)
+        for i in range(NL):
+            self.g.v_lshlrev_b32(a2.sub(i), 1, a.sub(i)); yield
+        yield from self.mont_columns27(ch, [terms], split, m, m if r is None else r)
+        return res
+
+    def dual27(self, ch, ch2, a, b, c, d, m, ba, bb, bc, bd, r=None, allow_split=True):
+        """r (default m) = REDC27 of a b + c d with ONE reduction on one chain; where a column can reach 2^64 (the bound
+        checker decides) it is closed in two parts: a b stays on the chain, c d + m p go to ch2's accumulator."""
+        ba, bb, bc, bd = (_bound(x) for x in (ba, bb, bc, bd))
+        groups = [self._terms27(a, b, self._caps(ba), self._caps(bb)), self._terms27(c, d, self._caps(bc), self._caps(bd))]
+        split, res = self.plan27(groups, ba.value(self.p) * bb.value(self.p) + bc.value(self.p) * bd.value(self.p), allow_split)
+        self.last_split = sorted(split)
+        yield from self.mont_columns27(ch, groups, split, m, m if r is None else r, ch2)
+        return res
+
+    def lazy_diff(self, ch, a, subs, s, dst, ba, bsubs):
+        """dst = a - sum(mult b) + 2^s p for subs = [(b, 1)] or [(b, 1), (q, 2)], carry-normalised: limbs 0 .. 24 below 2^29,
+        the top limb unmasked.  a None: 0.  The constant's limbs are literals (2^s p as 25 limbs and a wide top limb), the carry
+        runs signed through a VGPR: 4 instructions per limb (5 with the doubled subtrahend).  dst may alias any operand.
+        The checker wants 2^s p >= the subtrahends' bound (no negative value) and every partial sum inside 32 signed bits."""
+        g = self.g
+        ba = Bound(0) if a is None else _bound(ba)
+        bsubs = [_bound(x) for x in bsubs]
+        kp = self.p << s
+        K = limbs(kp, NL - 1) + [kp >> TOP_SHIFT]
+        ca = self._caps(ba)
+        cs = [self._caps(x) for x in bsubs]
+        low = sum(mult * x.value(self.p) for (_, mult), x in zip(subs, bsubs))
+        if low > kp:
+            raise BoundError("a lazy difference can be negative: subtrahends up to %.2f p against %d p" % (low / self.p, 1 << s))
+        res = Bound(ba.k + (1 << s), ba.slack)
+        self._caps(res)
+        cmin = cmax = 0
+        for i in range(NL):
+            hi = ca[i] + K[i] + cmax
+            lo = cmin - sum(mult * c[i] for (_, mult), c in zip(subs, cs))
+            if i + 1 < NL and (hi >> 31 or lo < -(1 << 31)):
+                raise BoundError("limb %d of a lazy difference leaves 32 signed bits" % i)
+            cmin, cmax = lo >> LB, hi >> LB
+        t, x, c = ch.t0, ch.acc.lo(), ch.t1
+        for i in range(NL):
+            if len(subs) == 1:
+                (b, mult), = subs
+                assert mult == 1
+                g.v_sub_u32(t, K[i], b.sub(i)); yield
+            else:
+                (b, mb), (q, mq) = subs
+                assert (mb, mq) == (1, 2)
+                g.v_lshl_add_u32(t, q.sub(i), 1, b.sub(i)); yield
+                g.v_sub_u32(t, K[i], t); yield
+            o = dst.sub(i) if i == NL - 1 else x
+            if a is None:
+                if i:
+                    g.v_add_u32(o, t, c); yield
+                else:
+                    g.v_mov_b32(o, t); yield
+            elif i:
+                g.v_add3_u32(o, t, a.sub(i), c); yield
+            else:
+                g.v_add_u32(o, t, a.sub(0)); yield
+            if i + 1 < NL:
+                g.v_ashrrev_i32(c, LB, x); yield
+                g.v_and_b32(dst.sub(i), S(self.s_lm), x); yield
+        return res
+
+    def zero_or_p_mask(self, ch, a, smask, stmp):
+        """smask (S pair) = lanes where the almost-reduced a is 0 mod p, i.e. 0 or p.  The whole wave first looks at the low
+        limb only (0 or p_0); the full comparison sits behind a wave-uniform branch that a lane takes with probability about 2^-28.
+        stmp: a second S pair.  Not to be interleaved (it branches)."""
+        g = self.g
+        skip = g.uniq("zp_skip")
+        g.v_cmp_eq_u32(smask, 0, a.sub(0))
+        g.v_cmp_eq_u32(stmp, self.sP(0), a.sub(0))
+        g.s_or_b64(smask, smask, stmp)
+        g.s_cbranch_scc0(skip)
+        run(self.is_zero_mask(ch, a, smask))
+        x = ch.acc.lo()
+        g.v_xor_b32(x, self.sP(0), a.sub(0))
+        for i in range(1, NL):
+            g.v_xor_b32(ch.t1, self.sP(i), a.sub(i))
+            g.v_or_b32(x, x, ch.t1)
+        g.v_cmp_eq_u32(stmp, 0, x)
+        g.s_or_b64(smask, smask, stmp)
+        g.label(skip)
+
     def set_const(self, slot, value):
         for i, l in enumerate(limbs(value)):
             self.g.v_mov_b32(slot.sub(i), l)
@@ -378,6 +599,15 @@ class FieldGen:
 def run(gen):
     for _ in gen:
         pass
+
+
+def runv(gen):
+    """run a generator to its end and hand back its return value (the lazy routines return their result's Bound)"""
+    while True:
+        try:
+            next(gen)
+        except StopIteration as e:
+            return e.value
 
 
 def interleave(*gens):

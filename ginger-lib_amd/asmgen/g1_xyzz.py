@@ -24,11 +24,25 @@ Two launch forms of the same update (nothing between L_LOOP and L_ADV differs):
 debug=True adds stamps (shader clock, constant-rate clock, hardware id) per tile / per wave of a block into a side buffer;
 the shipped kernels hold none (build.py: GH_ASM_DEBUG).
 
-Order of the products (each one chain of mads, pairs back to back -- `seq`; the subtractions of a pair stay interleaved):
-  U2, S2  P, W  PP, RR  park RR  PPP, ZZ3  Q, ZZZ3  X3, T  dual(W T + V PPP)
+Order of the products (each one chain of mads, one after the other):
+  U2, S2  P, W  PP, RR  zero tests  park RR  PPP, ZZ3  Q, ZZZ3  X3, T  dual(W T + V PPP)
+
+The lazy forms (csrc/ec29.h xyzz_madd_lazy restates the update limb for limb).  Table rows, the task
+table and the stored buckets are as before (x R, fully reduced); the running sum is private to the kernel and lives in the
+forms the 27-digit reduction REDC27(a, b) = a b (R D)^-1 (field.py, D = 2^29) closes on:
+  X R D, V R D (parked)   ZZ R D^2, ZZZ R D^2 (registers)   U2, S2, P, W, PP, RR, PPP, Q, X3, T and the dual product: R D
+REDC27 returns less than a b / (R D) + p, "almost reduced" (below p + 2^733) whatever its operands were, so no product has a
+conditional subtraction behind it, and the differences are carry-normalised a - b + k p with an unmasked top limb:
+  P = U2 - X + 8 p in (3 p, 9 p)   W = S2 - V + 2 p in (p, 3 p)   X3 = RR - PPP - 2 Q + 4 p in (p, 5 p), parked unreduced
+  T = X3 - Q + 2 p in (2 p, 7 p)
+field.py checks every product's columns against these declared bounds when the kernel is built; the dual product closes the
+columns that could pass 2^64 in two parts.  A zero is 0 or p: "the sum is infinity" is ZZ in {0, p}, "acc == q" is PP and RR in
+{0, p}, tested after the two squarings (nothing is parked before).  L_INIT converts q into the forms (two products by
+c = R D^2 mod p), the epilogue converts back: x = REDC27(X, ZZZ), y = REDC27(Y, ZZ), z = REDC27(REDC27(ZZ, ZZZ), R) all carry
+R D^2 -- the same projective point -- and get the kernel's only conditional subtractions.
 """
 from .isa import Prog, V, S, VCC, EXEC, OFF, fix_hazards
-from .field import FieldGen, Chain, interleave, run, NL, LM
+from .field import FieldGen, Chain, Bound, run, runv, NL, LB
 
 AFF_BYTES = 2 * NL * 4          # 208
 PROJ_WORDS = 3 * NL             # 78
@@ -82,10 +96,10 @@ def slot(i):
 
 
 def seq(*gens):
-    """The products of a pair one after the other.  (Rounds 2-4 interleaved them instruction by instruction on two accumulator
-    chains; measured on the card, tools/asm_mb mul_seq2 / sqr_seq2 against mul_pair / sqr_pair, the sequential form is 1.6 % /
-    2.6 % faster at two waves per SIMD: a v_mad_u64_u32 whose 64-bit addend is its predecessor's result does not read it from
-    the register file.)"""
+    """The products of a pair one after the other (g1_reduce.py).  (Rounds 2-4 interleaved them instruction by instruction on two
+    accumulator chains; measured on the card, tools/asm_mb mul_seq2 / sqr_seq2 against mul_pair / sqr_pair, the sequential form is
+    1.6 % / 2.6 % faster at two waves per SIMD: a v_mad_u64_u32 whose 64-bit addend is its predecessor's result does not read it
+    from the register file.)"""
     for gen in gens:
         run(gen)
 
@@ -113,6 +127,20 @@ def build(name, p, one_mont, prefetch=False, split=4, persistent=False, debug=Fa
     f = FieldGen(g, p, S_P, S_NP, S_INV, S_LM)
     chA = Chain(V(248, 2), V(252), V(253), S(14, 2), S(16, 2))
     chB = Chain(V(250, 2), V(254), V(255), S(18, 2), S(22, 2))
+    # The lazy forms (module docstring): what each value of the update may reach.  AR = "almost reduced", the result of any
+    # REDC27 whose operands stay below 2^758; the routines of field.py check every product's columns against these bounds and
+    # return their result's bound, which is checked against the declaration it feeds (`within`).
+    c_lazy = one_mont * (1 << (2 * LB)) % p                         # R D^2 mod p: ZZ = ZZZ = 1 in the accumulator's form
+    AR = Bound(1, 1 << 733)
+    B_TAB = Bound(1)                                                # a table row, and q.y after neg_sel (at most p)
+    B_X = Bound(5, 1 << 733)                                        # the parked X: RR - PPP - 2 Q + 4 p
+
+    def within(b, decl):
+        assert b.value(p) <= decl.value(p), (b, decl)
+        return decl
+
+    def mul27(ch, a, b, m, ba, bb, r=None, decl=AR):
+        return within(runv(f.mul27(ch, a, b, m, ba, bb, r)), decl)
 
     def park_addr(which, w):
         # DS offsets are 16 bits: the third parked element is addressed from a second base register
@@ -234,20 +262,24 @@ def build(name, p, one_mont, prefetch=False, split=4, persistent=False, debug=Fa
     # ------------------------------------------------------------ epilogue: (X ZZZ : Y ZZ : ZZ ZZZ), infinity -> (0, 1, 0)
     g.label(L_DONE)
     g.s_mov_b64(EXEC, S_LAUNCH)
-    run(f.is_zero_mask(chA, E[0], S_ZERO))
-    # lanes that never parked anything (empty task) read whatever LDS holds: their result is replaced below
+    f.zero_or_p_mask(chA, E[0], S_ZERO, S_T0)
+    # lanes that never parked anything (empty task) read whatever LDS holds: their products wrap harmlessly and their result is
+    # replaced below
     park_get(PARK_X, E[2])
     park_get(PARK_V, E[3])
     g.v_cmp_ne_u32(S_NEGSEL, 0, V_SNEG)
     g.s_waitcnt(lgkmcnt=0)
-    for w in range(NL):                                             # garbage from LDS must still be a normalised element
-        g.v_and_b32(E[2].sub(w), S(S_LM), E[2].sub(w))
-        g.v_and_b32(E[3].sub(w), S(S_LM), E[3].sub(w))
-    run(f.neg_sel(chA, E[3], V_TMP, S_NEGSEL))
-    seq(f.mul(chA, E[2], E[1], E[4], E[2]),                         # x = X ZZZ -> E4
-        f.mul(chB, E[3], E[0], E[5], E[3]))                         # y = Y ZZ  -> E5
-    run(f.cond_sub(chA, E[0], E[6], E[0]))                          # ZZ, ZZZ leave the loop below 2 p: one of them reduced for z
-    run(f.mul(chA, E[0], E[1], E[6], E[2]))                         # z = ZZ ZZZ -> E6
+    b_neg = runv(f.lazy_diff(chA, None, [(E[3], 1)], 1, E[4], None, [AR]))        # 2 p - V: Y where sigma is set
+    for w in range(NL):
+        g.v_cndmask_b32(E[3].sub(w), E[3].sub(w), E[4].sub(w), S_NEGSEL)
+    mul27(chA, E[2], E[1], E[4], B_X, AR)                           # x = X ZZZ -> E4   (all three in the form R D^2)
+    mul27(chB, E[3], E[0], E[5], b_neg, AR)                         # y = Y ZZ  -> E5
+    mul27(chA, E[0], E[1], E[6], AR, AR)                            # ZZ ZZZ in the form R D^3 -> E6
+    run(f.set_const(E[7], one_mont))
+    mul27(chA, E[6], E[7], E[2], AR, B_TAB, r=E[6])                 # z: times R, the reduction takes one D back
+    run(f.cond_sub(chA, E[4], E[2], E[4]))                          # the output is fully reduced
+    run(f.cond_sub(chA, E[5], E[2], E[5]))
+    run(f.cond_sub(chA, E[6], E[2], E[6]))
     g.s_mov_b64(S_SAVE, EXEC)
     g.s_and_b64(EXEC, EXEC, S_ZERO)
     for w in range(NL):
@@ -324,47 +356,48 @@ def build(name, p, one_mont, prefetch=False, split=4, persistent=False, debug=Fa
         for j in range(4):
             g.global_load_dword(V_TOUCH, V_NADDR, OFF, offset=min(64 * j, AFF_BYTES - 4))
     run(f.neg_sel(chA, E[3], V_TMP, S_NEGSEL))
-    run(f.is_zero_mask(chA, E[0], S_ZERO))
+    f.zero_or_p_mask(chA, E[0], S_ZERO, S_T0)                       # the running sum is infinity: ZZ = 0 mod p
     g.s_cmp_lg_u64(S_ZERO, 0)
     g.s_cbranch_scc0(L_INIT_RET)
     g.long_branch(L_INIT, S_JMP)
     g.label(L_INIT_RET)
 
     # ------------------------------------------------------------ the update
-    seq(f.mul(chA, E[2], E[0], E[4], E[2]),                         # U2 = q.x ZZ   -> E4
-        f.mul(chB, E[3], E[1], E[5], E[3]))                         # S2 = q.y ZZZ  -> E5
+    mul27(chA, E[2], E[0], E[4], B_TAB, AR)                         # U2 = q.x ZZ   -> E4
+    mul27(chB, E[3], E[1], E[5], B_TAB, AR)                         # S2 = q.y ZZZ  -> E5
     park_get(PARK_X, E[2])
     park_get(PARK_V, E[3])
     g.s_waitcnt(lgkmcnt=0)
-    interleave(f.sub(chA, E[4], E[2], E[4]),                        # P = U2 - X    -> E4
-               f.sub(chB, E[5], E[3], E[5]))                        # W = S2 - V    -> E5
-    # acc == q (P == 0 and W == 0 in phase 0): the salt detour
-    interleave(f.is_zero_mask(chA, E[4], S_T0), f.is_zero_mask(chB, E[5], S_T1))
+    b_p = runv(f.lazy_diff(chA, E[4], [(E[2], 1)], 3, E[4], AR, [B_X]))           # P = U2 - X + 8 p -> E4: (3 p, 9 p)
+    b_w = runv(f.lazy_diff(chB, E[5], [(E[3], 1)], 1, E[5], AR, [AR]))            # W = S2 - V + 2 p -> E5: (p, 3 p)
+    within(runv(f.sqr27(chA, E[4], E[2], E[6], b_p)), AR)           # PP = P^2      -> E6
+    within(runv(f.sqr27(chB, E[5], E[3], E[7], b_w)), AR)           # RR = W^2      -> E7
+    # acc == q (P = 0 and W = 0 mod p, i.e. PP and RR in {0, p}, in phase 0): the salt detour.  Nothing is parked yet.
+    f.zero_or_p_mask(chA, E[6], S_T0, S_T2)
+    f.zero_or_p_mask(chB, E[7], S_T1, S_T2)
     g.v_cmp_eq_u32(S_T2, 0, V_PHASE)
     g.s_and_b64(S_T0, S_T0, S_T1)
     g.s_and_b64(S_DETOUR, S_T0, S_T2)
     g.s_cbranch_scc0(L_DET_RET)
     g.long_branch(L_DETOUR, S_JMP)
     g.label(L_DET_RET)
-    seq(f.sqr(chA, E[4], E[2], E[6]),                               # PP = P^2      -> E6
-        f.sqr(chB, E[5], E[3], E[7]))                               # RR = W^2      -> E7
     park_put(PARK_RR, E[7])
-    seq(f.mul(chA, E[4], E[6], E[2], E[4], dst=E[4]),               # PPP = P PP    -> E4
-        f.mul(chB, E[0], E[6], E[3], E[0], dst=E[0], reduce=False))   # ZZ3 = ZZ PP -> E0, below 2 p (see the epilogue)
+    mul27(chA, E[4], E[6], E[2], b_p, AR, r=E[4])                   # PPP = P PP    -> E4
+    mul27(chB, E[0], E[6], E[3], AR, AR, r=E[0])                    # ZZ3 = ZZ PP   -> E0
     park_get(PARK_X, E[2])
     g.s_waitcnt(lgkmcnt=0)
-    seq(f.mul(chA, E[2], E[6], E[3], E[2], dst=E[2]),               # Q = X PP      -> E2
-        f.mul(chB, E[1], E[4], E[7], E[1], dst=E[1], reduce=False))   # ZZZ3 = ZZZ PPP -> E1, below 2 p
+    mul27(chA, E[2], E[6], E[3], B_X, AR, r=E[2])                   # Q = X PP      -> E2
+    mul27(chB, E[1], E[4], E[7], AR, AR, r=E[1])                    # ZZZ3 = ZZZ PPP -> E1
     park_get(PARK_RR, E[3])
     g.s_waitcnt(lgkmcnt=0)
-    run(f.sub(chA, E[3], E[4], E[3]))                               # X3 = RR - PPP - 2 Q -> E3
-    run(f.sub(chA, E[3], E[2], E[3]))
-    run(f.sub(chA, E[3], E[2], E[3]))
+    within(runv(f.lazy_diff(chA, E[3], [(E[4], 1), (E[2], 2)], 2, E[3], AR, [AR, AR])), B_X)    # X3 = RR - PPP - 2 Q + 4 p -> E3
     park_put(PARK_X, E[3])
     park_get(PARK_V, E[6])
-    run(f.sub(chA, E[3], E[2], E[2]))                               # T = X3 - Q    -> E2
+    b_t = runv(f.lazy_diff(chA, E[3], [(E[2], 1)], 1, E[2], B_X, [AR]))           # T = X3 - Q + 2 p -> E2: (2 p, 7 p)
     g.s_waitcnt(lgkmcnt=0)
-    run(f.dual(chA, chB, E[5], E[2], E[6], E[4], E[7], E[6]))       # W T + V PPP = -sigma Y3 -> E7: the new V, sigma flips
+    # W T + V PPP = -sigma Y3 -> E7: the new V, sigma flips.  W and T stay lazy: the columns that can pass 2^64 close in two parts
+    within(runv(f.dual27(chA, chB, E[5], E[2], E[6], E[4], E[7], b_w, b_t, AR, AR)), AR)
+    g.dual_split = f.last_split
     park_put(PARK_V, E[7])
     g.v_xor_b32(V_SNEG, 1, V_SNEG)
 
@@ -389,10 +422,12 @@ def build(name, p, one_mont, prefetch=False, split=4, persistent=False, debug=Fa
     g.label(L_INIT)
     g.s_mov_b64(S_SAVE, EXEC)
     g.s_mov_b64(EXEC, S_ZERO)
-    park_put(PARK_X, E[2])
-    park_put(PARK_V, E[3])
-    run(f.set_const(E[0], one_mont))
-    run(f.set_const(E[1], one_mont))
+    run(f.set_const(E[0], c_lazy))                                  # ZZ = ZZZ = 1 in the form R D^2
+    run(f.set_const(E[1], c_lazy))
+    mul27(chA, E[2], E[0], E[4], B_TAB, B_TAB)                      # X = q.x, V = q.y in the form R D
+    mul27(chB, E[3], E[0], E[5], B_TAB, B_TAB)
+    park_put(PARK_X, E[4])
+    park_put(PARK_V, E[5])
     g.s_andn2_b64(EXEC, S_SAVE, S_ZERO)
     g.s_cbranch_execz(L_ADV)
     g.long_branch(L_INIT_RET, S_JMP)
@@ -416,4 +451,28 @@ def build(name, p, one_mont, prefetch=False, split=4, persistent=False, debug=Fa
     g.s_cbranch_execz(L_ADV)
     g.long_branch(L_DET_RET, S_JMP)
     g.hazard_nops = fix_hazards(g)      # isa.py: the gfx950 VALU -> SGPR -> VALU wait states
+    g.loop_labels = (L_LOOP, L_ADV)
     return g
+
+
+def update_counts(g):
+    """What one iteration of the list walk issues on its common path (L_LOOP round to the jump back: the running sum is not
+    infinity, no low limb passes a zero filter, so every forward s_cbranch_scc0 is taken), counted from the emitted
+    instructions: the figures build.py writes into the build record and DESIGN.md section 4 quotes."""
+    at = {i.args[0]: n for n, i in enumerate(g.ins) if i.op == "label"}
+    n, end = at[g.loop_labels[0]], None
+    total = valu = mads = 0
+    while end is None:
+        i = g.ins[n]
+        n += 1
+        if i.op in ("label", "comment"):
+            continue
+        total += 1
+        valu += i.op.startswith("v_")
+        mads += i.op == "v_mad_u64_u32"
+        if i.op == "s_cbranch_scc0" and at[i.args[0]] > n:
+            n = at[i.args[0]]
+        elif i.op == "long_branch":
+            assert i.args[0] == g.loop_labels[0]
+            end = n
+    return dict(update_instructions=total, update_valu=valu, update_mads=mads)

@@ -98,7 +98,11 @@ class Wave:
         return self.S[126] | (self.S[127] << 32)
 
     def em(self):
-        return mask_arr(self.exec_mask())
+        m = self.exec_mask()
+        if m != getattr(self, "_em_key", None):                     # EXEC changes rarely: keep its lane array
+            self._em_key, self._em = m, mask_arr(m)
+            self._em.setflags(write=False)
+        return self._em
 
     # ---- operand access
     def ridx(self, r):
@@ -186,6 +190,8 @@ class Wave:
             self._inflight_lgkm = set()
             self._vm_fifo = []
         lg = self._inflight_lgkm
+        if not vm and not lg and not op.startswith(("global_", "ds_", "s_load")):
+            return                                                            # nothing in flight and nothing issued: the common case
         regs = set()
         for a in i.args:
             if isinstance(a, Reg) and a.kind in ("v", "a"):

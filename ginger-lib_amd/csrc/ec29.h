@@ -165,4 +165,62 @@ template <class C, class F = typename C::F> GH_HD Proj<C> xyzz_to_proj(const Xyz
     return Proj<C>{F::mul(p.x, p.zzz), F::mul(p.y, p.zz), F::mul(p.zz, p.zzz)};
 }
 
+// ----- The lazy G1 bucket update: what the generated kernels gh_asm_acc_g1_* compute (asmgen/g1_xyzz.py), as plain C++ over
+// one prime P.  Table rows stay x R; the running sum is private to a task and lives in the forms that REDC27 (fp29.h, D = 2^29)
+// closes on:  X R D,  V R D with V = sigma Y,  ZZ R D^2,  ZZZ R D^2.  Every product is a 27-digit reduction without a
+// conditional subtraction, every difference a carry-normalised a - b + 2^s p:
+//   P = U2 - X + 8p in (3p, 9p)   W = S2 - V + 2p in (p, 3p)   X3 = RR - PPP - 2Q + 4p in (p, 5p), kept unreduced
+//   T = X3 - Q + 2p in (2p, 7p)   V3 = REDC27(W T + V PPP), W and T lazy (fp_mul2s27 closes two columns in two parts)
+// A zero is 0 or p: infinity is ZZ in {0, p}; acc == q is PP and RR in {0, p}, seen after the two squarings.
+// msm_accumulate_xyzz_kernel keeps xyzz_madd: its buckets are the same points.
+struct XyzzLazy {
+    Fp x, v, zz, zzz;
+    uint32_t sneg;                // sigma: Y = sneg ? -V : V
+};
+GH_HD XyzzLazy xyzz_lazy_zero() { return XyzzLazy{fp_zero(), fp_zero(), fp_zero(), fp_zero(), 0u}; }
+template <class P> GH_HD bool xyzz_lazy_is_zero(const XyzzLazy& s) { return fp_is_zero_or_p<P>(s.zz); }
+// s += (neg ? -q : q) for q = (qx, qy) a table row; q == s is reported through `same` with s unchanged
+template <class P> GH_HD void xyzz_madd_lazy(XyzzLazy& s, const Fp& qx, const Fp& qy_row, bool neg, bool& same) {
+    same = false;
+    const Fp qy = (neg != (s.sneg != 0)) ? fp_neg_lazy<P>(qy_row) : qy_row;
+    if (xyzz_lazy_is_zero<P>(s)) {                 // init conversion: two products by c = R D^2
+        const Fp c = fp_lazy_one<P>();
+        s.x = fp_mul27<P>(qx, c);
+        s.v = fp_mul27<P>(qy, c);
+        s.zz = c;
+        s.zzz = c;
+        return;
+    }
+    const Fp pp = fp_lazy_sub<P, 3>(fp_mul27<P>(qx, s.zz), s.x);
+    const Fp w = fp_lazy_sub<P, 1>(fp_mul27<P>(qy, s.zzz), s.v);
+    const Fp p2 = fp_sqr27<P>(pp);
+    const Fp rr = fp_sqr27<P>(w);
+    if (fp_is_zero_or_p<P>(p2) && fp_is_zero_or_p<P>(rr)) { same = true; return; }
+    const Fp p3 = fp_mul27<P>(pp, p2);
+    const Fp q = fp_mul27<P>(s.x, p2);
+    s.zz = fp_mul27<P>(s.zz, p2);
+    s.zzz = fp_mul27<P>(s.zzz, p3);
+    s.x = fp_lazy_x3<P>(rr, p3, q);
+    const Fp t = fp_lazy_sub<P, 1>(s.x, q);
+    s.v = fp_mul2s27<P>(w, t, s.v, p3);            // W T + V PPP = -sigma Y3: the new V, sigma flips
+    s.sneg ^= 1u;
+}
+// exit conversion: (X ZZZ : Y ZZ : ZZ ZZZ), all three in the form R D^2 (the same projective point as xyzz_to_proj's),
+// fully reduced; infinity -> (0, 1, 0)
+template <class P> GH_HD void xyzz_lazy_to_proj(const XyzzLazy& s, Fp& x, Fp& y, Fp& z) {
+    if (xyzz_lazy_is_zero<P>(s)) {
+        x = fp_zero();
+        y = fp_one<P>();
+        z = fp_zero();
+        return;
+    }
+    const Fp yy = s.sneg ? fp_lazy_sub<P, 1>(fp_zero(), s.v) : s.v;
+    x = fp_mul27<P>(s.x, s.zzz);
+    y = fp_mul27<P>(yy, s.zz);
+    z = fp_mul27<P>(fp_mul27<P>(s.zz, s.zzz), fp_one<P>());       // R D^3, times R: the reduction takes one D back
+    fp_cond_sub<P>(x);
+    fp_cond_sub<P>(y);
+    fp_cond_sub<P>(z);
+}
+
 }  // namespace gh
