@@ -45,7 +45,7 @@ def programs():
         for k in (6, 7, 8):
             progs.append(ntt_pass.build("gh_asm_ntt_%s_k%d" % (tag, k), prime, k))
     progs.append(microbench.build("gh_asm_mb_mulpair", P4))
-    if os.environ.get("GH_ASM_DEBUG"):          # stage markers for tools/asm_g2_check.py (not shipped)
+    if os.environ.get("GH_ASM_DEBUG"):          # stage markers for tools/asm_g2_dbg.py (not shipped)
         progs.append(g2_rounds.build("gh_asm_aff_f2_bwd_r0_dbg", c2, False, True, debug=True))
         for tag, prime in (("p4", P4), ("p6", P6)):     # stamped accumulation kernels for tools/acc_timeline.py (not shipped)
             progs.append(g1_xyzz.build("gh_asm_acc_g1_%s_dbg" % tag, prime, R % prime, debug=True))
@@ -57,18 +57,24 @@ def programs():
     return progs
 
 
-def build(outdir):
+def assemble(progs, outdir, stem="gh_asm"):
+    """module text of progs -> OUTDIR/STEM.s, .o, .hsaco; returns (code object path, per-kernel register info)"""
     os.makedirs(outdir, exist_ok=True)
-    progs = programs()
     text, infos = module_text(progs)
-    s_path = os.path.join(outdir, "gh_asm.s")
+    s_path = os.path.join(outdir, stem + ".s")
     with open(s_path, "w") as f:
         f.write(text)
-    o_path = os.path.join(outdir, "gh_asm.o")
-    co_path = os.path.join(outdir, "gh_asm.hsaco")
+    o_path = os.path.join(outdir, stem + ".o")
+    co_path = os.path.join(outdir, stem + ".hsaco")
     subprocess.run([os.path.join(LLVM, "clang"), "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950",
                     "-c", s_path, "-o", o_path], check=True)
     subprocess.run([os.path.join(LLVM, "ld.lld"), "-shared", o_path, "-o", co_path], check=True)
+    return co_path, infos
+
+
+def build(outdir, progs=None):
+    progs = programs() if progs is None else progs
+    co_path, infos = assemble(progs, outdir)
     for p in progs:
         infos[p.name]["instructions"] = p.count()
         infos[p.name]["lds_bytes"] = p.lds_bytes

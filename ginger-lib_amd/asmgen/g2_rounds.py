@@ -113,7 +113,7 @@ def build(name, cfg, fwd, r0, debug=False):
         g.s_mov_b64(EXEC, S_LIVE)
 
     def dbg(stage):
-        """debug builds: flag[1 + wave of the block] = stage (tools/asm_g2_check.py)"""
+        """debug builds: flag[1 + wave of the block] = stage (tools/asm_g2_dbg.py)"""
         if not debug:
             return
         g.s_mov_b64(S_T1, EXEC)

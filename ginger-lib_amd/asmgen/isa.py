@@ -370,3 +370,95 @@ def fix_hazards(prog):
     found, out = hazard_scan(prog, True)
     prog.ins = out
     return len(found)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Which operands an instruction writes and which it reads, and as what: the register bookkeeping of sim.py's strict mode
+# (a read of a register nobody wrote) and of the dependency scanner that lives with the card runner (tests/asm_card.py).
+SCC = Reg("scc", 0, 1)
+SCC_READERS = {"s_addc_u32", "s_subb_u32", "s_cselect_b64", "s_cselect_b32", "s_cbranch_scc0", "s_cbranch_scc1"}
+SCC_WRITERS = {"s_and_b32", "s_or_b32", "s_lshl_b32", "s_lshr_b32", "s_add_u32", "s_addc_u32", "s_sub_u32", "s_sub_i32", "s_subb_u32",
+               "s_and_b64", "s_or_b64", "s_xor_b64", "s_andn2_b64", "s_orn2_b64", "s_not_b64", "s_lshl_b64", "s_min_u32",
+               "s_and_saveexec_b64", "s_or_saveexec_b64", "long_branch"}
+NO_OPERANDS = {"s_nop", "s_waitcnt", "s_barrier", "s_sleep", "s_setprio", "s_clause", "s_endpgm", "s_branch"}
+
+
+def unit_of(i):
+    op = i.op
+    if op.startswith("v_"):
+        return "VALU"
+    if op.startswith("global_"):
+        return "VMEM"
+    if op.startswith("ds_"):
+        return "LDS"
+    if op.startswith("s_load") or op.startswith("s_mem"):
+        return "SMEM"
+    return "SALU"
+
+
+def roles(i):
+    """-> (dests, sources): the registers instruction i writes, and (register, role) for those it reads.  Roles: src (VALU / SALU
+    source), mask (select mask), carry (carry-in), const (an SGPR as a 32-bit VALU source), pair (an SGPR pair as a 64-bit VALU
+    source), addr, data (store / atomic data), rfl (v_readfirstlane source), exec (the lane mask of a VALU / VMEM / LDS
+    instruction), scc."""
+    op, a = i.op, i.args
+    if op in ("label", "comment") or op in NO_OPERANDS:
+        return [], []
+    regs = lambda xs: [x for x in xs if isinstance(x, Reg)]
+    unit = unit_of(i)
+    if unit == "VALU":
+        nd = 2 if op in CARRY_OUT_OPS else 1
+        dests, srcs = regs(a[:nd]), []
+        for k, x in enumerate(a[nd:]):
+            if not isinstance(x, Reg):
+                continue
+            last = k == len(a) - nd - 1
+            if op == "v_cndmask_b32" and last:
+                role = "mask"
+            elif op in ("v_addc_co_u32", "v_subb_co_u32", "v_subbrev_co_u32") and last:
+                role = "carry"
+            elif op in ("v_readfirstlane_b32", "v_readlane_b32"):
+                role = "rfl"
+            elif x.kind in ("s", "vcc", "exec"):
+                role = "pair" if x.n == 2 else "const"
+            else:
+                role = "src"
+            srcs.append((x, role))
+        if op not in ("v_readfirstlane_b32", "v_readlane_b32"):
+            srcs.append((EXEC, "exec"))
+        return dests, srcs
+    if unit == "VMEM":
+        if op.startswith("global_load"):
+            return regs(a[:1]), [(x, "addr") for x in regs(a[1:])] + [(EXEC, "exec")]
+        if op.startswith("global_store"):
+            return [], [(a[0], "addr"), (a[1], "data")] + [(x, "addr") for x in regs(a[2:])] + [(EXEC, "exec")]
+        if i.mods.get("sc0"):                                        # a returning atomic: dst, addr, data, saddr
+            return [a[0]], [(a[1], "addr"), (a[2], "data")] + [(x, "addr") for x in regs(a[3:])] + [(EXEC, "exec")]
+        return [], [(a[0], "addr"), (a[1], "data")] + [(x, "addr") for x in regs(a[2:])] + [(EXEC, "exec")]
+    if unit == "LDS":
+        if op.startswith("ds_read"):
+            return regs(a[:1]), [(x, "addr") for x in regs(a[1:])] + [(EXEC, "exec")]
+        if op.startswith("ds_write"):
+            return [], [(a[0], "addr")] + [(x, "data") for x in regs(a[1:])] + [(EXEC, "exec")]
+        return regs(a[:1]), [(a[1], "addr"), (a[2], "data"), (EXEC, "exec")]      # ds_bpermute_b32 / ds_permute_b32
+    if unit == "SMEM":
+        return regs(a[:1]), [(x, "addr") for x in regs(a[1:])]
+    # SALU
+    if op == "long_branch":
+        return [a[1], SCC], []
+    if op.startswith("s_cbranch_"):
+        what = op[len("s_cbranch_"):]
+        if what.startswith("scc"):
+            return [], [(SCC, "scc")]
+        return [], [((VCC if what.startswith("vcc") else EXEC), "src")]
+    if op.startswith("s_cmp_"):
+        return [SCC], [(x, "src") for x in regs(a)]
+    dests, srcs = regs(a[:1]), [(x, "src") for x in regs(a[1:])]
+    if op in SCC_WRITERS:
+        dests.append(SCC)
+    if op in SCC_READERS:
+        srcs.append((SCC, "scc"))
+    if op.endswith("saveexec_b64"):
+        dests.append(EXEC)
+        srcs.append((EXEC, "src"))
+    return dests, srcs

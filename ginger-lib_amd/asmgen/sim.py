@@ -7,7 +7,7 @@ Semantics follow the CDNA3/4 ISA manual (operand order of the *rev forms, v_cndm
 """
 import numpy as np
 
-from .isa import Reg
+from .isa import Reg, SCC_READERS, roles
 
 U32 = np.uint32
 U64 = np.uint64
@@ -37,10 +37,19 @@ class Memory:
         self.loads = 0
         self.stores = 0
 
-    def add(self, name, arr_u32, writable=False):
+    def add(self, name, arr_u32, writable=False, base=None):
+        """base: the address the region sits at (a device allocation: the same image then serves the simulator and the card);
+        without it the next synthetic address"""
         arr = np.ascontiguousarray(arr_u32, dtype=U32).reshape(-1)
-        base = self.next
-        self.next += (arr.nbytes + 0xFFFF) // 0x10000 * 0x10000 + 0x10000
+        if base is None:
+            base = self.next
+            self.next += (arr.nbytes + 0xFFFF) // 0x10000 * 0x10000 + 0x10000
+        else:
+            if base & 3:
+                raise ValueError("region %s at an unaligned address 0x%x" % (name, base))
+            for b, size, _, other, _ in self.regions:
+                if base < b + size and b < base + arr.nbytes:
+                    raise ValueError("region %s overlaps %s" % (name, other))
         self.regions.append((base, arr.nbytes, arr, name, writable))
         return base
 
@@ -74,8 +83,16 @@ class Memory:
 
 
 class Wave:
-    def __init__(self, prog, mem, lds_words=0):
+    def __init__(self, prog, mem, lds_words=0, strict=False):
+        """strict: reading a VGPR, AGPR or SGPR (VCC included) that neither the launch ABI (s[0:1] kernarg, s2 / s3 workgroup ids,
+        v0 work-item id, EXEC) nor an earlier instruction of this wave has written raises -- the zeros such a register holds here
+        are not what the card holds.  Tracked per register, not per lane."""
         self.prog = prog
+        self.strict = strict
+        self._written = {0, 1000, 1001, 1002, 1126, 1127}          # VGPRs / AGPRs as 0 .. 511, SGPR n as 1000 + n
+        if getattr(prog, "wg_id_y", 0):
+            self._written.add(1003)
+        self._rw = {}
         self.mem = mem
         self.V = np.zeros((512, LANES), dtype=U32)      # VGPRs 0..255, AGPRs at 256 + i
         self.S = [0] * 128
@@ -225,6 +242,33 @@ class Wave:
             else:
                 pend.update(-1 - r for r in range(dst.idx, dst.idx + dst.n))
 
+    # ---- strict mode: registers nobody has written
+    @staticmethod
+    def _regkeys(r):
+        if r.kind in ("v", "a"):
+            base = r.idx + (256 if r.kind == "a" else 0)
+            return range(base, base + r.n)
+        if r.kind in ("s", "vcc", "exec"):
+            return range(1000 + r.idx, 1000 + r.idx + r.n)
+        return ()
+
+    def _check_written(self, pc, i):
+        rw = self._rw.get(pc)
+        if rw is None:
+            dests, srcs = roles(i)
+            rd = frozenset(k for r, _ in srcs for k in self._regkeys(r))
+            wr = frozenset(k for r in dests for k in self._regkeys(r))
+            if i.op.startswith("s_load"):                                # the width is in the mnemonic, the operand names the first SGPR
+                n = {"dword": 1, "dwordx2": 2, "dwordx4": 4, "dwordx8": 8, "dwordx16": 16}[i.op[len("s_load_"):]]
+                wr = frozenset(range(1000 + i.args[0].idx, 1000 + i.args[0].idx + n))
+            rw = self._rw[pc] = (rd, wr)
+        rd, wr = rw
+        if not rd <= self._written:
+            bad = sorted(rd - self._written)
+            raise RuntimeError("%s reads a register nobody has written: %s" % (
+                i.text().strip(), ["v%d" % k if k < 256 else "a%d" % (k - 256) if k < 1000 else "s%d" % (k - 1000) for k in bad][:6]))
+        self._written |= wr
+
     # ---- run
     def run(self, max_steps=50_000_000):
         pc = 0
@@ -241,6 +285,10 @@ class Wave:
                 self.executed += 1
                 self.hist[op] = self.hist.get(op, 0) + 1
                 self._check_inflight(i)
+                if self.scc is None and op in SCC_READERS:
+                    raise RuntimeError("%s reads SCC, which a long_branch left undefined" % i.text().strip())
+                if self.strict:
+                    self._check_written(pc - 1, i)
                 if self.executed > max_steps:
                     raise RuntimeError("step limit")
                 if op == "s_endpgm":
@@ -367,8 +415,8 @@ def _alignbit(w, i):
 def _bfe(w, i):
     d, a, off, width = i.args
     o = np.asarray(w.rd(off)) & U32(31)
-    wd = int(np.asarray(w.rd(width)).reshape(-1)[0]) & 31
-    w.wr(d, (np.asarray(w.rd(a), dtype=U32) >> o) & U32((1 << wd) - 1))
+    wd = np.asarray(w.rd(width)) & U32(31)                           # per lane: the width may be a VGPR
+    w.wr(d, (np.asarray(w.rd(a), dtype=U32) >> o) & ((U32(1) << wd) - U32(1)))
 
 
 @op("v_mad_u64_u32")
@@ -655,7 +703,9 @@ def _s_branch(w, i):
 
 @op("long_branch")
 def _long_branch(w, i):
-    w.scc = 0
+    # the macro closes with s_addc_u32 on the high half of the PC: SCC is that carry (1 for every backward jump, hi + 0xFFFFFFFF
+    # + carry), not a value the program may use -- None makes the next reader raise (Wave.run)
+    w.scc = None
     return i.args[0]
 
 
@@ -823,7 +873,11 @@ def _mad_i64(w, i):
     c64 = np.asarray(np.broadcast_to(w.rd64(c), (LANES,)), dtype=U64).astype(np.int64)
     res = x * y + c64
     w.wr64(d, res.astype(U64))
-    w.wr_lanemask(sd, np.zeros(LANES, dtype=bool))
+    # {sdst, D} is the 65-bit signed sum (ISA manual; seen on the card): the mask bit is bit 64, set where the exact sum is negative.
+    # |x y| <= 2^62, so the exact sum's sign follows from the wrapped one unless the addition overflowed int64
+    prod = x * y
+    over = ((prod >= 0) == (c64 >= 0)) & ((res >= 0) != (prod >= 0))
+    w.wr_lanemask(sd, np.where(over, prod < 0, res < 0))
 
 
 def _f64_src(w, o):
@@ -911,14 +965,18 @@ HANDLERS["v_mul_u32_u24"] = _bin(lambda a, b: ((np.asarray(a) & U32(0xFFFFFF)).a
 
 @op("global_atomic_add")
 def _gatomic_add(w, i):
-    d, addr_op, data, saddr = i.args
+    if i.mods.get("sc0"):
+        d, addr_op, data, saddr = i.args
+    else:                                                                     # no return: no destination operand, nothing written
+        (addr_op, data, saddr), d = i.args, None
     addrs = np.broadcast_to(_vaddr(w, i, addr_op, saddr), (LANES,))
     em = w.em()
     vals = np.asarray(np.broadcast_to(w.rd(data), (LANES,)), dtype=U32)
     for l in np.nonzero(em)[0]:
         old = int(w.mem.load(int(addrs[l]), 1)[0])
         w.mem.store(int(addrs[l]), [(old + int(vals[l])) & M32])
-        w.V[w.ridx(d)][l] = old
+        if d is not None:
+            w.V[w.ridx(d)][l] = old
 
 
 # ------------------------------------------------------------------ clocks and hardware ids (the stamps of g1_xyzz.py debug=True):

@@ -40,6 +40,16 @@ def _get(w, s):
     return [unlimbs(w.V[s.idx:s.idx + NL, l]) for l in range(64)]
 
 
+def _execute(g, fill):
+    """a one-wave program over registers that fill(w) sets by hand, in the simulator -> the wave.  The register-level tests of
+    this module, test_asmgen_lazy.py and test_asmgen_ntt.py all run through this name: tests/test_gpu_asm_sim.py puts the card
+    runner here and runs the same tests, operands and expectations over the GPU."""
+    w = Wave(g, Memory())
+    fill(w)
+    w.run()
+    return w
+
+
 @pytest.mark.parametrize("tag", ["p4", "p6"])
 def test_field_routines_in_the_simulator(tag):
     p = pyref.FIELDS[tag].p
@@ -65,10 +75,7 @@ def test_field_routines_in_the_simulator(tag):
     c[2] = 0
     a[3] = b[3] = 1
     c[5], d[5] = a[5], b[5]                    # equal products on lane 5: the difference is zero
-    w = Wave(g, Memory())
-    for s, v in ((0, a), (1, b), (2, c), (3, d)):
-        _put(w, _slot(s), v)
-    w.run()
+    w = _execute(g, lambda w: [_put(w, _slot(s), v) for s, v in ((0, a), (1, b), (2, c), (3, d))])
     ri = pow(R, -1, p)
     e4 = [a[l] * b[l] * ri % p for l in range(64)]
     e5 = [c[l] * d[l] * ri % p for l in range(64)]
@@ -120,7 +127,7 @@ def _run_kernel(cname, lists, pts, seed=0):
         for wv in range(4):
             if blk * 256 + wv * 64 >= nt:
                 break
-            w = Wave(g, mem, lds_words=g.lds_bytes // 4)
+            w = Wave(g, mem, lds_words=g.lds_bytes // 4, strict=True)
             w.S[0], w.S[1], w.S[2] = a_karg & 0xFFFFFFFF, a_karg >> 32, blk
             w.V[0] = np.arange(64, dtype=np.uint32) + 64 * wv
             w.lds[:] = 0xDEADBEEF
@@ -274,15 +281,15 @@ def test_tower_field_routines_in_the_simulator(tag):
     ks = [13 if (l & 1) == 0 else 1 for l in range(64)]
     ks[3] = 15
     vals[0][3] = p - 1
-    w = Wave(g, Memory())
-    for s_ in range(6):
+    def fill(w):
+        for s_ in range(6):
+            for l in range(64):
+                for i, x in enumerate(limbs(vals[s_][l])):
+                    w.V[sl(s_).idx + i][l] = x
         for l in range(64):
-            for i, x in enumerate(limbs(vals[s_][l])):
-                w.V[sl(s_).idx + i][l] = x
-    for l in range(64):
-        w.V[19][l] = ks[l]
-        w.V[18][l] = 4 * (l ^ 1)
-    w.run()
+            w.V[19][l] = ks[l]
+            w.V[18][l] = 4 * (l ^ 1)
+    w = _execute(g, fill)
     get = lambda s_: [unlimbs(w.V[s_.idx:s_.idx + NL, l]) for l in range(64)]
     ri = pow(R, -1, p)
     assert get(sl(6)) == [(vals[0][l] * vals[1][l] + vals[2][l] * vals[3][l] + vals[4][l] * vals[5][l]) * ri % p for l in range(64)]

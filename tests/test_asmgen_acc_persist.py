@@ -75,14 +75,14 @@ def _setup(cname):
     return st
 
 
-def _memory(st, nt, stamps_at=None, budget=0):
+def _memory(st, nt, stamps_at=None, budget=0, mem=None):
     """-> (mem, kernarg address); the first nt tasks; the counter sits 16 bytes behind the task table as on the device.
     stamps_at: kernarg word of the pointer to a side buffer of two stamp records (the diagnostic kernels)"""
     C, p, r = st["C"], st["p"], R % st["p"]
 
     def enc(pt):
         return limbs(pt[0][0] * r % p) + limbs(pt[1][0] * r % p)
-    mem = Memory()
+    mem = Memory() if mem is None else mem                           # the card runner passes one at device addresses
     a_bases = mem.add("bases", np.array([enc(pt) for pt in st["pts"]], dtype=np.uint32))
     sorted_l, tasks = [], []
     for l in st["lists"][:nt]:
@@ -110,7 +110,7 @@ def _memory(st, nt, stamps_at=None, budget=0):
 
 
 def _wave(g, mem, a_karg, wg, tid0):
-    w = Wave(g, mem, lds_words=g.lds_bytes // 4)
+    w = Wave(g, mem, lds_words=g.lds_bytes // 4, strict=True)
     w.S[0], w.S[1], w.S[2] = a_karg & 0xFFFFFFFF, a_karg >> 32, wg
     w.V[0] = np.arange(64, dtype=np.uint32) + tid0
     w.lds[:] = 0xDEADBEEF

@@ -77,7 +77,7 @@ def sim_runner(g, bufs, scalars, waves):
     karg[18], karg[19], karg[20] = scalars
     a_karg = mem.add("karg", karg)
     for wv in range(waves + 1):                                   # one wave more than the work: it must leave at once
-        w = Wave(g, mem, lds_words=max(g.lds_bytes // 4, 1))
+        w = Wave(g, mem, lds_words=max(g.lds_bytes // 4, 1), strict=True)
         w.S[0], w.S[1], w.S[2] = a_karg & 0xFFFFFFFF, a_karg >> 32, wv // 4
         w.V[0] = np.arange(64, dtype=np.uint32) + 64 * (wv % 4)
         w.lds[:] = 0xDEADBEEF

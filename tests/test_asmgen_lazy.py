@@ -23,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ginger-lib_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pyref                                                      # noqa: E402
+import test_asmgen as TA                                          # noqa: E402  (its _execute: the simulator, or the card runner)
 import test_asmgen_acc_persist as TP                              # noqa: E402  (its memory image and launchers of both forms)
 from asmgen import g1_xyzz                                        # noqa: E402
 from asmgen.field import Bound, BoundError, Chain, FieldGen, LB, LM, NL, limbs, run, runv, unlimbs   # noqa: E402
@@ -79,11 +80,7 @@ def _get(w, s, normalised=True):
 
 def _run(g, puts):
     g.s_endpgm()
-    w = Wave(g, Memory())
-    for s, v in puts:
-        _put(w, s, v)
-    w.run()
-    return w
+    return TA._execute(g, lambda w: [_put(w, s, v) for s, v in puts])
 
 
 @pytest.mark.parametrize("tag", ["p4", "p6"])

@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ginger-lib_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pyref                                                      # noqa: E402
+import test_asmgen as TA                                          # noqa: E402  (its _execute: the simulator, or the card runner)
 from asmgen import ntt_pass as NP                                 # noqa: E402
 from asmgen.field import NL, limbs, unlimbs, FieldGen, Chain      # noqa: E402
 from asmgen.isa import Prog, V, S, fix_hazards                    # noqa: E402
@@ -27,7 +28,7 @@ _PROGS = {}
 
 def _prog(p, k):
     if (p, k) not in _PROGS:
-        _PROGS[(p, k)] = NP.build("ntt_k%d" % k, p, k)
+        _PROGS[(p, k)] = NP.build("ntt_%x_k%d" % (p & 0xFFFF, k), p, k)     # a name per prime: both go into one code object
     return _PROGS[(p, k)]
 
 
@@ -53,11 +54,12 @@ def root_of_unity(p, log_n):
     return pow(pow(g, q, p), 1 << (s - log_n), p)
 
 
-def run_pass(p, k, x, w, log_n, log_ns, inverse, pre=None, post=None, post_scalar=None, waves=None):
-    """x: N residues (as the ABI words hold them); returns the output vector (None where no simulated wave wrote)"""
+def run_pass(p, k, x, w, log_n, log_ns, inverse, pre=None, post=None, post_scalar=None, waves=None, card=None):
+    """x: N residues (as the ABI words hold them); returns the output vector (None where no simulated wave wrote)
+    card: an asm_card.Runner -- the image at device addresses, every wave of the grid in the simulator and on the GPU, word for word"""
     N = 1 << log_n
     g = _prog(p, k)
-    mem = Memory()
+    mem = Memory() if card is None else card.memory()
     xin = np.array([abi_words(v) for v in x], dtype=np.uint32)
     out = np.full((N, 24), 0xDEADBEEF, dtype=np.uint32)
     tw = np.array([limbs(pow(w, i, p) * R % p) for i in range(N)], dtype=np.uint32)
@@ -78,8 +80,13 @@ def run_pass(p, k, x, w, log_n, log_ns, inverse, pre=None, post=None, post_scala
     karg[10], karg[11], karg[12], karg[13], karg[14] = log_n, log_ns, 1 if inverse else 0, stride, n_waves
     a_karg = mem.add("karg", karg)
     todo = list(range(n_waves)) if waves is None else list(waves)
-    for wv in todo + [n_waves]:                                   # one wave beyond the work: it must leave at once
-        wave = Wave(g, mem)
+    if card is not None:
+        from asm_card import Launch
+        assert card.run(mem, [Launch(g, a_karg, (n_waves + 1 + 3) // 4, 256)]) == []
+        mem.release()
+        todo = None
+    for wv in [] if todo is None else todo + [n_waves]:                                   # one wave beyond the work: it must leave at once
+        wave = Wave(g, mem, strict=True)
         wave.S[0], wave.S[1], wave.S[2] = a_karg & 0xFFFFFFFF, a_karg >> 32, wv // 4
         wave.V[0] = np.arange(64, dtype=np.uint32) + 64 * (wv % 4)
         wave.run()
@@ -151,13 +158,13 @@ def test_add_and_difference_routines_against_integers():
     a[3], b[3] = p - 1, 0
     a[4], b[4] = 1, p - 1                       # a + b == p exactly
     a[5], b[5] = (p + 1) // 2, (p - 1) // 2     # a + b == p
-    w = Wave(g, Memory())
-    for l in range(64):
-        la, lb = limbs(a[l]), limbs(b[l])
-        for i in range(NL):
-            w.V[20 + i][l] = la[i]
-            w.V[46 + i][l] = lb[i]
-    w.run()
+    def fill(w):
+        for l in range(64):
+            la, lb = limbs(a[l]), limbs(b[l])
+            for i in range(NL):
+                w.V[20 + i][l] = la[i]
+                w.V[46 + i][l] = lb[i]
+    w = TA._execute(g, fill)
     for l in range(64):
         s = unlimbs([int(w.V[20 + i][l]) for i in range(NL)])
         d = unlimbs([int(w.V[72 + i][l]) for i in range(NL)])
@@ -166,8 +173,12 @@ def test_add_and_difference_routines_against_integers():
         assert d == a[l] - b[l] + p
 
 
-@pytest.mark.parametrize("k", [8, 7, 6])
-def test_first_pass_of_a_wave_against_the_dft(k):
+FIRST_PASS = [8, 7, 6]
+LATER_PASS = [(8, False, None), (7, True, "scalar"), (6, True, "table"), (6, False, "pre")]
+
+
+def first_pass_case(k):
+    """-> (arguments of run_pass / model_pass, the waves whose columns are checked against the model)"""
     p = _fr("mnt4753_g1")
     log_n = k + 2 if k < 8 else 10
     N = 1 << log_n
@@ -175,17 +186,10 @@ def test_first_pass_of_a_wave_against_the_dft(k):
     rnd = random.Random(100 + k)
     x = [rnd.randrange(p) for _ in range(N)]
     x[0], x[1] = 0, p - 1
-    C = 1 << (8 - k)
-    waves = [0, (N >> 8) - 1]
-    got = run_pass(p, k, x, w, log_n, 0, False, waves=waves)
-    cols = [wv * C + c for wv in waves for c in range(C)]
-    exp = model_pass(p, k, x, w, log_n, 0, False, columns=cols)
-    assert [i for i in range(N) if exp[i] is not None] == [i for i in range(N) if got[i] is not None]
-    assert all(got[i] == exp[i] for i in range(N) if exp[i] is not None)
+    return (p, k, x, w, log_n, 0, False), {}, [0, (N >> 8) - 1]
 
 
-@pytest.mark.parametrize("k,inverse,fac", [(8, False, None), (7, True, "scalar"), (6, True, "table"), (6, False, "pre")])
-def test_later_pass_with_twiddles_and_factors(k, inverse, fac):
+def later_pass_case(k, inverse, fac):
     p = _fr("mnt6753_g1")
     log_ns = 3
     log_n = k + log_ns
@@ -200,12 +204,28 @@ def test_later_pass_with_twiddles_and_factors(k, inverse, fac):
         kw["post"] = [rnd.randrange(p) for _ in range(N)]
     elif fac == "pre":
         kw["pre"] = [rnd.randrange(p) for _ in range(N)]
-    C = 1 << (8 - k)
     n_waves = N >> 8
-    waves = sorted({0, n_waves - 1, n_waves // 2})
-    got = run_pass(p, k, x, w, log_n, log_ns, inverse, waves=waves, **kw)
+    return (p, k, x, w, log_n, log_ns, inverse), kw, sorted({0, n_waves - 1, n_waves // 2})
+
+
+@pytest.mark.parametrize("k", FIRST_PASS)
+def test_first_pass_of_a_wave_against_the_dft(k):
+    args, kw, waves = first_pass_case(k)
+    N, C = len(args[2]), 1 << (8 - k)
+    got = run_pass(*args, waves=waves)
     cols = [wv * C + c for wv in waves for c in range(C)]
-    exp = model_pass(p, k, x, w, log_n, log_ns, inverse, columns=cols, **kw)
+    exp = model_pass(*args, columns=cols)
+    assert [i for i in range(N) if exp[i] is not None] == [i for i in range(N) if got[i] is not None]
+    assert all(got[i] == exp[i] for i in range(N) if exp[i] is not None)
+
+
+@pytest.mark.parametrize("k,inverse,fac", LATER_PASS)
+def test_later_pass_with_twiddles_and_factors(k, inverse, fac):
+    args, kw, waves = later_pass_case(k, inverse, fac)
+    N, C = len(args[2]), 1 << (8 - k)
+    got = run_pass(*args, waves=waves, **kw)
+    cols = [wv * C + c for wv in waves for c in range(C)]
+    exp = model_pass(*args, columns=cols, **kw)
     assert [i for i in range(N) if exp[i] is not None] == [i for i in range(N) if got[i] is not None]
     assert all(got[i] == exp[i] for i in range(N) if exp[i] is not None)
 

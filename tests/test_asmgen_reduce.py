@@ -37,8 +37,9 @@ def _prog(cname):
     return _PROGS[cname]
 
 
-def _run(cname, items, RW, count, valid, L):
-    """items: RW * count affine points (None = infinity) -> per program: flag, [(run, wacc) per lane] as affine points"""
+def _run(cname, items, RW, count, valid, L, card=None):
+    """items: RW * count affine points (None = infinity) -> per program: flag, [(run, wacc) per lane] as affine points
+    card: an asm_card.Runner -- the image at device addresses, the same grid in the simulator and on the GPU, word for word"""
     C = pyref.CURVES[cname]
     p = C.F.p
     r = R % p
@@ -53,7 +54,7 @@ def _run(cname, items, RW, count, valid, L):
             return limbs(0) + limbs(r) + limbs(0) if n % 2 else limbs(rnd.randrange(p)) + limbs(rnd.randrange(p)) + limbs(0)
         z = rnd.randrange(1, p)
         return limbs(pt[0][0] * z % p * r % p) + limbs(pt[1][0] * z % p * r % p) + limbs(z * r % p)
-    mem = Memory()
+    mem = Memory() if card is None else card.memory()
     a_items = mem.add("items", np.array([enc(n, pt) for n, pt in enumerate(items)], dtype=np.uint32))
     a_out = mem.add("out", np.full((nprog * 64 * 2, 78), 0xDEADBEEF, dtype=np.uint32), writable=True)
     a_slabs = mem.add("slabs", np.full(nprog * g1_reduce.SLAB_BYTES // 4, 0xDEADBEEF, dtype=np.uint32), writable=True)
@@ -64,9 +65,13 @@ def _run(cname, items, RW, count, valid, L):
     karg[8:13] = (count, valid, segs, L, nprog)
     a_karg = mem.add("karg", karg)
     assert g.kernarg_bytes == 56
-    for w_ in range(RW):
+    if card is not None:
+        from asm_card import Launch
+        assert card.run(mem, [Launch(g, a_karg, (segs, RW), 64)]) == []
+        mem.release()
+    for w_ in range(RW if card is None else 0):
         for seg in range(segs):
-            w = Wave(g, mem)
+            w = Wave(g, mem, strict=True)
             w.S[0], w.S[1], w.S[2], w.S[3] = a_karg & 0xFFFFFFFF, a_karg >> 32, seg, w_
             w.V[0] = np.arange(64, dtype=np.uint32)
             w.V[40:256] = 0x1234567                                 # registers start as garbage too
