@@ -313,6 +313,22 @@ template <class P> int lagrange_t(int fidx, uint32_t log_n, const uint64_t* tau1
     return rc;
 }
 
+template <class P> int domain_table_t(int fidx, uint32_t log_n, const Fp** tw) {
+    if ((int)log_n >= FieldConsts<P>::two_adicity) { g_err = "domain exceeds the field's 2-adicity"; return GH_E_UNSUPPORTED; }
+    *tw = nullptr;
+    if (log_n == 0) return GH_OK;
+    Domain* d;
+    if (int rc = get_domain<P>(fidx, (int)log_n, false, false, &d)) return rc;
+    *tw = d->tw;
+    return GH_OK;
+}
+int domain_table(gh_field_t field, uint32_t log_n, const Fp** tw) {
+    if (field == GH_MNT4753_FR) return domain_table_t<P6>(0, log_n, tw);
+    if (field == GH_MNT6753_FR) return domain_table_t<P4>(1, log_n, tw);
+    g_err = "unknown field id";
+    return GH_E_BAD_ARG;
+}
+
 int sap_witness_map(gh_field_t field, void* d_a, void* d_c, uint32_t log_n, const uint64_t* d1, const uint64_t* d2, void* d_h) {
     if (field == GH_MNT4753_FR) return sap_witness_map_t<P6>(0, d_a, d_c, log_n, d1, d2, d_h);
     if (field == GH_MNT6753_FR) return sap_witness_map_t<P4>(1, d_a, d_c, log_n, d1, d2, d_h);

@@ -239,6 +239,8 @@ int witness_map(gh_field_t field, void* d_a, void* d_b, void* d_c, uint32_t log_
 int sap_witness_map(gh_field_t field, void* d_a, void* d_c, uint32_t log_n, const uint64_t* d1, const uint64_t* d2, void* d_h);
 int batch_inverse(gh_field_t field, void* d_a, size_t n);
 int lagrange_coefficients(gh_field_t field, uint32_t log_n, const uint64_t* tau12, void* d_out);
+// *tw = the domain's table of group_gen^i, i < 2^log_n, in the internal form (built on first use); null for log_n = 0, which has none
+int domain_table(gh_field_t field, uint32_t log_n, const gh::Fp** tw);
 
 // ---- lock-held helpers for other units (schnorr.hip, ecvrf.hip); the caller holds api_mutex() and has run ensure_init()
 struct FixedTable;                                 // fixed_base.hip: a window table of one base
