@@ -17,10 +17,23 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PARAMS_JSON = os.path.join(_HERE, "golden", "poseidon_params.json")
 FIELD_OF = {"mnt4753": pyref.P6, "mnt6753": pyref.P4}     # Fr of MNT4-753 is the MNT6-753 base prime and vice versa
 FIELD_ID = {"mnt4753": 0, "mnt6753": 1}
+KATS_JSON = os.path.join(_HERE, "golden", "poseidon_kats.json")
 
 
 def load_params():
     return json.load(open(PARAMS_JSON))
+
+
+def phantom_root_kat():
+    """the one hash answer the reference ships (MNT4753_PHANTOM_MERKLE_ROOT; tests/golden/extract_poseidon_kats.py)
+    -> (tag, the input element: the sentence zero-padded to 96 bytes and read little-endian, the answer's twelve ABI words)"""
+    k = json.load(open(KATS_JSON))["mnt4753_phantom_merkle_root"]
+    data = k["sentence"].encode("ascii")
+    assert len(data) == 81 and k["input_bytes"] == 96
+    x = int.from_bytes(data.ljust(96, b"\0"), "little")
+    words = [int(w, 16) for w in k["words_montgomery_2p768"]]
+    assert len(words) == 12 and x < FIELD_OF[k["tag"]].p
+    return k["tag"], x, words
 
 
 class Poseidon:

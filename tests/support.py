@@ -134,6 +134,20 @@ def random_scalars_np(n, modulus_bits_top=49, seed=1, below=None):
     return s
 
 
+# ---- raw limb values at the extremes (the device builds of fp29.h: tests/test_gpu_parity.py, tests/test_gpu_tower_ops.py)
+def edge_values(p):
+    """raw limb values below p at which a carry, a conditional subtraction or a lazily reduced sum goes wrong first: around 0 and
+    p, around p / 2, the Montgomery radix, the top bit, every 29-bit limb saturated alone, and every run of saturated low limbs"""
+    v = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, (1 << 768) % p, 1 << 752, (1 << 752) - 1]
+    v += [((1 << 29) - 1) << (29 * j) for j in range(26)]
+    v += [(1 << k) - 1 for k in range(29, 726, 29)] + [(1 << 752) - 1]
+    out = []
+    for x in v:
+        if x < p and x not in out:
+            out.append(x)
+    return out
+
+
 # ---- oracle wrappers
 def oracle_msm(curve, bases, inf, scalars, threads=8):
     C = pyref.CURVES[curve]

@@ -10,6 +10,7 @@ import pytest
 
 import pyref
 import support as S
+from support import edge_values
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -158,19 +159,6 @@ def test_vec_ops(gpu):
 
 
 # ---- the device build of fp29.h at the extremes (tests/test_fp29_host.py has the host build of the same header there)
-def edge_values(p):
-    """raw limb values below p at which a carry, a conditional subtraction or a lazily reduced sum goes wrong first: around 0 and
-    p, around p / 2, the Montgomery radix, the top bit, every 29-bit limb saturated alone, and every run of saturated low limbs"""
-    v = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, (1 << 768) % p, 1 << 752, (1 << 752) - 1]
-    v += [((1 << 29) - 1) << (29 * j) for j in range(26)]
-    v += [(1 << k) - 1 for k in range(29, 726, 29)] + [(1 << 752) - 1]
-    out = []
-    for x in v:
-        if x < p and x not in out:
-            out.append(x)
-    return out
-
-
 @pytest.mark.parametrize("field", ["mnt4753_fr", "mnt6753_fr"])
 def test_vec_ops_at_the_extremes(gpu, field):
     """gh_vec_mul, gh_vec_sub_dev and gh_vec_scale on every ordered pair of edge_values, against Python integers: the ABI's words

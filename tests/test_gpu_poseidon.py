@@ -59,6 +59,28 @@ def test_evaluate_many_every_k(pos, sets, tag, k):
         pos.set_tuning(0, None)
 
 
+@pytest.mark.parametrize("k", [1, 2, 4, 8])
+def test_evaluate_many_reproduces_the_reference_phantom_merkle_root(pos, sets, k):
+    """the one hash answer the reference ships (MNT4753_PHANTOM_MERKLE_ROOT: the hash of ONE element), word for word, with the
+    element in rows 0, 63 and 64 of a batch of 65 single-element inputs"""
+    tag, x, words = poseidon_ref.phantom_root_kat()
+    R, prm = sets[tag]
+    rng = random.Random(5 + k)
+    vals = [rng.randrange(R.p) for _ in range(65)]
+    at = (0, 63, 64)
+    for i in at:
+        vals[i] = x
+    pos.set_tuning(k, None)
+    try:
+        out = pos.PoseidonHash(prm).evaluate_many(rows(R, vals).reshape(65, 1, 12)).reshape(65, 12)
+    finally:
+        pos.set_tuning(0, None)
+    for i in at:
+        assert [int(w) for w in out[i]] == words, (k, i)
+    for i in (1, 62):
+        assert R.from_abi(out[i]) == R.evaluate([vals[i]]), (k, i)
+
+
 @pytest.mark.parametrize("tag", TAGS)
 @pytest.mark.parametrize("k", [1, 2, 4, 8])
 def test_zero_sbox_inputs_inside_a_batch_and_last(pos, sets, tag, k):

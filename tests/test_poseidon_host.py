@@ -111,6 +111,28 @@ def test_host_permutation_matches_restatement(shim, refs, tag, k, slab):
         assert shim_perm(shim, P, b, k, slab) == [P.perm(s) for s in b]
 
 
+def test_restatement_reproduces_the_reference_phantom_merkle_root(refs):
+    """evaluate() against the one hash answer the reference ships (after_zero_perm anchors the permutation only)"""
+    tag, x, words = poseidon_ref.phantom_root_kat()
+    P = refs[tag]
+    assert P.to_abi(P.evaluate([x])) == words
+    assert P.evaluate([x]) == P.from_abi(words) != P.evaluate([x, 1])
+
+
+@pytest.mark.parametrize("k,slab", [(1, 0), (1, 1), (2, 0), (2, 1), (4, 0), (4, 1), (8, 1)])
+def test_host_permutation_reproduces_the_reference_phantom_merkle_root(shim, refs, k, slab):
+    """the same answer through the g++ build of the permutation: evaluate([x]) is element 0 of perm(after_zero_perm + (x, 0, C2));
+    the state in every position of a batch of k"""
+    tag, x, words = poseidon_ref.phantom_root_kat()
+    P = refs[tag]
+    state = [(P.azp[0] + x) % P.p, P.azp[1], (P.azp[2] + P.c2) % P.p]
+    rng = random.Random(40 + k)
+    for at in range(k):
+        b = [[rng.randrange(P.p) for _ in range(3)] for _ in range(k)]
+        b[at] = state
+        assert P.to_abi(shim_perm(shim, P, b, k, slab)[at][0]) == words, (k, slab, at)
+
+
 def test_poseidon_symbols_exported_and_kept_apart(gl):
     from ginger_lib_amd import poseidon
     lib = gl.load_library()
