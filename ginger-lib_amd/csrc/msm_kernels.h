@@ -265,9 +265,10 @@ static __device__ __forceinline__ uint32_t wave_agg_inc(uint32_t* base, uint32_t
 
 // ---------------------------------------------------------------- 1. digits + histogram
 // scalars: n x 24 words canonical (< r).  digits[w * n + i] = signed digit (0 = no contribution).
-// counts[w * win_stride + |d| - slot_shift] += 1; win_stride = nb = 2^(c-1) + 1 (slot 0 unused, slot_shift 0) gives every
-// window its own bucket set; win_stride = 0 files all windows into ONE bucket set (precomputed
-// shift tables, section 0 below: window w then reads its bases from table row w).  That merged set uses slot_shift 1:
+// counts[(w % sets) * win_stride + |d| - slot_shift] += 1; sets = num_windows, win_stride = nb = 2^(c-1) + 1 (slot 0 unused,
+// slot_shift 0) gives every window its own bucket set; sets = 1 files all windows into ONE bucket set (precomputed
+// shift tables, section 0 above: window w then reads its bases from table row w), a partial table's sets = G files window w
+// into set w % G and reads row w / G.  A merged set has win_stride = nb = 2^(c-1) and uses slot_shift 1:
 // slot = |d| - 1, exactly 2^(c-1) slots -- a power of two, so the bucket reduction's segments tile it without a
 // remainder (one straggling wave program on an already occupied SIMD doubled the whole launch); the weight of a slot
 // is then slot + 1 and the fold adds the plain sum of all buckets once (msm_fold.h fold_merged).
