@@ -15,20 +15,11 @@
 // zero), so no loop depends on the data and the lanes of a wave diverge nowhere.
 // Products, squarings counted as products, in units of the point's field: 1 S (x1^2, computed for every row) + 1 M + 1 S + 1 M
 // = 4 and the inversion.  G1: 4 + ~42 (fp_inv: ~40 and two products) = 46 Fq products.  G2 on MNT4-753: 4 Fq2 operations
-// = 10 Fq products, inv2 = 2 + 42 + 2: 56.  G2 on MNT6-753: 4 Fq3 operations = 22, inv3 = 9 + 42 + 3: 76.
+// = 10 Fq products, Mnt4Pairing::inv = 2 + 42 + 2: 56.  G2 on MNT6-753: 4 Fq3 operations = 22, Mnt6Pairing::inv = 9 + 42 + 3: 76.
 #pragma once
 #include "pairing29_mnt6.h"
 
 namespace gh {
-
-// 1 / a in the tower's base of an engine: Fq2 for MNT4-753, Fq3 for MNT6-753; zero gives zero
-template <class E> struct Gm17TowerInv;
-template <> struct Gm17TowerInv<Mnt4Pairing> {
-    static GH_HD Fp2T inv(const Fp2T& a) { return Mnt4Pairing::inv2(a); }
-};
-template <> struct Gm17TowerInv<Mnt6Pairing> {
-    static GH_HD Fp3T inv(const Fp3T& a) { return Mnt6Pairing::inv3(a); }
-};
 
 // what the sum needs of a group: F the field policy of a coordinate, a the curve's coefficient, inv the inverse
 template <class E> struct Gm17G1 {
@@ -39,7 +30,7 @@ template <class E> struct Gm17G1 {
 template <class E> struct Gm17G2 {
     typedef typename E::B F;
     static GH_HD typename F::T a() { return E::G2::mul_by_a(F::one()); }
-    static GH_HD typename F::T inv(const typename F::T& v) { return Gm17TowerInv<E>::inv(v); }
+    static GH_HD typename F::T inv(const typename F::T& v) { return E::inv(v); }
 };
 
 template <class T> struct Gm17Point {

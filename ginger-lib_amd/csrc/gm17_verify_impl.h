@@ -113,9 +113,8 @@ template <class E> int gm17_vk_ensure(gh_gm17_vk* h) {
     // e(-g_alpha, h_beta): one row of one variable pair
     PairIn in{};
     const uint8_t* zero = d_g1.as<const uint8_t>() + 3 * 192;
-    in.g1[0] = d_g1.as<const uint32_t>() + 2 * 48;
-    in.g2[0] = d_g2.as<const uint32_t>() + 2 * 2 * TW;
-    in.g1_inf[0] = in.g2_inf[0] = zero;
+    in.g1_rows(0, d_g1.as<const uint32_t>() + 2 * 48, zero, 0, 0);
+    in.g2_rows(0, d_g2.as<const uint32_t>() + 2 * 2 * TW, zero, 0, 0);
     if ((rc = launch_pairs<E, 1, 0>(in, nullptr, nullptr, 1, d_gt.as<uint64_t>(), nullptr))) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
     if ((rc = ensure_abc_tables<E>(h->query.data(), h->n_query, h->tables))) return rc;
@@ -133,82 +132,58 @@ int run_gm17_verify(gh_gm17_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, c
                     const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
     constexpr size_t TW = tower_words<E>() / 2;    // u64 words of a G2 point and of a GT element
     if (int rc = gm17_vk_ensure<E>(h)) return rc;
-    uint64_t *d_a, *d_b, *d_c, *d_in = nullptr, *d_psi, *d_ns1, *d_s2, *d_nb, *d_val1, *d_val2;
-    uint8_t *d_ai, *d_bi, *d_ci, *d_pi, *d_s1i, *d_s2i, *d_st, *d_st2;
-    int rc = dbuf("vb_pair_g1", n * 24, &d_a);
-    if (!rc) rc = dbuf("vb_pair_g2", n * TW, &d_b);
-    if (!rc) rc = dbuf("vb_pair_c", n * 24, &d_c);
-    if (!rc) rc = dbuf("vb_pair_i1", n, &d_ai);
-    if (!rc) rc = dbuf("vb_pair_i2", n, &d_bi);
-    if (!rc) rc = dbuf("vb_pair_i3", n, &d_ci);
-    if (!rc && n_inputs) rc = dbuf("vb_pair_in", n * n_inputs * 12, &d_in);
-    if (!rc) rc = dbuf("vb_xy", n * 24, &d_psi);
-    if (!rc) rc = dbuf("vb_inf", n, &d_pi);
+    VerifyBufs v;                                  // v.d_gic / v.d_gi hold g_psi, v.d_val test1's values until the compare
+    uint64_t *d_ns1, *d_s2, *d_nb, *d_val2;
+    uint8_t *d_s1i, *d_s2i, *d_st2;
+    int rc = verify_bufs<E>(n, n_inputs, v);
     if (!rc) rc = dbuf("vb_gm17_ns1", n * 24, &d_ns1);
     if (!rc) rc = dbuf("vb_gm17_s2", n * TW, &d_s2);
     if (!rc) rc = dbuf("vb_gm17_nb", n * TW, &d_nb);
     if (!rc) rc = dbuf("vb_gm17_i1", n, &d_s1i);
     if (!rc) rc = dbuf("vb_gm17_i2", n, &d_s2i);
-    if (!rc) rc = dbuf("vb_pair_val", n * TW, &d_val1);
-    if (!rc) rc = dbuf("vb_gm17_val2", n * TW, &d_val2);           // test1's values stay in vb_pair_val until the compare
-    if (!rc) rc = dbuf("vb_st", n, &d_st);
+    if (!rc) rc = dbuf("vb_gm17_val2", n * TW, &d_val2);
     if (!rc) rc = dbuf("vb_gm17_st2", n, &d_st2);
     if (rc) return rc;
     Phases ph{g_gm17_tm};
     if ((rc = ph.mark())) return rc;
-    if ((rc = up(d_a, a_xy, n * 24)) || (rc = up(d_b, b_xy, n * TW)) || (rc = up(d_c, c_xy, n * 24)) || (rc = up(d_ai, a_inf, n)) ||
-        (rc = up(d_bi, b_inf, n)) || (rc = up(d_ci, c_inf, n)) || (n_inputs && (rc = up(d_in, inputs, n * n_inputs * 12))) || (rc = ph.mark()))
+    if ((rc = upload_proofs<E>(v, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, n)) || (n_inputs && (rc = up(v.d_in, inputs, n * n_inputs * 12))) ||
+        (rc = ph.mark()))
         return rc;
-    GH_LAUNCH((proof_check_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_a, (const uint8_t*)d_ai,
-              (const uint32_t*)d_b, (const uint8_t*)d_bi, (const uint32_t*)d_c, (const uint8_t*)d_ci, n, curve_b<typename E::G1>(),
-              EngineHost<E>::g2_b(), d_st);
-    if ((rc = launch_g_ic<E>(h->d_query.as<const uint32_t>(), h->tables, d_in, n, n_inputs, d_psi, d_pi)) || (rc = ph.mark())) return rc;
+    GH_LAUNCH((proof_check_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)v.d_a, (const uint8_t*)v.d_ai,
+              (const uint32_t*)v.d_b, (const uint8_t*)v.d_bi, (const uint32_t*)v.d_c, (const uint8_t*)v.d_ci, n, curve_b<typename E::G1>(),
+              EngineHost<E>::g2_b(), v.d_st);
+    if ((rc = launch_g_ic<E>(h->d_query.as<const uint32_t>(), h->tables, v.d_in, n, n_inputs, v.d_gic, v.d_gi)) || (rc = ph.mark())) return rc;
     const uint32_t* key_g1 = h->d_g1.as<const uint32_t>();
     const uint32_t* key_g2 = h->d_g2.as<const uint32_t>();
     const uint8_t* zero = h->d_g1.as<const uint8_t>() + 3 * 192;
-    GH_LAUNCH((gm17_sums_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_a, (const uint8_t*)d_ai,
-              (const uint32_t*)d_b, (const uint8_t*)d_bi, (const uint8_t*)d_st, key_g1, key_g2 + 2 * 2 * TW, n, (uint32_t*)d_ns1, d_s1i,
+    GH_LAUNCH((gm17_sums_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)v.d_a, (const uint8_t*)v.d_ai,
+              (const uint32_t*)v.d_b, (const uint8_t*)v.d_bi, (const uint8_t*)v.d_st, key_g1, key_g2 + 2 * 2 * TW, n, (uint32_t*)d_ns1, d_s1i,
               (uint32_t*)d_s2, d_s2i, (uint32_t*)d_nb);
     HIPCHK(hipGetLastError());
     if ((rc = ph.mark())) return rc;
     const typename E::Coeff* tab = h->d_tab.as<const typename E::Coeff>();
     {   // test1: (-S1, S2) variable, (g_psi, h_gamma) and (C, h) prepared
         PairIn in{};
-        const uint64_t* g1s[3] = {d_ns1, d_psi, d_c};
-        const uint8_t* infs[3] = {d_s1i, d_pi, d_ci};
-        for (int j = 0; j < 3; j++) {
-            in.g1[j] = (const uint32_t*)g1s[j];
-            in.g1_inf[j] = infs[j];
-            in.g1_stride[j] = 48;
-            in.g1_inf_stride[j] = 1;
-        }
-        in.g2[0] = (const uint32_t*)d_s2;
-        in.g2_inf[0] = d_s2i;
-        in.g2_stride[0] = 2 * TW;
-        in.g2_inf_stride[0] = 1;
-        if ((rc = launch_pairs<E, 1, 2>(in, d_st, tab, n, d_val1, &ph))) return rc;
+        in.g1_rows(0, d_ns1, d_s1i);
+        in.g2_rows(0, d_s2, d_s2i, 2 * TW);
+        in.g1_rows(1, v.d_gic, v.d_gi);
+        in.g1_rows(2, v.d_c, v.d_ci);
+        if ((rc = launch_pairs<E, 1, 2>(in, v.d_st, tab, n, v.d_val, &ph))) return rc;
     }
     {   // test2: (g_gamma, -B) variable, g_gamma the key's for every row; (A, h_gamma) prepared: the first table
         PairIn in{};
-        in.g1[0] = key_g1 + 48;
-        in.g1_inf[0] = zero;                       // strides 0
-        in.g2[0] = (const uint32_t*)d_nb;
-        in.g2_inf[0] = d_bi;
-        in.g2_stride[0] = 2 * TW;
-        in.g2_inf_stride[0] = 1;
-        in.g1[1] = (const uint32_t*)d_a;
-        in.g1_inf[1] = d_ai;
-        in.g1_stride[1] = 48;
-        in.g1_inf_stride[1] = 1;
-        if ((rc = launch_pairs<E, 1, 1>(in, d_st, tab, n, d_val2, &ph))) return rc;
+        in.g1_rows(0, key_g1 + 48, zero, 0, 0);
+        in.g2_rows(0, d_nb, v.d_bi, 2 * TW);
+        in.g1_rows(1, v.d_a, v.d_ai);
+        if ((rc = launch_pairs<E, 1, 1>(in, v.d_st, tab, n, d_val2, &ph))) return rc;
     }
-    HIPCHK(hipMemcpyAsync(d_st2, d_st, n, hipMemcpyDeviceToDevice, g.stream));
-    GH_LAUNCH((gt_compare_kernel<(int)TW>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)d_val1, h->d_gt.as<const uint64_t>(), n, d_st);
+    HIPCHK(hipMemcpyAsync(d_st2, v.d_st, n, hipMemcpyDeviceToDevice, g.stream));
+    GH_LAUNCH((gt_compare_kernel<(int)TW>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)v.d_val, h->d_gt.as<const uint64_t>(), n, v.d_st);
     GH_LAUNCH((gt_compare_kernel<(int)TW>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)d_val2, h->d_gt.as<const uint64_t>() + TW, n, d_st2);
-    GH_LAUNCH(gm17_and_kernel, dim3(blocks(n, 256)), dim3(256), 0, g.stream, d_st, (const uint8_t*)d_st2, n);
+    GH_LAUNCH(gm17_and_kernel, dim3(blocks(n, 256)), dim3(256), 0, g.stream, v.d_st, (const uint8_t*)d_st2, n);
     HIPCHK(hipGetLastError());
     if ((rc = ph.mark())) return rc;
-    HIPCHK(hipMemcpyAsync(out_status, d_st, n, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(out_status, v.d_st, n, hipMemcpyDeviceToHost, g.stream));
     if ((rc = ph.mark())) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
     return ph.finish();
@@ -256,19 +231,7 @@ int api_gm17_vk_create(int engine, const uint64_t* g_alpha_g1_xy, const uint64_t
 template <class E>
 int api_gm17_verify(gh_gm17_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
                     const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
-    typedef typename E::PF PF;
-    if (n_inputs + 1 != h->n_query) { g_err = "the number of public inputs does not match query (MalformedVerifyingKey)"; return GH_E_BAD_ARG; }
-    if (n && (!a_xy || !a_inf || !b_xy || !b_inf || !c_xy || !c_inf || (n_inputs && !inputs) || !out_status)) {
-        g_err = "null argument";
-        return GH_E_BAD_ARG;
-    }
-    size_t ni = 0, b = 0;
-    if (mul_overflows(n, n_inputs, &ni) || mul_overflows(ni, 96 * 4, &b) || mul_overflows(n, 4096, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
-    if (!all_below<PF>(a_xy, 2 * n) || !all_below<PF>(b_xy, 2 * E::BDEG * n) || !all_below<PF>(c_xy, 2 * n)) {
-        g_err = "a proof coordinate is not below the modulus";
-        return GH_E_BAD_ARG;
-    }
-    if (n_inputs && !all_below<typename EngineHost<E>::PS>(inputs, ni)) { g_err = "a public input is not below the modulus"; return GH_E_BAD_ARG; }
+    if (int rc = check_proof_args<E>(h->n_query, "query", false, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status)) return rc;
     if (n == 0) return GH_OK;
     if (int rc = gh_rt::ensure_init()) return rc;
     return run_gm17_verify<E>(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);

@@ -28,6 +28,25 @@ int checked_handle(gh_gm17_vk* h) {
     return GH_OK;
 }
 
+// what the verify entry points begin with: the lock, the Trim, the handle check and the PairingOps of the key's engine, which
+// `last` records for the scheme's last_timing; then call(ops)
+template <class H, class F> int with_key(H* h, int& last, F call) {
+    std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
+    Trim trim_;
+    if (int rc = checked_handle(h)) return rc;
+    const gh_rt::PairingOps* ops = ops_of_engine(h->engine);
+    if (!ops) return GH_E_BAD_HANDLE;
+    last = h->engine;
+    return call(ops);
+}
+template <class H> int vk_free(H* h) {
+    std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
+    if (!h) return GH_OK;
+    if (int rc = checked_handle(h)) return rc;
+    delete h;
+    return GH_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------- C ABI
@@ -56,22 +75,14 @@ int gh_groth16_vk_create(int engine, const uint64_t* alpha_g1_beta_g2, const uin
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_groth16_vk_free(gh_groth16_vk_t h) try {
-    std::lock_guard<std::mutex> lk(api_mutex());
-    if (!h) return GH_OK;
-    if (int rc = checked_handle(h)) return rc;
-    delete h;
-    return GH_OK;
+    return vk_free(h);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_groth16_verify(gh_groth16_vk_t h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf,
                       const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) try {
-    std::lock_guard<std::mutex> lk(api_mutex());
-    Trim trim_;
-    if (int rc = checked_handle(h)) return rc;
-    const PairingOps* ops = ops_of_engine(h->engine);
-    if (!ops) return GH_E_BAD_HANDLE;
-    g_last_engine = h->engine;
-    return ops->verify(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);
+    return with_key(h, g_last_engine, [&](const PairingOps* ops) {
+        return ops->verify(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);
+    });
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_pairing_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
@@ -83,25 +94,17 @@ int gh_pairing_last_timing(float* phase_ms, int max_phases, float* total_ms) try
 int gh_groth16_verify_checked(gh_groth16_vk_t h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf,
                               const uint64_t* c_xy, const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status,
                               uint8_t* out_point_status) try {
-    std::lock_guard<std::mutex> lk(api_mutex());
-    Trim trim_;
-    if (int rc = checked_handle(h)) return rc;
-    const PairingOps* ops = ops_of_engine(h->engine);
-    if (!ops) return GH_E_BAD_HANDLE;
-    g_last_engine = h->engine;
-    return ops->verify_validated(h, 0, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status, out_point_status);
+    return with_key(h, g_last_engine, [&](const PairingOps* ops) {
+        return ops->verify_validated(h, 0, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status, out_point_status);
+    });
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_groth16_verify_compressed(gh_groth16_vk_t h, const uint64_t* a_x, const uint8_t* a_flags, const uint64_t* b_x, const uint8_t* b_flags,
                                  const uint64_t* c_x, const uint8_t* c_flags, const uint64_t* inputs, size_t n, size_t n_inputs,
                                  uint8_t* out_status, uint8_t* out_point_status) try {
-    std::lock_guard<std::mutex> lk(api_mutex());
-    Trim trim_;
-    if (int rc = checked_handle(h)) return rc;
-    const PairingOps* ops = ops_of_engine(h->engine);
-    if (!ops) return GH_E_BAD_HANDLE;
-    g_last_engine = h->engine;
-    return ops->verify_validated(h, 1, a_x, a_flags, b_x, b_flags, c_x, c_flags, inputs, n, n_inputs, out_status, out_point_status);
+    return with_key(h, g_last_engine, [&](const PairingOps* ops) {
+        return ops->verify_validated(h, 1, a_x, a_flags, b_x, b_flags, c_x, c_flags, inputs, n, n_inputs, out_status, out_point_status);
+    });
 } catch (...) { return gh_rt::api_exception(); }
 
 // ---- include/ginger_hip_gm17.h
@@ -116,22 +119,14 @@ int gh_gm17_vk_create(int engine, const uint64_t* g_alpha_g1_xy, const uint64_t*
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_gm17_vk_free(gh_gm17_vk_t h) try {
-    std::lock_guard<std::mutex> lk(api_mutex());
-    if (!h) return GH_OK;
-    if (int rc = checked_handle(h)) return rc;
-    delete h;
-    return GH_OK;
+    return vk_free(h);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_gm17_verify(gh_gm17_vk_t h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
                    const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) try {
-    std::lock_guard<std::mutex> lk(api_mutex());
-    Trim trim_;
-    if (int rc = checked_handle(h)) return rc;
-    const PairingOps* ops = ops_of_engine(h->engine);
-    if (!ops) return GH_E_BAD_HANDLE;
-    g_last_gm17_engine = h->engine;
-    return ops->gm17_verify(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);
+    return with_key(h, g_last_gm17_engine, [&](const PairingOps* ops) {
+        return ops->gm17_verify(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);
+    });
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_gm17_last_timing(float* phase_ms, int max_phases, float* total_ms) try {

@@ -131,20 +131,30 @@ struct PairIn {
     const uint32_t* g2[MAX_PAIRS];                 // the variable pairs only
     const uint8_t* g2_inf[MAX_PAIRS];
     size_t g2_stride[MAX_PAIRS], g2_inf_stride[MAX_PAIRS];
+    // pair j takes its G1 / G2 point of row i from xy + i * stride (u32 words; 0: one point for every row) and the point's
+    // infinity byte from inf[i * inf_stride]
+    void g1_rows(int j, const void* xy, const uint8_t* inf, size_t stride = 48, size_t inf_stride = 1) {
+        g1[j] = (const uint32_t*)xy;
+        g1_inf[j] = inf;
+        g1_stride[j] = stride;
+        g1_inf_stride[j] = inf_stride;
+    }
+    void g2_rows(int j, const void* xy, const uint8_t* inf, size_t stride, size_t inf_stride = 1) {
+        g2[j] = (const uint32_t*)xy;
+        g2_inf[j] = inf;
+        g2_stride[j] = stride;
+        g2_inf_stride[j] = inf_stride;
+    }
 };
 
-// a tower coordinate in D consecutive slots
-template <class T> __device__ __forceinline__ T ld_t(const RowSlab& s, int slot);
-template <> __device__ __forceinline__ Fp2T ld_t<Fp2T>(const RowSlab& s, int slot) { return Fp2T{s.ld(slot), s.ld(slot + 1)}; }
-template <> __device__ __forceinline__ Fp3T ld_t<Fp3T>(const RowSlab& s, int slot) { return Fp3T{s.ld(slot), s.ld(slot + 1), s.ld(slot + 2)}; }
-__device__ __forceinline__ void st_t(const RowSlab& s, int slot, const Fp2T& v) {
-    s.st(slot, v.c0);
-    s.st(slot + 1, v.c1);
+// a tower coordinate in B::DEG consecutive slots
+template <class B> __device__ __forceinline__ typename B::T ld_t(const RowSlab& s, int slot) {
+    if constexpr (B::DEG == 2) return typename B::T{s.ld(slot), s.ld(slot + 1)};
+    else return typename B::T{s.ld(slot), s.ld(slot + 1), s.ld(slot + 2)};
 }
-__device__ __forceinline__ void st_t(const RowSlab& s, int slot, const Fp3T& v) {
-    s.st(slot, v.c0);
-    s.st(slot + 1, v.c1);
-    s.st(slot + 2, v.c2);
+template <class B> __device__ __forceinline__ void st_t(const RowSlab& s, int slot, const typename B::T& v) {
+#pragma unroll
+    for (int i = 0; i < B::DEG; i++) s.st(slot + i, B::comp(v, i));
 }
 
 template <class E, int KV, int KP>
@@ -173,12 +183,12 @@ pair_setup_kernel(PairIn in, const uint8_t* __restrict__ status, size_t row0, si
         if (j < KV) {
             const uint32_t* q = in.g2[j] + i * in.g2_stride[j];
             const typename B::T qx = B::from_abi(q), qy = B::from_abi(q + tower_words<E>() / 2);
-            st_t(s, VS * j, qx);
-            st_t(s, VS * j + D, qy);
-            st_t(s, VS * j + 2 * D, B::one());
-            st_t(s, VS * j + 3 * D, B::one());
-            st_t(s, VS * j + 4 * D, qx);
-            st_t(s, VS * j + 5 * D, qy);
+            st_t<B>(s, VS * j, qx);
+            st_t<B>(s, VS * j + D, qy);
+            st_t<B>(s, VS * j + 2 * D, B::one());
+            st_t<B>(s, VS * j + 3 * D, B::one());
+            st_t<B>(s, VS * j + 4 * D, qx);
+            st_t<B>(s, VS * j + 5 * D, qy);
         }
     }
 }
@@ -205,20 +215,20 @@ miller_kernel(uint32_t* __restrict__ slab, const uint8_t* __restrict__ skip, con
         for (int j = 0; j < KV; j++) {
             if (sk[j]) continue;
             const int b = VS * j;
-            typename E::G2Run R{ld_t<BT>(s, b), ld_t<BT>(s, b + D), ld_t<BT>(s, b + 2 * D), ld_t<BT>(s, b + 3 * D)};
+            typename E::G2Run R{ld_t<B>(s, b), ld_t<B>(s, b + D), ld_t<B>(s, b + 2 * D), ld_t<B>(s, b + 3 * D)};
             const typename E::G1Pre P{s.ld(b + 6 * D), s.ld(b + 6 * D + 1)};
             GT l;
             if (add == 0) {
                 l = dbl_step_call<E>(R, P);
             } else {
-                BT qy = ld_t<BT>(s, b + 5 * D);
+                BT qy = ld_t<B>(s, b + 5 * D);
                 if (add < 0) qy = B::neg(qy);
-                l = add_step_call<E>(R, ld_t<BT>(s, b + 4 * D), qy, P);
+                l = add_step_call<E>(R, ld_t<B>(s, b + 4 * D), qy, P);
             }
-            st_t(s, b, R.x);
-            st_t(s, b + D, R.y);
-            st_t(s, b + 2 * D, R.z);
-            st_t(s, b + 3 * D, R.t);
+            st_t<B>(s, b, R.x);
+            st_t<B>(s, b + D, R.y);
+            st_t<B>(s, b + 2 * D, R.z);
+            st_t<B>(s, b + 3 * D, R.t);
             f = gt_mul_call<E>(f, l);
         }
 #pragma unroll
@@ -378,14 +388,8 @@ int run_product(const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2
         return rc;
     PairIn in{};
     for (size_t j = 0; j < k; j++) {
-        in.g1[j] = (const uint32_t*)d_g1 + 48 * j;
-        in.g1_inf[j] = d_i1 + j;
-        in.g1_stride[j] = 48 * k;
-        in.g1_inf_stride[j] = k;
-        in.g2[j] = (const uint32_t*)d_g2 + 2 * TW * j;
-        in.g2_inf[j] = d_i2 + j;
-        in.g2_stride[j] = 2 * TW * k;
-        in.g2_inf_stride[j] = k;
+        in.g1_rows(j, d_g1 + 24 * j, d_i1 + j, 48 * k, k);
+        in.g2_rows(j, d_g2 + TW * j, d_i2 + j, 2 * TW * k, k);
     }
     switch (k) {
         case 1: rc = launch_pairs<E, 1, 0>(in, nullptr, nullptr, n, d_val, &ph); break;
@@ -502,6 +506,18 @@ template <class E> int verify_bufs(size_t n, size_t n_inputs, VerifyBufs& v) {
     return rc;
 }
 
+// A, B, C and their infinity bytes from the host into v
+template <class E>
+int upload_proofs(const VerifyBufs& v, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+                  const uint8_t* c_inf, size_t n) {
+    constexpr size_t TW = tower_words<E>() / 2;
+    int rc;
+    if ((rc = up(v.d_a, a_xy, n * 24)) || (rc = up(v.d_b, b_xy, n * TW)) || (rc = up(v.d_c, c_xy, n * 24)) || (rc = up(v.d_ai, a_inf, n)) ||
+        (rc = up(v.d_bi, b_inf, n)))
+        return rc;
+    return up(v.d_ci, c_inf, n);
+}
+
 // the device part of a verification, over proof points and inputs that are on the device: the curve check, g_ic, the Miller
 // loops, the final exponentiation and the compare, with the marks of those phases; v.d_st holds the rows' status.  d_pst
 // (nullable): 3 point codes per row, a row with a non-zero one gets status 3 and is not evaluated.
@@ -514,18 +530,10 @@ template <class E> int verify_device(gh_groth16_vk* h, const VerifyBufs& v, cons
     if (d_pst) GH_LAUNCH(point_status_kernel, dim3(blocks(n, 256)), dim3(256), 0, g.stream, d_pst, n, v.d_st);
     if ((rc = launch_g_ic<E>(h->d_abc.as<const uint32_t>(), h->tables, v.d_in, n, n_inputs, v.d_gic, v.d_gi)) || (rc = ph.mark())) return rc;
     PairIn in{};
-    const uint64_t* g1s[3] = {v.d_a, v.d_gic, v.d_c};
-    const uint8_t* infs[3] = {v.d_ai, v.d_gi, v.d_ci};
-    for (int j = 0; j < 3; j++) {
-        in.g1[j] = (const uint32_t*)g1s[j];
-        in.g1_inf[j] = infs[j];
-        in.g1_stride[j] = 48;
-        in.g1_inf_stride[j] = 1;
-    }
-    in.g2[0] = (const uint32_t*)v.d_b;
-    in.g2_inf[0] = v.d_bi;
-    in.g2_stride[0] = 2 * TW;
-    in.g2_inf_stride[0] = 1;
+    in.g1_rows(0, v.d_a, v.d_ai);
+    in.g2_rows(0, v.d_b, v.d_bi, 2 * TW);
+    in.g1_rows(1, v.d_gic, v.d_gi);
+    in.g1_rows(2, v.d_c, v.d_ci);
     if ((rc = launch_pairs<E, 1, 2>(in, v.d_st, h->d_tab.as<const typename E::Coeff>(), n, v.d_val, &ph))) return rc;
     GH_LAUNCH((gt_compare_kernel<(int)TW>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const uint64_t*)v.d_val, h->d_gt.as<const uint64_t>(), n, v.d_st);
     HIPCHK(hipGetLastError());
@@ -535,15 +543,14 @@ template <class E> int verify_device(gh_groth16_vk* h, const VerifyBufs& v, cons
 template <class E>
 int run_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
                const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
-    constexpr size_t TW = tower_words<E>() / 2;
     if (int rc = vk_ensure<E>(h)) return rc;
     VerifyBufs v;
     int rc = verify_bufs<E>(n, n_inputs, v);
     if (rc) return rc;
     Phases ph{g_tm};
     if ((rc = ph.mark())) return rc;
-    if ((rc = up(v.d_a, a_xy, n * 24)) || (rc = up(v.d_b, b_xy, n * TW)) || (rc = up(v.d_c, c_xy, n * 24)) || (rc = up(v.d_ai, a_inf, n)) ||
-        (rc = up(v.d_bi, b_inf, n)) || (rc = up(v.d_ci, c_inf, n)) || (n_inputs && (rc = up(v.d_in, inputs, n * n_inputs * 12))) || (rc = ph.mark()))
+    if ((rc = upload_proofs<E>(v, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, n)) || (n_inputs && (rc = up(v.d_in, inputs, n * n_inputs * 12))) ||
+        (rc = ph.mark()))
         return rc;
     if ((rc = verify_device<E>(h, v, nullptr, n, n_inputs, ph))) return rc;
     HIPCHK(hipMemcpyAsync(out_status, v.d_st, n, hipMemcpyDeviceToHost, g.stream));
@@ -588,8 +595,7 @@ int run_verify_validated(gh_groth16_vk* h, int compressed, const uint64_t* a, co
             (rc = gh_rt::points_decompress_dev(G1, d_cx, d_cf, n, v.d_c, v.d_ci, d_pst + 2, 3)))
             return rc;
     } else {
-        if ((rc = up(v.d_a, a, n * 24)) || (rc = up(v.d_b, b, n * TW)) || (rc = up(v.d_c, c, n * 24)) || (rc = up(v.d_ai, a_fl, n)) ||
-            (rc = up(v.d_bi, b_fl, n)) || (rc = up(v.d_ci, c_fl, n)) || (rc = gh_rt::points_validate_mark(0)) ||
+        if ((rc = upload_proofs<E>(v, a, a_fl, b, b_fl, c, c_fl, n)) || (rc = gh_rt::points_validate_mark(0)) ||
             (rc = gh_rt::points_member_dev(G1, v.d_a, v.d_ai, n, d_pst, 3)) || (rc = gh_rt::points_member_dev(G2, v.d_b, v.d_bi, n, d_pst + 1, 3)) ||
             (rc = gh_rt::points_member_dev(G1, v.d_c, v.d_ci, n, d_pst + 2, 3)))
             return rc;
@@ -666,22 +672,33 @@ int api_vk_create(int engine, const uint64_t* alpha_g1_beta_g2, const uint64_t* 
     return GH_OK;
 }
 
+// the argument checks the verify entry points share.  n_points: the points of the key that take the public inputs (one more
+// than the inputs), what: that array's name.  compressed: a, b, c hold untrusted x coordinates, and what is wrong with them
+// is a row's status, not an argument error.
 template <class E>
-int api_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
-               const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
+int check_proof_args(size_t n_points, const char* what, bool compressed, const uint64_t* a, const uint8_t* a_inf, const uint64_t* b,
+                     const uint8_t* b_inf, const uint64_t* c, const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs,
+                     const uint8_t* out_status) {
     typedef typename E::PF PF;
-    if (n_inputs + 1 != h->n_abc) { g_err = "the number of public inputs does not match gamma_abc_g1 (MalformedVerifyingKey)"; return GH_E_BAD_ARG; }
-    if (n && (!a_xy || !a_inf || !b_xy || !b_inf || !c_xy || !c_inf || (n_inputs && !inputs) || !out_status)) {
-        g_err = "null argument";
+    if (n_inputs + 1 != n_points) {
+        g_err = std::string("the number of public inputs does not match ") + what + " (MalformedVerifyingKey)";
         return GH_E_BAD_ARG;
     }
-    size_t ni = 0, b = 0;
-    if (mul_overflows(n, n_inputs, &ni) || mul_overflows(ni, 96 * 4, &b) || mul_overflows(n, 4096, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
-    if (!all_below<PF>(a_xy, 2 * n) || !all_below<PF>(b_xy, 2 * E::BDEG * n) || !all_below<PF>(c_xy, 2 * n)) {
+    if (n && (!a || !a_inf || !b || !b_inf || !c || !c_inf || (n_inputs && !inputs) || !out_status)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    size_t ni = 0, by = 0;
+    if (mul_overflows(n, n_inputs, &ni) || mul_overflows(ni, 96 * 4, &by) || mul_overflows(n, 4096, &by)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (!compressed && (!all_below<PF>(a, 2 * n) || !all_below<PF>(b, 2 * E::BDEG * n) || !all_below<PF>(c, 2 * n))) {
         g_err = "a proof coordinate is not below the modulus";
         return GH_E_BAD_ARG;
     }
     if (n_inputs && !all_below<typename EngineHost<E>::PS>(inputs, ni)) { g_err = "a public input is not below the modulus"; return GH_E_BAD_ARG; }
+    return GH_OK;
+}
+
+template <class E>
+int api_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, const uint64_t* b_xy, const uint8_t* b_inf, const uint64_t* c_xy,
+               const uint8_t* c_inf, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status) {
+    if (int rc = check_proof_args<E>(h->n_abc, "gamma_abc_g1", false, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status)) return rc;
     if (n == 0) return GH_OK;
     if (int rc = gh_rt::ensure_init()) return rc;
     return run_verify<E>(h, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, inputs, n, n_inputs, out_status);
@@ -691,17 +708,7 @@ template <class E>
 int api_verify_validated(gh_groth16_vk* h, int compressed, const uint64_t* a, const uint8_t* a_fl, const uint64_t* b, const uint8_t* b_fl,
                          const uint64_t* c, const uint8_t* c_fl, const uint64_t* inputs, size_t n, size_t n_inputs, uint8_t* out_status,
                          uint8_t* out_point_status) {
-    typedef typename E::PF PF;
-    if (n_inputs + 1 != h->n_abc) { g_err = "the number of public inputs does not match gamma_abc_g1 (MalformedVerifyingKey)"; return GH_E_BAD_ARG; }
-    if (n && (!a || !a_fl || !b || !b_fl || !c || !c_fl || (n_inputs && !inputs) || !out_status)) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    size_t ni = 0, by = 0;
-    if (mul_overflows(n, n_inputs, &ni) || mul_overflows(ni, 96 * 4, &by) || mul_overflows(n, 4096, &by)) { g_err = "input too large"; return GH_E_BAD_ARG; }
-    // compressed coordinates are untrusted data: what is wrong with them is a row's status, not an argument error
-    if (!compressed && (!all_below<PF>(a, 2 * n) || !all_below<PF>(b, 2 * E::BDEG * n) || !all_below<PF>(c, 2 * n))) {
-        g_err = "a proof coordinate is not below the modulus";
-        return GH_E_BAD_ARG;
-    }
-    if (n_inputs && !all_below<typename EngineHost<E>::PS>(inputs, ni)) { g_err = "a public input is not below the modulus"; return GH_E_BAD_ARG; }
+    if (int rc = check_proof_args<E>(h->n_abc, "gamma_abc_g1", compressed != 0, a, a_fl, b, b_fl, c, c_fl, inputs, n, n_inputs, out_status)) return rc;
     if (n == 0) return GH_OK;
     if (int rc = gh_rt::ensure_init()) return rc;
     return run_verify_validated<E>(h, compressed, a, a_fl, b, b_fl, c, c_fl, inputs, n, n_inputs, out_status, out_point_status);

@@ -108,10 +108,28 @@ def _wire_rows(data, rec, coeffs, engine="mnt4753"):
     return limbs.mont_rows(vals, fq).reshape(n, 12 * coeffs), inf
 
 
-class PreparedVerifyingKey(_handles.Handle):
+class _ProofKey(_handles.Handle):
+    """what the Groth16 key and the GM17 key (gm17_verify.py) share; a subclass names its entry point in _verify"""
+
+    def verify(self, a, b, c, inputs):
+        """a, c: G1 batches, b: a G2 batch, inputs: (n, num_inputs, 12) Montgomery rows of Fr -> status (n,) uint8"""
+        axy, ainf = _points(a, 24)
+        bxy, binf = _points(b, _WIDTHS[self.engine].g2_words)
+        cxy, cinf = _points(c, 24)
+        n = axy.shape[0]
+        x = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(n, -1) if n else np.zeros((0, 12 * self.num_inputs), dtype=np.uint64)
+        if bxy.shape[0] != n or cxy.shape[0] != n or x.shape[1] % 12:
+            raise ValueError("one A, B, C and one row of inputs per proof")
+        st = np.zeros(n, dtype=np.uint8)
+        _check(getattr(self._lib(), self._verify)(self.handle, _ptr(axy), _ptr(ainf), _ptr(bxy), _ptr(binf), _ptr(cxy), _ptr(cinf),
+                                                  _ptr(x) if x.size else None, n, x.shape[1] // 12, _ptr(st)))
+        return st
+
+
+class PreparedVerifyingKey(_ProofKey):
     """prepare_verifying_key (verifier.rs:9-16): keeps alpha_g1_beta_g2, -gamma_g2, -delta_g2 (as line tables, built on the
     device on first use) and gamma_abc_g1 (as fixed-base tables)"""
-    _lib, _prefix = staticmethod(_lib), "gh_groth16_vk"
+    _lib, _prefix, _verify = staticmethod(_lib), "gh_groth16_vk", "gh_groth16_verify"
 
     def __init__(self, alpha_g1_beta_g2, gamma_g2, delta_g2, gamma_abc_g1, engine="mnt4753"):
         w = _WIDTHS[engine]
@@ -141,20 +159,6 @@ class PreparedVerifyingKey(_handles.Handle):
         if gi.any() or di.any() or ai.any():
             raise ValueError("a point of the verifying key is the point at infinity")
         return cls(gt.reshape(1, w.gt_words), g, d, abc, engine=pairing)
-
-    def verify(self, a, b, c, inputs):
-        """a, c: G1 batches, b: a G2 batch, inputs: (n, num_inputs, 12) Montgomery rows of Fr -> status (n,) uint8"""
-        axy, ainf = _points(a, 24)
-        bxy, binf = _points(b, _WIDTHS[self.engine].g2_words)
-        cxy, cinf = _points(c, 24)
-        n = axy.shape[0]
-        x = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(n, -1) if n else np.zeros((0, 12 * self.num_inputs), dtype=np.uint64)
-        if bxy.shape[0] != n or cxy.shape[0] != n or x.shape[1] % 12:
-            raise ValueError("one A, B, C and one row of inputs per proof")
-        st = np.zeros(n, dtype=np.uint8)
-        _check(_lib().gh_groth16_verify(self.handle, _ptr(axy), _ptr(ainf), _ptr(bxy), _ptr(binf), _ptr(cxy), _ptr(cinf),
-                                        _ptr(x) if x.size else None, n, x.shape[1] // 12, _ptr(st)))
-        return st
 
     def verify_checked(self, a, b, c, inputs):
         """verify after group_membership_test of A, B, C on the device -> (status (n,), point status (n, 3)); status 3: a

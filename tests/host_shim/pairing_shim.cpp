@@ -20,7 +20,7 @@ static void st4(uint64_t* w, const Fq4T& a) {
     fp_to_abi<P4>((uint32_t*)(w + 24), a.c1.c0);
     fp_to_abi<P4>((uint32_t*)(w + 36), a.c1.c1);
 }
-static E::G1Pre pre(const uint64_t* xy) { return E::G1Pre{ld(xy), E::mul13(ld(xy + 12))}; }
+static E::G1Pre pre(const uint64_t* xy) { return E::g1_pre(ld(xy), ld(xy + 12)); }
 
 // out = final_exp(prod_j miller(P_j, Q_j)), 1 <= k <= 3, the running points Jacobian (the variable-Q steps)
 extern "C" int t_pairing_product(const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy, const uint8_t* g2_inf, int k, uint64_t* out) {
@@ -34,7 +34,7 @@ extern "C" int t_pairing_product(const uint64_t* g1_xy, const uint8_t* g1_inf, c
         qy[j] = ld2(g2_xy + 48 * j + 24);
         skip[j] = g1_inf[j] || g2_inf[j];
     }
-    st4(out, E::final_exponentiation(mnt4_miller_variable(P, qx, qy, skip, k, ATE_NAF), W0_NAF));
+    st4(out, E::final_exponentiation(miller_variable<E>(P, qx, qy, skip, k, ATE_NAF), W0_NAF));
     return 0;
 }
 
@@ -47,10 +47,10 @@ extern "C" int t_pairing_prepared(const uint64_t* g1_xy, const uint64_t* g2_xy, 
     int idx = 0;
     for (int i = 0; i < E::ATE_DIGITS; i++) {
         f = E::sqr(f);
-        f = E::mul_by_023(f, P.py13, E::prepared_line(tab[idx++], P));
-        if (ATE_NAF[i] != 0) f = E::mul_by_023(f, P.py13, E::prepared_line(tab[idx++], P));
+        f = E::mul_by_line(f, E::line_c0(P), E::prepared_line(tab[idx++], P));
+        if (ATE_NAF[i] != 0) f = E::mul_by_line(f, E::line_c0(P), E::prepared_line(tab[idx++], P));
     }
-    st4(out, E::final_exponentiation(E::unitary_inverse(f), W0_NAF));
+    st4(out, E::final_exponentiation(E::miller_end(f), W0_NAF));
     return idx == E::TABLE_STEPS ? 0 : -1;
 }
 

@@ -2,7 +2,8 @@
 """MNT4-753 (or, with --engine mnt6753, MNT6-753) pairings and Groth16 verification on the device: pairings/s (gh_pairing_product, k = 1) and verifications/s
 (gh_groth16_verify, two public inputs) at 2^16 and 2^20 rows, warmed, best of 3, timed around the call (which synchronises
 the device before it returns), the phase split of every call, and the Miller and final-exponentiation kernels' products per
-row (counted from the formulas as written in csrc/pairing29.h and pairing29_mnt6.h, squarings as products) over their kernel time as a fraction of
+row (counted from the formulas as written in the PairingTower of csrc/pairing29.h and the sparse products of its two engines, squarings as products)
+over their kernel time as a fraction of
 the product peak gh_measure_fpmul_peak measures in the same run.
 
 The rows are valid proofs of a key made from random scalars, so that (A, B, C) is known in the exponent:
@@ -32,7 +33,7 @@ from schnorr_bench import INV, MADD, ADD   # noqa: E402
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 DISTINCT = 4096
 N_INPUTS = 2
-# products of the steps of csrc/pairing29.h and csrc/pairing29_mnt6.h (their headers count them)
+# products of the steps of csrc/pairing29.h (its header counts them for both engines, MNT4-753 / MNT6-753)
 FQ4_MUL, FQ4_SQR, MUL_023, CYC_SQR = 9, 6, 8, 4
 DBL_STEP, ADD_STEP, PREPARED_LINE = 25 + 4, 28 + 8, 2
 FQ3_MUL, FQ3_SQR = 6, 5
