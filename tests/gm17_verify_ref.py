@@ -1,18 +1,10 @@
 """What the GM17 verification tests share (tests/test_gm17_verify_host.py, tests/test_gpu_gm17_verify.py): a literal restatement
-of proof-systems/src/gm17/verifier.rs:24-76 over a pairing restatement module `pr` (pairing_ref for MNT4-753, pairing6_ref for
-MNT6-753), a verifying key known in the exponent with its closed-form verdicts, and the edge rows every layer is checked on.
-Points are pyref's (None for infinity).  Test infrastructure."""
+of proof-systems/src/gm17/verifier.rs:24-76 over an engine object `pr` of the pairing restatement (pairing_ref.engine("mnt4753")
+or ("mnt6753")), a verifying key known in the exponent with its closed-form verdicts, and the edge rows every layer is checked
+on.  Points are pyref's (None for infinity).  Test infrastructure."""
 import random
 
 import numpy as np
-
-import pyref
-
-ENGINE_OF = {"pairing_ref": "mnt4753", "pairing6_ref": "mnt6753"}
-
-
-def engine_of(pr):
-    return ENGINE_OF[pr.__name__]
 
 
 def on_curves(pr, proof):
@@ -139,24 +131,16 @@ def edge_rows(key):
 
 
 # ---- the package's layouts
-def input_rows(pr, inputs):
-    """lists of integers -> (n, n_inputs, 12) Montgomery rows of the engine's Fr"""
-    F = pyref.P4 if engine_of(pr) == "mnt6753" else pyref.P6
-    assert F.p == pr.r
-    n = len(inputs)
-    return np.array([[pyref.int_to_limbs(F.to_mont(v % pr.r)) for v in row] for row in inputs], dtype=np.uint64).reshape(n, -1, 12)
-
-
 def pvk_of(gm17_verify_mod, key):
     """the package's PreparedVerifyingKey of an ExpKey (or of any vk dict of points)"""
     pr = key.pr
     vk = key.vk
     return gm17_verify_mod.PreparedVerifyingKey(pr.g1_row(vk["g_alpha_g1"]), pr.g2_row(vk["h_beta_g2"]), pr.g1_row(vk["g_gamma_g1"]),
                                                 pr.g2_row(vk["h_gamma_g2"]), pr.g2_row(vk["h_g2"]),
-                                                np.stack([pr.g1_row(P) for P in vk["query"]]), engine=engine_of(pr))
+                                                np.stack([pr.g1_row(P) for P in vk["query"]]), engine=pr.name)
 
 
 def device_statuses(pr, pvk, rows):
     a, b, c = ([row[j] for row in rows] for j in range(3))
-    st = pvk.verify(pr.g1_batch(a), pr.g2_batch(b), pr.g1_batch(c), input_rows(pr, [row[3] for row in rows]))
+    st = pvk.verify(pr.g1_batch(a), pr.g2_batch(b), pr.g1_batch(c), pr.input_rows([row[3] for row in rows]))
     return [int(v) for v in st]

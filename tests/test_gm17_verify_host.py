@@ -3,7 +3,6 @@ of a key known in the exponent, the GH_HD group additions of ginger-lib_amd/csrc
 (tests/host_shim/gm17_shim.cpp) against pyref's curve add and, composed with the shim's Miller loop and final exponentiation,
 against the closed form, and the argument checks of include/ginger_hip_gm17.h.  Every comparison is exact."""
 import ctypes
-import importlib
 import os
 import random
 import re
@@ -14,19 +13,18 @@ import numpy as np
 import pytest
 
 import gm17_verify_ref as R
+import pairing_ref
 import pyref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "build", "libgm17_shim.so")
 GH_E_BAD_ARG, GH_E_NO_DEVICE = -1, -3
 V = ctypes.c_void_p
-ENGINE_ID = {"mnt4753": 0, "mnt6753": 2}
-REFS = ["pairing_ref", "pairing6_ref"]
 
 
-@pytest.fixture(scope="module", params=REFS)
+@pytest.fixture(scope="module", params=pairing_ref.ENGINES)
 def pr(request):
-    return importlib.import_module(request.param)
+    return pairing_ref.engine(request.param)
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +59,7 @@ def test_restatement_equals_the_closed_form(pr, edge):
 
 # ---- 2. the device's group additions on the host
 def _shim_sum(shim, pr, g2, P, Q):
-    eng = ENGINE_ID[R.engine_of(pr)]
+    eng = pr.id
     row = pr.g2_row if g2 else pr.g1_row
     p, q = np.ascontiguousarray(row(P)), np.ascontiguousarray(row(Q))
     out, inf = np.zeros_like(p), np.zeros(1, dtype=np.uint8)
@@ -92,7 +90,7 @@ def test_shim_verdict_equals_the_closed_form(shim, pr, edge):
     """one row's verdict composed on the host: the shim's sums, Miller loop and final exponentiation"""
     key = edge["key"]
     vk, C1 = key.vk, pr.C1
-    eng = ENGINE_ID[R.engine_of(pr)]
+    eng = pr.id
     keep = [np.ascontiguousarray(a) for a in (pr.g1_row(vk["g_alpha_g1"]), pr.g2_row(vk["h_beta_g2"]), pr.g1_row(vk["g_gamma_g1"]),
                                               pr.g2_row(vk["h_gamma_g2"]), pr.g2_row(vk["h_g2"]))]
     got, bits = [], []
@@ -157,7 +155,7 @@ def test_rust_gm17_extern_block_is_generated_from_the_header():
 def test_vk_create_checks_arguments(gl, pr):
     from ginger_lib_amd import gm17_verify
     lib = gm17_verify._lib()
-    eng = ENGINE_ID[R.engine_of(pr)]
+    eng = pr.id
     arrs = _vk_arrays(pr)
     ptr = lambda a: a.ctypes.data_as(V)
     h = V()
@@ -193,9 +191,9 @@ def test_vk_create_checks_arguments(gl, pr):
     with pytest.raises(gm17_verify.GingerHipError):
         bad = [a.copy() for a in arrs]
         bad[3].reshape(-1)[:12] = pr.limbs(1234)
-        gm17_verify.PreparedVerifyingKey(*bad, engine=R.engine_of(pr))
+        gm17_verify.PreparedVerifyingKey(*bad, engine=pr.name)
     with pytest.raises(ValueError):                                                             # two g_alpha rows
-        gm17_verify.PreparedVerifyingKey(np.concatenate([arrs[0], arrs[0]]), *arrs[1:], engine=R.engine_of(pr))
+        gm17_verify.PreparedVerifyingKey(np.concatenate([arrs[0], arrs[0]]), *arrs[1:], engine=pr.name)
 
 
 def test_verify_entry_point_without_gpu(gl, pr):
@@ -203,8 +201,7 @@ def test_verify_entry_point_without_gpu(gl, pr):
     GH_E_NO_DEVICE; creating a key needs no device."""
     from ginger_lib_amd import gm17_verify
     lib = gm17_verify._lib()
-    engine = R.engine_of(pr)
-    w = 48 if engine == "mnt4753" else 72
+    engine, w = pr.name, pr.gt_words
     pvk = gm17_verify.PreparedVerifyingKey(*_vk_arrays(pr), engine=engine)
     assert pvk.num_inputs == 1 and pvk.engine == engine
     h = pvk.handle
@@ -249,8 +246,7 @@ def test_verify_entry_point_without_gpu(gl, pr):
 
 def test_verify_proofs_refuses_bad_records(gl, pr):
     from ginger_lib_amd import gm17_verify
-    engine = R.engine_of(pr)
-    g2_rec = 385 if engine == "mnt4753" else 577
+    engine, g2_rec = pr.name, 96 * pr.k + 1
     pvk = gm17_verify.PreparedVerifyingKey(*_vk_arrays(pr), engine=engine)
     try:
         rec = bytes(193 + g2_rec + 193)

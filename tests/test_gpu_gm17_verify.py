@@ -9,10 +9,10 @@ import numpy as np
 import pytest
 
 import gm17_verify_ref as R
+import pairing_ref
 import pyref
 
 pytestmark = pytest.mark.gpu
-REFS = {"mnt4753": "pairing_ref", "mnt6753": "pairing6_ref"}
 LOOP = {"mnt4753": "launch_pairs", "mnt6753": "launch_pairs_mnt6"}
 
 
@@ -21,14 +21,14 @@ def gv(gpu):
     return importlib.import_module("ginger_lib_amd.gm17_verify")
 
 
-@pytest.fixture(scope="module", params=sorted(REFS))
+@pytest.fixture(scope="module", params=pairing_ref.ENGINES)
 def engine(request):
     return request.param
 
 
 @pytest.fixture(scope="module")
 def pr(engine):
-    return importlib.import_module(REFS[engine])
+    return pairing_ref.engine(engine)
 
 
 @pytest.fixture(scope="module")

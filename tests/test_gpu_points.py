@@ -11,8 +11,10 @@ import random
 import numpy as np
 import pytest
 
+import pairing_ref
 import points_ref as pr
 import pyref
+from groth16_exp_key import ExpKey
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -249,83 +251,52 @@ def test_compress_round_trip(points, name, n):
 
 
 # ---------------------------------------------------------------------------------------------------- validated verification
-class ExpKey:
-    """A Groth16 key known in the exponent over the engine of `ref` (tests/pairing_ref.py or pairing6_ref.py):
-    gamma_abc_g1 = [x0 G1, x1 G1, x2 G1], alpha_g1_beta_g2 = e0^(alpha beta), gamma_g2 = gamma G2, delta_g2 = delta G2.  For inputs
-    s, g_ic = g G1 with g = x0 + s0 x1 + s1 x2, and (a G1, b G2, c G1) is valid iff a b = alpha beta + g gamma + c delta."""
-
-    def __init__(self, ref, seed):
-        import schnorr_ref
-        self.ref, self.C1, self.C2, self.r = ref, ref.C1, ref.C2, ref.r
-        rng = random.Random(seed)
-        r = self.r
-        self.g1 = lambda k: schnorr_ref.mul(ref.C1, k % r, ref.C1.G) if k % r else None
-        self.alpha, self.beta, self.gamma, self.delta = (rng.randrange(1, r) for _ in range(4))
-        self.x = [rng.randrange(1, r) for _ in range(3)]
-        self.ab0 = self.alpha * self.beta % r
-        self.gt = ref.fpow(ref.pairing(ref.C1.G, ref.C2.G), self.ab0)
-        self.s = [rng.randrange(1, r), rng.randrange(1, r)]
-        self.rng = rng
-
-    def proof(self):
-        a, b = self.rng.randrange(1, self.r), self.rng.randrange(1, 1 << 20)
-        g = (self.x[0] + self.s[0] * self.x[1] + self.s[1] * self.x[2]) % self.r
-        c = (a * b - self.ab0 - g * self.gamma) * pow(self.delta, -1, self.r) % self.r
-        return self.g1(a), self.C2.mul(b, self.C2.G), self.g1(c)
-
-    def pvk(self, pairing, engine):
-        ref = self.ref
-        gt_row = ref.fq4_row if engine == "mnt4753" else ref.fq6_row
-        return pairing.PreparedVerifyingKey(gt_row(self.gt), ref.g2_row(self.C2.mul(self.gamma, self.C2.G)), ref.g2_row(self.C2.mul(self.delta, self.C2.G)),
-                                            np.stack([ref.g1_row(self.g1(v)) for v in self.x]), engine=engine)
-
-    def inputs(self, n):
-        fr = pyref.P6 if self.ref.__name__ == "pairing_ref" else pyref.P4
-        assert fr.p == self.r
-        return np.array([[pyref.int_to_limbs(fr.to_mont(v)) for v in self.s]] * n, dtype=np.uint64)
-
-
 @pytest.fixture(scope="module", params=["mnt4753", "mnt6753"])
 def validated(request, gpu):
-    """per engine: the key, and rows (A, B, C, expected status, expected point status) for the checked entry point: two valid
-    proofs, C + G (a false proof of valid points), B on the twist outside the subgroup, B = T + B (the same, in another
+    """per engine: the key known in the exponent (tests/groth16_exp_key.py) with the inputs s and the proofs drawn after it,
+    and rows (A, B, C, expected status, expected point status) for the checked entry point: two valid proofs, C + G (a false proof of valid points), B on the twist outside the subgroup, B = T + B (the same, in another
     position), A off its curve, C off its curve, A at infinity"""
     engine = request.param
-    ref = importlib.import_module("pairing_ref" if engine == "mnt4753" else "pairing6_ref")
+    ref = pairing_ref.engine(engine)
     pairing = importlib.import_module("ginger_lib_amd.pairing")
     K = ExpKey(ref, 1500 + len(engine))
-    C1, C2 = K.C1, K.C2
-    A, B, C = K.proof()
-    A2, B2, Cc2 = K.proof()
+    C1, C2, rng = ref.C1, ref.C2, K.rng
+    s = [rng.randrange(1, ref.r), rng.randrange(1, ref.r)]
+
+    def proof():
+        a, b = rng.randrange(1, ref.r), rng.randrange(1, 1 << 20)
+        return K.g1(a), C2.mul(b, C2.G), K.g1(K.c_of(a, b, s))
+    A, B, C = proof()
+    A2, B2, Cc2 = proof()
     T = outside_point(C2)
     off = (A[0], C1.E.add(A[1], C1.E.one()))
     assert not C1.on_curve(off) and C2.on_curve(T)
     rows = [(A, B, C, 1, [0, 0, 0]), (A2, B2, Cc2, 1, [0, 0, 0]), (A, B, C1.add(C, C1.G), 0, [0, 0, 0]),
             (A, T, C, 3, [0, pr.NOT_PRIME_ORDER, 0]), (A2, C2.add(T, B2), Cc2, 3, [0, pr.NOT_PRIME_ORDER, 0]),
             (off, B, C, 3, [pr.NOT_ON_CURVE, 0, 0]), (A, T, off, 3, [0, pr.NOT_PRIME_ORDER, pr.NOT_ON_CURVE]), (None, B, C, 0, [0, 0, 0])]
-    pvk = K.pvk(pairing, engine)
-    yield {"engine": engine, "key": K, "rows": rows, "pvk": pvk, "pairing": pairing}
+    pvk = K.pvk(pairing)
+    yield {"engine": engine, "ref": ref, "inputs": lambda n: ref.input_rows([s] * n), "rows": rows, "pvk": pvk, "pairing": pairing}
     pvk.close()
 
 
-def _abc(K, rows):
-    return batch(K.C1, [r[0] for r in rows]), batch(K.C2, [r[1] for r in rows]), batch(K.C1, [r[2] for r in rows])
+def _abc(ref, rows):
+    return batch(ref.C1, [r[0] for r in rows]), batch(ref.C2, [r[1] for r in rows]), batch(ref.C1, [r[2] for r in rows])
 
 
 @pytest.mark.parametrize("n", [8, 130])
 def test_verify_checked(points, validated, n):
-    K, pvk, pairing = validated["key"], validated["pvk"], validated["pairing"]
+    ref, inputs, pvk, pairing = validated["ref"], validated["inputs"], validated["pvk"], validated["pairing"]
     order = list(range(8)) if n == 8 else spread(validated["rows"], n, 1300)
     rows = [validated["rows"][i] for i in order]
-    a, b, c = _abc(K, rows)
-    st, pst = pvk.verify_checked(a, b, c, K.inputs(n))
+    a, b, c = _abc(ref, rows)
+    st, pst = pvk.verify_checked(a, b, c, inputs(n))
     assert [int(v) for v in st] == [r[3] for r in rows]
     assert pst.tolist() == [r[4] for r in rows]
     tm, _ = points.last_timing()
     ptm, _ = pairing.last_timing()
     assert tm["validate"] > 0 and tm["upload"] == 0 and all(ptm[ph] > 0 for ph in ("g_ic", "miller", "final_exp"))
     # gh_groth16_verify on the rows of valid points returns what it returned before; on the rows it cannot judge, anything but a fault
-    plain = [int(v) for v in pvk.verify(a, b, c, K.inputs(n))]
+    plain = [int(v) for v in pvk.verify(a, b, c, inputs(n))]
     for k, r in enumerate(rows):
         if r[3] != 3:
             assert plain[k] == r[3], k
@@ -338,13 +309,13 @@ def test_verify_checked(points, validated, n):
 @pytest.mark.parametrize("n", [8, 130])
 def test_verify_compressed(points, validated, n):
     """the same proofs in the wire form, compressed by the device; then rows that do not decompress"""
-    K, pvk = validated["key"], validated["pvk"]
-    C1 = K.C1
+    ref, inputs, pvk = validated["ref"], validated["inputs"], validated["pvk"]
+    C1 = ref.C1
     g1, g2 = "%s_g1" % validated["engine"], "%s_g2" % validated["engine"]
     good = [r for r in validated["rows"] if pr.NOT_ON_CURVE not in r[4]]         # an off-curve point has no compressed form
     order = list(range(len(good))) if n == 8 else spread(good, n - 2, 1400)
     rows = [good[i] for i in order]
-    a, b, c = _abc(K, rows)
+    a, b, c = _abc(ref, rows)
     ax, af = points.compress_limbs(g1, a)
     bx, bf = points.compress_limbs(g2, b)
     cx, cf = points.compress_limbs(g1, c)
@@ -359,6 +330,6 @@ def test_verify_compressed(points, validated, n):
     cx, cf = np.vstack([cx, cx[first], x_row((C1.E.p,))]), np.concatenate([cf, [cf[first]], [cf[first]]]).astype(np.uint8)
     want += [(3, [pr.NOT_ON_CURVE, 0, 0]), (3, [0, pr.INVALID_FLAGS, pr.INVALID_FIELD_ELEMENT])]
     m = len(want)
-    st, pst = pvk.verify_compressed((ax, af), (bx, bf), (cx, cf), K.inputs(m))
+    st, pst = pvk.verify_compressed((ax, af), (bx, bf), (cx, cf), inputs(m))
     assert [int(v) for v in st] == [w[0] for w in want]
     assert pst.tolist() == [w[1] for w in want]

@@ -299,10 +299,11 @@ def test_entry_points_without_gpu(gl):
     assert lib.gh_points_last_timing(buf, 3, ctypes.byref(tot)) == 3
     assert lib.gh_points_last_timing(None, 3, None) == GH_E_BAD_ARG
     # the two verifiers: the checks of gh_groth16_verify, and compressed coordinates are data, not arguments
-    C1, C2 = pairing_ref.C1, pairing_ref.C2
-    gt = pairing_ref.fq4_row(pairing_ref.ONE).reshape(1, 48)
-    gamma, delta = pairing_ref.g2_row(C2.mul(3, C2.G)).reshape(1, 48), pairing_ref.g2_row(C2.mul(5, C2.G)).reshape(1, 48)
-    abc = np.stack([pairing_ref.g1_row(C1.mul(k, C1.G)) for k in (2, 7)])
+    m4 = pairing_ref.engine("mnt4753")
+    C1, C2 = m4.C1, m4.C2
+    gt = m4.gt_row(m4.ONE).reshape(1, 48)
+    gamma, delta = m4.g2_row(C2.mul(3, C2.G)).reshape(1, 48), m4.g2_row(C2.mul(5, C2.G)).reshape(1, 48)
+    abc = np.stack([m4.g1_row(C1.mul(k, C1.G)) for k in (2, 7)])
     pvk = pairing.PreparedVerifyingKey(gt, gamma, delta, abc)
     h = pvk.handle
     for fn in (lib.gh_groth16_verify_checked, lib.gh_groth16_verify_compressed):
@@ -314,10 +315,10 @@ def test_entry_points_without_gpu(gl):
             args[hole] = None
             assert fn(h, *args[:7], 1, 1, args[7], None) == GH_E_BAD_ARG, hole
         rbad = np.zeros((1, 12), dtype=np.uint64)
-        rbad[0] = pyref.int_to_limbs(pairing_ref.r)
+        rbad[0] = pyref.int_to_limbs(m4.r)
         assert fn(h, p, pb, p, pb, p, pb, rbad.ctypes.data_as(V), 1, 1, pb, pb) == GH_E_BAD_ARG
     big = np.zeros((1, 48), dtype=np.uint64)
-    big[0, :12] = pyref.int_to_limbs(pairing_ref.p)
+    big[0, :12] = pyref.int_to_limbs(m4.p)
     pbig = big.ctypes.data_as(V)
     assert lib.gh_groth16_verify_checked(h, pbig, pb, p, pb, p, pb, p, 1, 1, pb, pb) == GH_E_BAD_ARG
     gm17_h = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(64)))                # not a Groth16 key
