@@ -41,7 +41,7 @@ namespace {
 constexpr int VB_W = 4;                               // gh_batch_mul's default window
 constexpr int BH_ENTRIES = 4;                         // {1, 2, 3, 4} g
 enum { PH_UPLOAD, PH_GROUP_HASH, PH_FIXED_BASE, PH_VARIABLE_BASE, PH_NORMALISE, PH_HASH, PH_FINISH, NPHASES };
-Timing g_tm{NPHASES};
+PhaseTimer g_tm{NPHASES};
 
 // ---------------------------------------------------------------------------------------------------- Bowe-Hopwood
 template <class C>
@@ -264,15 +264,13 @@ template <class C> int run_bh_hash(gh_bh* b, const uint8_t* input, size_t n, siz
     if (!rc) rc = dbuf("vb_xy", n * 24, &d_xy);
     if (!rc) rc = dbuf("vb_inf", n, &d_inf);
     if (rc || (rc = up(d_in, input, n * nbytes)) || (rc = bh_ensure<C>(b))) return rc;
-    HIPCHK(hipEventRecord(g.ev[0], g.stream));
-    if ((rc = bh_launch<C>(b, d_in, nbytes, nbytes, n, d_p))) return rc;
-    HIPCHK(hipEventRecord(g.ev[1], g.stream));
+    if ((rc = g_tm.begin().mark()) || (rc = bh_launch<C>(b, d_in, nbytes, nbytes, n, d_p)) || (rc = g_tm.mark())) return rc;
     if ((rc = launch_normalize<C>(d_p, nullptr, n, d_zp, d_xy, 48, 0, d_inf))) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_xy, d_xy, n * 192, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipMemcpyAsync(out_inf, d_inf, n, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
-    return g_tm.single(PH_GROUP_HASH, g.ev[0], g.ev[1]);     // the hash kernel
+    return g_tm.single(PH_GROUP_HASH);                         // the hash kernel
 }
 
 template <class C> int run_double_mul(const uint64_t* xy1, const uint8_t* inf1, const uint64_t* k1, const uint64_t* xy2, const uint8_t* inf2,
@@ -292,16 +290,16 @@ template <class C> int run_double_mul(const uint64_t* xy1, const uint8_t* inf1, 
         HIPCHK(hipMemsetAsync(d_inf, 0, 2 * n, g.stream));
         if ((inf1 && (rc = up(d_inf, inf1, n))) || (inf2 && (rc = up(d_inf + n, inf2, n)))) return rc;
     }
-    HIPCHK(hipEventRecord(g.ev[0], g.stream));
-    if ((rc = vb_joint<C>(d_xy, d_inf, 0, (const uint32_t*)d_k, d_xy + n * 24, d_inf ? d_inf + n : nullptr, 0, (const uint32_t*)(d_k + n * 12),
-                          n, d_p)))
+    if ((rc = g_tm.begin().mark()) ||
+        (rc = vb_joint<C>(d_xy, d_inf, 0, (const uint32_t*)d_k, d_xy + n * 24, d_inf ? d_inf + n : nullptr, 0, (const uint32_t*)(d_k + n * 12),
+                          n, d_p)) ||
+        (rc = g_tm.mark()))
         return rc;
-    HIPCHK(hipEventRecord(g.ev[1], g.stream));
     GH_LAUNCH((proj_to_abi_kernel<C>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const Proj<C>*)d_p, n, (uint32_t*)d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_xyz, d_out, n * 288, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
-    return g_tm.single(PH_VARIABLE_BASE, g.ev[0], g.ev[1]);  // the tables and the joint kernel
+    return g_tm.single(PH_VARIABLE_BASE);                      // the tables and the joint kernel
 }
 
 // prove: mh = BH(m); gamma = sk mh and b = r mh from ONE table of mh; a = r G on the fixed-base path; c = H(m || pk.x || a.x || b.x);
@@ -338,7 +336,7 @@ template <class C> int run_prove(gh_ecvrf* h, const uint64_t* sk, const uint64_t
     d_nonce = d_sk + n * 12;
     d_ri = d_ski + n * 24;
     Proj<C>*d_a = d_p3, *d_b = d_p3 + n, *d_g = d_p3 + 2 * n;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_sk, sk, n * 12)) || (rc = up(d_nonce, nonce, n * 12)) || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_pkinf, pk_inf, n)) ||
         (rc = up(d_msg, msg, n * len * 12)) || (rc = ph.mark()))
@@ -402,7 +400,7 @@ template <class C> int run_proof_to_hash(gh_ecvrf* h, const uint64_t* pk_xy, con
     uint32_t* d_si = d_ci + n * 24;
     d_out = d_c2 + n * 12;
     Proj<C>*d_sg = d_p3, *d_cpk = d_p3 + n, *d_v = d_p3 + 2 * n;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_cs, cs, n * 24)) || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_pkinf, pk_inf, n)) || (rc = up(d_gm, gamma_xy, n * 24)) ||
         (rc = up(d_gminf, gamma_inf, n)) || (rc = up(d_msg, msg, n * len * 12)) || (rc = ph.mark()))
@@ -461,7 +459,7 @@ extern "C" {
 
 int gh_bh_create(gh_curve_t curve, const uint64_t* gen_xy, const uint8_t* gen_inf, size_t num_windows, size_t window_size, gh_bh_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!out) return null_arg();
     *out = nullptr;
     if (!is_g1(curve)) { g_err = "the Bowe-Hopwood group must be a G1 curve"; return GH_E_BAD_ARG; }
     size_t ng = 0, b = 0;
@@ -469,21 +467,13 @@ int gh_bh_create(gh_curve_t curve, const uint64_t* gen_xy, const uint8_t* gen_in
         g_err = "num_windows and window_size must be positive and their product small enough";
         return GH_E_BAD_ARG;
     }
-    if (!gen_xy) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    if (!GH_G1_DISPATCH(curve, data_below, gen_xy, 2 * ng)) { g_err = "a generator coordinate is not below the modulus"; return GH_E_BAD_ARG; }
-    for (size_t i = 0; i < ng; i++)
-        if (!(gen_inf && gen_inf[i]) && !GH_G1_DISPATCH(curve, on_curve_host, gen_xy + 24 * i)) {
-            g_err = "a generator is not on the curve";
-            return GH_E_BAD_ARG;
-        }
+    if (!gen_xy) return null_arg();
+    if (int rc = check_generators(curve, "", gen_xy, gen_inf, ng)) return rc;
     auto* h = new gh_bh();
     h->curve = curve;
     h->num_windows = num_windows;
     h->window_size = window_size;
-    h->gen_xy.assign(gen_xy, gen_xy + 24 * ng);
-    h->gen_inf.assign(ng, 0);
-    if (gen_inf)
-        for (size_t i = 0; i < ng; i++) h->gen_inf[i] = gen_inf[i] != 0;
+    keep(h->gen_xy, h->gen_inf, gen_xy, gen_inf, ng);
     *out = h;
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
@@ -502,9 +492,9 @@ int gh_bh_hash(gh_bh_t h, const uint8_t* input, size_t n, size_t nbytes, uint64_
     std::lock_guard<std::mutex> lk(api_mutex());
     Trim trim_;
     if (!valid(h)) { g_err = "not a Bowe-Hopwood handle"; return GH_E_BAD_HANDLE; }
-    if (n && ((nbytes && !input) || !out_xy || !out_inf)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && ((nbytes && !input) || !out_xy || !out_inf)) return null_arg();
     size_t b = 0;
-    if (mul_overflows(n, nbytes, &b) || mul_overflows(n, 1024, &b) || nbytes > (SIZE_MAX >> 4)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, nbytes, &b) || mul_overflows(n, 1024, &b) || nbytes > (SIZE_MAX >> 4)) return too_large();
     if (8 * nbytes > 3 * h->num_windows * h->window_size) {
         g_err = "the input is longer than the parameters take (8 nbytes > 3 num_windows window_size)";
         return GH_E_BAD_ARG;
@@ -531,7 +521,7 @@ int gh_batch_double_mul(gh_curve_t curve, const uint64_t* xy1, const uint8_t* in
 
 int gh_ecvrf_create(gh_curve_t curve, gh_poseidon_t hash, gh_bh_t group_hash, int window, gh_ecvrf_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if (!hash || !group_hash || !out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!hash || !group_hash || !out) return null_arg();
     *out = nullptr;
     if (int rc = check_create("EC-VRF", curve, hash, window)) return rc;
     if (!valid(group_hash)) { g_err = "not a Bowe-Hopwood handle"; return GH_E_BAD_ARG; }
@@ -567,10 +557,8 @@ int gh_ecvrf_prove(gh_ecvrf_t h, const uint64_t* sk, const uint64_t* pk_xy, cons
     std::lock_guard<std::mutex> lk(api_mutex());
     Trim trim_;
     if (int rc = checked(h)) return rc;
-    if (n && (!sk || !pk_xy || !pk_inf || (len && !msg) || !nonce || !out_gamma_xy || !out_gamma_inf || !out_cs || !out_status)) {
-        g_err = "null argument";
-        return GH_E_BAD_ARG;
-    }
+    if (n && (!sk || !pk_xy || !pk_inf || (len && !msg) || !nonce || !out_gamma_xy || !out_gamma_inf || !out_cs || !out_status))
+        return null_arg();
     if (int rc = GH_G1_DISPATCH(h->curve, check_common, h, pk_xy, len ? msg : nullptr, n, len)) return rc;
     if (!GH_G1_DISPATCH(h->curve, scalar_below, sk, n) || !GH_G1_DISPATCH(h->curve, scalar_below, nonce, n)) {
         g_err = "a secret key or nonce is not below the modulus";
@@ -586,10 +574,8 @@ int gh_ecvrf_proof_to_hash(gh_ecvrf_t h, const uint64_t* pk_xy, const uint8_t* p
     std::lock_guard<std::mutex> lk(api_mutex());
     Trim trim_;
     if (int rc = checked(h)) return rc;
-    if (n && (!pk_xy || !pk_inf || (len && !msg) || !gamma_xy || !gamma_inf || !cs || !out_hash || !out_status)) {
-        g_err = "null argument";
-        return GH_E_BAD_ARG;
-    }
+    if (n && (!pk_xy || !pk_inf || (len && !msg) || !gamma_xy || !gamma_inf || !cs || !out_hash || !out_status))
+        return null_arg();
     if (int rc = GH_G1_DISPATCH(h->curve, check_common, h, pk_xy, len ? msg : nullptr, n, len)) return rc;
     if (!GH_G1_DISPATCH(h->curve, data_below, gamma_xy, 2 * n)) { g_err = "a gamma coordinate is not below the modulus"; return GH_E_BAD_ARG; }
     if (!GH_G1_DISPATCH(h->curve, data_below, cs, 2 * n)) { g_err = "a proof element is not below the modulus"; return GH_E_BAD_ARG; }

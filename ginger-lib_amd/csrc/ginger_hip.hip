@@ -69,7 +69,6 @@ int ensure_init() {
         if (msm_knobs().acc_alt) HIPCHK(hipStreamCreateWithPriority(&g.stream_acc_alt, hipStreamDefault, prio("GH_PRIO_ACC", least)));
     }
     for (auto& ev : g.tev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    for (auto& ev : g.ev) HIPCHK(hipEventCreate(&ev));
     for (auto& sl : g.pev) for (auto& ev : sl) HIPCHK(hipEventCreate(&ev));
     g.ready = true;
     return GH_OK;
@@ -244,13 +243,12 @@ int gh_shutdown(void) try {
     if (!g.ready) return GH_OK;
     (void)sync_msm_streams();
     pool_release("");
-    for (auto& f : g.at_shutdown) f();   // function-local device / pinned allocations (msm_impl.h)
+    for (auto& f : g.at_shutdown) f();   // function-local device / pinned allocations (msm_impl.h), the units' timer events (unit_host.h)
     g.at_shutdown.clear();
     for (int f = 0; f < 2; f++) {
         for (auto& kv : g.domains[f]) kv.second.release();
         g.domains[f].clear();
     }
-    for (auto& ev : g.ev) hipEventDestroy(ev);
     for (auto& sl : g.pev) for (auto& ev : sl) hipEventDestroy(ev);
     for (auto& ev : g.tev) hipEventDestroy(ev);
     hipStreamDestroy(g.stream_acc);

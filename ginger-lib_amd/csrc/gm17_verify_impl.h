@@ -37,7 +37,7 @@ struct gh_gm17_vk {
 
 namespace {
 
-Timing g_gm17_tm{9};                               // upload, g_psi, sums, test1 Miller / final exp, test2 Miller / final exp, compare, download
+PhaseTimer g_gm17_tm{9};                           // upload, g_psi, sums, test1 Miller / final exp, test2 Miller / final exp, compare, download
 
 // rows of status 2 are left alone (their pairs are skipped by pair_setup_kernel); every other row gets
 //   ns1 = -(A + g_alpha),  s2 = B + h_beta,  nb = -B     with their infinity bytes (nb's is B's own)
@@ -144,7 +144,7 @@ int run_gm17_verify(gh_gm17_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, c
     if (!rc) rc = dbuf("vb_gm17_val2", n * TW, &d_val2);
     if (!rc) rc = dbuf("vb_gm17_st2", n, &d_st2);
     if (rc) return rc;
-    Phases ph{g_gm17_tm};
+    PhaseTimer& ph = g_gm17_tm.begin();
     if ((rc = ph.mark())) return rc;
     if ((rc = upload_proofs<E>(v, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, n)) || (n_inputs && (rc = up(v.d_in, inputs, n * n_inputs * 12))) ||
         (rc = ph.mark()))
@@ -196,7 +196,7 @@ int api_gm17_vk_create(int engine, const uint64_t* g_alpha_g1_xy, const uint64_t
     typedef typename E::PF PF;
     typedef typename E::G1::FC F;
     constexpr size_t TW = tower_words<E>() / 2, TC = 2 * E::BDEG;       // u64 words / Fq coefficients of a G2 point
-    if (!g_alpha_g1_xy || !h_beta_g2_xy || !g_gamma_g1_xy || !h_gamma_g2_xy || !h_g2_xy || !query_g1_xy) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!g_alpha_g1_xy || !h_beta_g2_xy || !g_gamma_g1_xy || !h_gamma_g2_xy || !h_g2_xy || !query_g1_xy) return null_arg();
     size_t b;
     if (n_query == 0 || mul_overflows(n_query, 4096, &b)) { g_err = "query must hold at least one point"; return GH_E_BAD_ARG; }
     if (!all_below<PF>(g_alpha_g1_xy, 2) || !all_below<PF>(h_beta_g2_xy, TC) || !all_below<PF>(g_gamma_g1_xy, 2) || !all_below<PF>(h_gamma_g2_xy, TC) ||

@@ -1,11 +1,13 @@
 // ntt.hip -- evaluation-domain tables and launch sequence of the transforms (ntt_kernels.h).
-#include "runtime.h"
+#include "unit_host.h"
 #include "ntt_kernels.h"
 #include "host_math.h"
 #include "asm_kernels.h"
 
 namespace gh_rt {
 using namespace gh;
+
+static PhaseTimer g_fft_tm;   // the bracket around one transform: what g.last_fft_ms reports
 
 template <class P> struct FieldConsts;
 template <> struct FieldConsts<P6> {  // MNT4-753 Fr
@@ -120,7 +122,7 @@ template <class P> int fft_run(int fidx, void* d_data, uint32_t log_n, uint32_t 
     uint32_t* bufs[2] = {(uint32_t*)d_data, d->scratch};
     int cur = 0, log_ns = 0;
     static const bool ntt_asm = gh_asm::ntt_enabled();
-    HIPCHK(hipEventRecord(g.ev[4], g.stream));
+    if ((rc = g_fft_tm.begin().mark())) return rc;
     for (int s = 0; s < P_; s++) {
         NttPassArgs A;
         A.in = bufs[cur];
@@ -167,10 +169,10 @@ template <class P> int fft_run(int fidx, void* d_data, uint32_t log_n, uint32_t 
     }
     HIPCHK(hipGetLastError());
     if (cur == 1) HIPCHK(hipMemcpyAsync(d_data, d->scratch, ((size_t)96) << log_n, hipMemcpyDeviceToDevice, g.stream));
-    HIPCHK(hipEventRecord(g.ev[5], g.stream));
+    if ((rc = g_fft_tm.mark())) return rc;
     if (sync) {
         HIPCHK(hipStreamSynchronize(g.stream));
-        HIPCHK(hipEventElapsedTime(&g.last_fft_ms, g.ev[4], g.ev[5]));
+        return g_fft_tm.bracket(&g.last_fft_ms);
     }
     return GH_OK;
 }
@@ -325,48 +327,41 @@ template <class P> int domain_table_t(int fidx, uint32_t log_n, const Fp** tw) {
 int domain_table(gh_field_t field, uint32_t log_n, const Fp** tw) {
     if (field == GH_MNT4753_FR) return domain_table_t<P6>(0, log_n, tw);
     if (field == GH_MNT6753_FR) return domain_table_t<P4>(1, log_n, tw);
-    g_err = "unknown field id";
-    return GH_E_BAD_ARG;
+    return unknown_field();
 }
 
 int sap_witness_map(gh_field_t field, void* d_a, void* d_c, uint32_t log_n, const uint64_t* d1, const uint64_t* d2, void* d_h) {
     if (field == GH_MNT4753_FR) return sap_witness_map_t<P6>(0, d_a, d_c, log_n, d1, d2, d_h);
     if (field == GH_MNT6753_FR) return sap_witness_map_t<P4>(1, d_a, d_c, log_n, d1, d2, d_h);
-    g_err = "unknown field id";
-    return GH_E_BAD_ARG;
+    return unknown_field();
 }
 int batch_inverse(gh_field_t field, void* d_a, size_t n) {
     if (field == GH_MNT4753_FR) return batch_inverse_t<P6>(d_a, n);
     if (field == GH_MNT6753_FR) return batch_inverse_t<P4>(d_a, n);
-    g_err = "unknown field id";
-    return GH_E_BAD_ARG;
+    return unknown_field();
 }
 int lagrange_coefficients(gh_field_t field, uint32_t log_n, const uint64_t* tau12, void* d_out) {
     if (field == GH_MNT4753_FR) return lagrange_t<P6>(0, log_n, tau12, d_out);
     if (field == GH_MNT6753_FR) return lagrange_t<P4>(1, log_n, tau12, d_out);
-    g_err = "unknown field id";
-    return GH_E_BAD_ARG;
+    return unknown_field();
 }
 
 int witness_map(gh_field_t field, void* d_a, void* d_b, void* d_c, uint32_t log_n, const uint64_t* d1,
                 const uint64_t* d2, const uint64_t* d3, void* d_h) {
     if (field == GH_MNT4753_FR) return witness_map_t<P6>(0, d_a, d_b, d_c, log_n, d1, d2, d3, d_h);
     if (field == GH_MNT6753_FR) return witness_map_t<P4>(1, d_a, d_b, d_c, log_n, d1, d2, d3, d_h);
-    g_err = "unknown field id";
-    return GH_E_BAD_ARG;
+    return unknown_field();
 }
 
 int fft_run(gh_field_t field, void* d_data, uint32_t log_n, uint32_t flags) {
     if (field == GH_MNT4753_FR) return fft_run<P6>(0, d_data, log_n, flags);
     if (field == GH_MNT6753_FR) return fft_run<P4>(1, d_data, log_n, flags);
-    g_err = "unknown field id";
-    return GH_E_BAD_ARG;
+    return unknown_field();
 }
 int vec_op(gh_field_t field, int op, void* d_a, const void* d_b, const uint64_t* s, size_t n) {
     if (field == GH_MNT4753_FR) return vec_op<P6>(op, d_a, d_b, s, n);
     if (field == GH_MNT6753_FR) return vec_op<P4>(op, d_a, d_b, s, n);
-    g_err = "unknown field id";
-    return GH_E_BAD_ARG;
+    return unknown_field();
 }
 
 }  // namespace gh_rt

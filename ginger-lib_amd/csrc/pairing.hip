@@ -67,7 +67,7 @@ int gh_pairing_product(int engine, const uint64_t* g1_xy, const uint8_t* g1_inf,
 int gh_groth16_vk_create(int engine, const uint64_t* alpha_g1_beta_g2, const uint64_t* gamma_g2_xy, const uint64_t* delta_g2_xy,
                          const uint64_t* gamma_abc_g1_xy, size_t n_abc, gh_groth16_vk_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!out) return null_arg();
     *out = nullptr;
     const PairingOps* ops = ops_of_engine(engine);
     if (!ops) return GH_E_BAD_ARG;
@@ -111,7 +111,7 @@ int gh_groth16_verify_compressed(gh_groth16_vk_t h, const uint64_t* a_x, const u
 int gh_gm17_vk_create(int engine, const uint64_t* g_alpha_g1_xy, const uint64_t* h_beta_g2_xy, const uint64_t* g_gamma_g1_xy,
                       const uint64_t* h_gamma_g2_xy, const uint64_t* h_g2_xy, const uint64_t* query_g1_xy, size_t n_query, gh_gm17_vk_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!out) return null_arg();
     *out = nullptr;
     const PairingOps* ops = ops_of_engine(engine);
     if (!ops) return GH_E_BAD_ARG;

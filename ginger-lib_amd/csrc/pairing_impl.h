@@ -70,7 +70,7 @@ const PairingOps* pairing_ops_mnt6753();
 
 namespace {
 
-Timing g_tm{6};                                    // upload, g_ic, Miller loop, final exponentiation, compare, download
+PhaseTimer g_tm{6};                                // upload, g_ic, Miller loop, final exponentiation, compare, download
 
 // the signed digits of an engine's loop count and of its w0, most significant first
 __constant__ int8_t c_ate_naf4[GH_MNT4_ATE_DIGITS] = GH_MNT4_ATE_NAF;
@@ -346,7 +346,7 @@ __global__ void __launch_bounds__(256) bcast_xy_kernel(const uint32_t* __restric
 // setup, Miller loop and final exponentiation of n rows on g.stream: d_val[i] = the row's value in ABI form (24 D u64).  tab: the
 // KP prepared tables.  The slab is cut into chunks below PAIR_SLAB_BYTES.
 template <class E, int KV, int KP>
-int launch_pairs(const PairIn& in, const uint8_t* d_status, const typename E::Coeff* tab, size_t n, uint64_t* d_val, Phases* ph) {
+int launch_pairs(const PairIn& in, const uint8_t* d_status, const typename E::Coeff* tab, size_t n, uint64_t* d_val, PhaseTimer* ph) {
     constexpr size_t row_bytes = (size_t)(var_slots<E>() * KV + PRE_SLOTS * KP) * NL * 4;
     const size_t chunk = slab_chunk_rows(EngineHost<E>::pairs_loop, PAIR_SLAB_BYTES, row_bytes, n);
     uint32_t* slab;
@@ -381,7 +381,7 @@ int run_product(const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2
     if (!rc) rc = dbuf("vb_pair_i2", m, &d_i2);
     if (!rc) rc = dbuf("vb_pair_val", n * TW, &d_val);
     if (rc) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_g1, g1_xy, m * 24)) || (rc = up(d_g2, g2_xy, m * TW)) || (rc = up(d_i1, g1_inf, m)) || (rc = up(d_i2, g2_inf, m)) ||
         (rc = ph.mark()) || (rc = ph.mark()))                                                                    // no g_ic phase
@@ -521,7 +521,7 @@ int upload_proofs(const VerifyBufs& v, const uint64_t* a_xy, const uint8_t* a_in
 // the device part of a verification, over proof points and inputs that are on the device: the curve check, g_ic, the Miller
 // loops, the final exponentiation and the compare, with the marks of those phases; v.d_st holds the rows' status.  d_pst
 // (nullable): 3 point codes per row, a row with a non-zero one gets status 3 and is not evaluated.
-template <class E> int verify_device(gh_groth16_vk* h, const VerifyBufs& v, const uint8_t* d_pst, size_t n, size_t n_inputs, Phases& ph) {
+template <class E> int verify_device(gh_groth16_vk* h, const VerifyBufs& v, const uint8_t* d_pst, size_t n, size_t n_inputs, PhaseTimer& ph) {
     constexpr size_t TW = tower_words<E>() / 2;
     int rc;
     GH_LAUNCH((proof_check_kernel<E>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)v.d_a, (const uint8_t*)v.d_ai,
@@ -547,7 +547,7 @@ int run_verify(gh_groth16_vk* h, const uint64_t* a_xy, const uint8_t* a_inf, con
     VerifyBufs v;
     int rc = verify_bufs<E>(n, n_inputs, v);
     if (rc) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark())) return rc;
     if ((rc = upload_proofs<E>(v, a_xy, a_inf, b_xy, b_inf, c_xy, c_inf, n)) || (n_inputs && (rc = up(v.d_in, inputs, n * n_inputs * 12))) ||
         (rc = ph.mark()))
@@ -584,7 +584,7 @@ int run_verify_validated(gh_groth16_vk* h, int compressed, const uint64_t* a, co
         if (!rc) rc = dbuf("vb_pts_cf", n, &d_cf);
     }
     if (rc) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark())) return rc;
     if (n_inputs && (rc = up(v.d_in, inputs, n * n_inputs * 12))) return rc;
     if (compressed) {
@@ -635,9 +635,9 @@ template <class E>
 int api_product(const uint64_t* g1_xy, const uint8_t* g1_inf, const uint64_t* g2_xy, const uint8_t* g2_inf, size_t n, size_t k, uint64_t* out_gt) {
     typedef typename E::PF PF;
     if (k < 1 || k > MAX_PAIRS) { g_err = "the number of pairs per row must be 1, 2 or 3"; return GH_E_BAD_ARG; }
-    if (n && (!g1_xy || !g1_inf || !g2_xy || !g2_inf || !out_gt)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!g1_xy || !g1_inf || !g2_xy || !g2_inf || !out_gt)) return null_arg();
     size_t b;
-    if (mul_overflows(n, 4096, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, 4096, &b)) return too_large();
     if (!all_below<PF>(g1_xy, 2 * n * k) || !all_below<PF>(g2_xy, 2 * E::BDEG * n * k)) { g_err = "a coordinate is not below the modulus"; return GH_E_BAD_ARG; }
     if (n == 0) return GH_OK;
     if (int rc = gh_rt::ensure_init()) return rc;
@@ -649,7 +649,7 @@ int api_vk_create(int engine, const uint64_t* alpha_g1_beta_g2, const uint64_t* 
                   const uint64_t* gamma_abc_g1_xy, size_t n_abc, gh_groth16_vk** out) {
     typedef typename E::PF PF;
     constexpr size_t TW = tower_words<E>() / 2, TC = 2 * E::BDEG;       // u64 words / Fq coefficients of a G2 point and of a GT element
-    if (!alpha_g1_beta_g2 || !gamma_g2_xy || !delta_g2_xy || !gamma_abc_g1_xy) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!alpha_g1_beta_g2 || !gamma_g2_xy || !delta_g2_xy || !gamma_abc_g1_xy) return null_arg();
     size_t b;
     if (n_abc == 0 || mul_overflows(n_abc, 4096, &b)) { g_err = "gamma_abc_g1 must hold at least one point"; return GH_E_BAD_ARG; }
     if (!all_below<PF>(alpha_g1_beta_g2, TC) || !all_below<PF>(gamma_g2_xy, TC) || !all_below<PF>(delta_g2_xy, TC) ||
@@ -684,9 +684,9 @@ int check_proof_args(size_t n_points, const char* what, bool compressed, const u
         g_err = std::string("the number of public inputs does not match ") + what + " (MalformedVerifyingKey)";
         return GH_E_BAD_ARG;
     }
-    if (n && (!a || !a_inf || !b || !b_inf || !c || !c_inf || (n_inputs && !inputs) || !out_status)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!a || !a_inf || !b || !b_inf || !c || !c_inf || (n_inputs && !inputs) || !out_status)) return null_arg();
     size_t ni = 0, by = 0;
-    if (mul_overflows(n, n_inputs, &ni) || mul_overflows(ni, 96 * 4, &by) || mul_overflows(n, 4096, &by)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, n_inputs, &ni) || mul_overflows(ni, 96 * 4, &by) || mul_overflows(n, 4096, &by)) return too_large();
     if (!compressed && (!all_below<PF>(a, 2 * n) || !all_below<PF>(b, 2 * E::BDEG * n) || !all_below<PF>(c, 2 * n))) {
         g_err = "a proof coordinate is not below the modulus";
         return GH_E_BAD_ARG;

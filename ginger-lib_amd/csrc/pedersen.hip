@@ -1,5 +1,6 @@
 // pedersen.hip -- the C ABI of include/ginger_hip_pedersen.h: the Pedersen hash (primitives/src/crh/pedersen) and the Pedersen
-// commitment (primitives/src/commitment/pedersen) over the two G1 groups, on the helpers of vb_kernels.h.  DESIGN.md section 13a.
+// commitment (primitives/src/commitment/pedersen) over the two G1 groups, on the host layer of unit_host.h and the normalisation
+// and conversion kernels of vb_kernels.h.  DESIGN.md section 13a.
 //
 // Both are sums of fixed generators selected by input bits.  With t table bits (pedersen_digits.h) the generators are cut into
 // groups of t and the table holds the 2^t - 1 subset sums of every group, so that a row costs one mixed addition per t bits:
@@ -35,7 +36,7 @@ namespace {
 constexpr size_t RAND_BITS = VB_BITS;                 // 753 randomness generators: MODULUS_BITS of both scalar fields
 constexpr int DEFAULT_TABLE_BITS = 8;
 enum { PH_UPLOAD, PH_HASH, PH_NORMALISE, PH_FINISH, NPHASES };
-Timing g_tm{NPHASES};
+PhaseTimer g_tm{NPHASES};
 
 // entry e = ped_entry(t, p, m) of `count` generators: the sum of g_(p t + j) over the bits j of m, as Proj<C>
 template <class C>
@@ -162,7 +163,7 @@ int run_rows(gh_pedersen* h, const uint8_t* input, size_t n, size_t nbytes, cons
     if (!rc && !dev) rc = dbuf("vb_xy", n * 24, &d_xy);
     if (!rc && !dev) rc = dbuf("vb_inf", n, &d_inf);
     if (rc || (rc = ped_ensure<C>(h, rnd != nullptr))) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark())) return rc;
     if (dev) {
         d_in = const_cast<uint8_t*>(input);
@@ -195,34 +196,13 @@ int checked(const gh_pedersen* h) {
     return GH_OK;
 }
 
-// x || y rows of `count` generators: below the modulus, and on the curve unless flagged at infinity; `what` names them
-int check_generators(gh_curve_t curve, const char* what, const uint64_t* xy, const uint8_t* inf, size_t count) {
-    if (!GH_G1_DISPATCH(curve, data_below, xy, 2 * count)) {
-        g_err = std::string(what) + ": a generator coordinate is not below the modulus";
-        return GH_E_BAD_ARG;
-    }
-    for (size_t i = 0; i < count; i++)
-        if (!(inf && inf[i]) && !GH_G1_DISPATCH(curve, on_curve_host, xy + 24 * i)) {
-            g_err = std::string(what) + ": a generator is not on the curve";
-            return GH_E_BAD_ARG;
-        }
-    return GH_OK;
-}
-
-void keep(std::vector<uint64_t>& xy, std::vector<uint8_t>& flags, const uint64_t* src, const uint8_t* inf, size_t count) {
-    xy.assign(src, src + 24 * count);
-    flags.assign(count, 0);
-    if (inf)
-        for (size_t i = 0; i < count; i++) flags[i] = inf[i] != 0;
-}
-
 // what the four compute entry points share; rnd_given: a commitment
 int compute_api(gh_pedersen* h, const void* input, size_t n, size_t nbytes, bool rnd_given, const void* rnd, void* out_xy, void* out_inf, bool dev) {
     if (int rc = checked(h)) return rc;
     if (rnd_given && h->rand_xy.empty()) { g_err = "randomness: the handle was made without randomness generators (rand_xy)"; return GH_E_BAD_ARG; }
-    if (n && ((nbytes && !input) || (rnd_given && !rnd) || !out_xy || !out_inf)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && ((nbytes && !input) || (rnd_given && !rnd) || !out_xy || !out_inf)) return null_arg();
     size_t b = 0;
-    if (mul_overflows(n, nbytes, &b) || mul_overflows(n, 1024, &b) || nbytes > (SIZE_MAX >> 4)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, nbytes, &b) || mul_overflows(n, 1024, &b) || nbytes > (SIZE_MAX >> 4)) return too_large();
     if (8 * nbytes > h->ng) {
         g_err = "nbytes: the input is longer than the parameters take (8 nbytes > num_windows window_size)";
         return GH_E_BAD_ARG;
@@ -247,7 +227,7 @@ extern "C" {
 int gh_pedersen_create(gh_curve_t curve, const uint64_t* gen_xy, const uint8_t* gen_inf, size_t num_windows, size_t window_size,
                        const uint64_t* rand_xy, const uint8_t* rand_inf, size_t n_rand, int table_bits, gh_pedersen_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!out) return null_arg();
     *out = nullptr;
     if (curve == GH_MNT4753_G2 || curve == GH_MNT6753_G2) { g_err = "gh_pedersen_create: G1 curves only"; return GH_E_UNSUPPORTED; }
     if (!is_g1(curve)) { g_err = "unknown curve id"; return GH_E_BAD_ARG; }
@@ -257,14 +237,14 @@ int gh_pedersen_create(gh_curve_t curve, const uint64_t* gen_xy, const uint8_t* 
         g_err = "num_windows and window_size must be positive and their product small enough";
         return GH_E_BAD_ARG;
     }
-    if (!gen_xy) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!gen_xy) return null_arg();
     if (n_rand ? (n_rand != RAND_BITS || !rand_xy) : rand_xy != nullptr) {
         g_err = "n_rand must be 753 with rand_xy (the scalar fields' MODULUS_BITS), or 0 with rand_xy null";
         return GH_E_BAD_ARG;
     }
-    if (int rc = check_generators(curve, "gen_xy", gen_xy, gen_inf, ng)) return rc;
+    if (int rc = check_generators(curve, "gen_xy: ", gen_xy, gen_inf, ng)) return rc;
     if (n_rand)
-        if (int rc = check_generators(curve, "rand_xy", rand_xy, rand_inf, n_rand)) return rc;
+        if (int rc = check_generators(curve, "rand_xy: ", rand_xy, rand_inf, n_rand)) return rc;
     auto* h = new gh_pedersen();
     h->curve = curve;
     h->num_windows = num_windows;

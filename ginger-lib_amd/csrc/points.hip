@@ -11,7 +11,7 @@
 
 namespace {
 
-Timing g_tm{3};                                    // upload, validate, download
+PhaseTimer g_tm{3};                                // upload, validate, download
 
 // (t - 1) / 2 of the three fields a root is taken in, and the signed digits of the two group orders
 __constant__ uint32_t c_e_p4[SQRT_E_WORDS_P4] = GH_P4_SQRT_E32;
@@ -106,7 +106,7 @@ template <class C> int run_membership(const uint64_t* xy, const uint8_t* inf, si
     if (!rc) rc = dbuf("vb_pts_inf", n, &d_inf);
     if (!rc) rc = dbuf("vb_pts_st", n, &d_ok);
     if (rc) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark()) || (rc = up(d_xy, xy, n * 2 * CW)) || (rc = up(d_inf, inf, n)) || (rc = ph.mark())) return rc;
     if ((rc = member_dev<C>(d_xy, d_inf, n, d_ok, 1, 1)) || (rc = ph.mark())) return rc;
     HIPCHK(hipMemcpyAsync(out_ok, d_ok, n, hipMemcpyDeviceToHost, g.stream));
@@ -125,7 +125,7 @@ template <class C> int run_decompress(const uint64_t* x, const uint8_t* flags, s
     if (!rc) rc = dbuf("vb_pts_inf", n, &d_inf);
     if (!rc) rc = dbuf("vb_pts_st", n, &d_st);
     if (rc) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark()) || (rc = up(d_x, x, n * CW)) || (rc = up(d_fl, flags, n)) || (rc = ph.mark())) return rc;
     if ((rc = decompress_dev<C>(d_x, d_fl, n, d_xy, d_inf, d_st, 1)) || (rc = ph.mark())) return rc;
     HIPCHK(hipMemcpyAsync(out_xy, d_xy, n * 2 * CW * 8, hipMemcpyDeviceToHost, g.stream));
@@ -145,7 +145,7 @@ template <class C> int run_compress(const uint64_t* xy, const uint8_t* inf, size
     if (!rc) rc = dbuf("vb_pts_xy", n * 2 * CW, &d_xy);
     if (!rc) rc = dbuf("vb_pts_inf", n, &d_inf);
     if (rc) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark()) || (rc = up(d_xy, xy, n * 2 * CW)) || (rc = up(d_inf, inf, n)) || (rc = ph.mark())) return rc;
     GH_LAUNCH((compress_kernel<C>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_xy, (const uint8_t*)d_inf, n, (uint32_t*)d_x,
               d_fl);
@@ -164,9 +164,9 @@ template <class C> bool coords_below(const uint64_t* xy, size_t n) { return all_
 // what every entry point checks of the curve, the pointers (non_null) and the row count
 int check_call(gh_curve_t curve, size_t n, bool non_null) {
     if (curve < GH_MNT4753_G1 || curve > GH_MNT6753_G2) return gh_rt::unknown_curve();
-    if (n && !non_null) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && !non_null) return null_arg();
     size_t b;
-    if (mul_overflows(n, 4096, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, 4096, &b)) return too_large();
     return GH_OK;
 }
 
@@ -183,15 +183,9 @@ int points_decompress_dev(gh_curve_t curve, const void* d_x, const uint8_t* d_fl
     return GH_CURVE_DISPATCH(curve, decompress_dev, d_x, d_flags, n, d_xy, d_inf, d_code, stride);
 }
 int points_validate_mark(int end) {
-    HIPCHK(hipEventRecord(g.ev[8 + (end ? 1 : 0)], g.stream));
-    return GH_OK;
+    return end ? g_tm.mark() : g_tm.begin().mark();
 }
-int points_validate_finish() {
-    for (int i = 0; i < g_tm.nph; i++) g_tm.ms[i] = 0;
-    HIPCHK(hipEventElapsedTime(&g_tm.ms[1], g.ev[8], g.ev[9]));
-    g_tm.total_ms = g_tm.ms[1];
-    return GH_OK;
-}
+int points_validate_finish() { return g_tm.single(1); }
 
 }  // namespace gh_rt
 

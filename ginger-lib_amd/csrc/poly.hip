@@ -13,26 +13,21 @@
 // Mul and the division of evaluations are sequences over fft_run, vec_op and batch_inverse of runtime.h.
 #include <algorithm>
 #include <vector>
-#include "runtime.h"
+#include "unit_host.h"
 #include "poly_kernels.h"
 #include "../../include/ginger_hip_poly.h"
 
 namespace {
 
-using namespace gh;
 using gh_rt::DevMem;
-using gh_rt::g;
-using gh_rt::g_err;
 
 constexpr int BLOCK = 128;             // the fold and the scan: lanes that hold a product
 constexpr int EBLOCK = 256;            // one row per lane
 constexpr int RBLOCK = 256, RITEMS = 8;   // a block of the reduction covers RBLOCK * RITEMS rows
 constexpr int FOLD_GROUP = 4;          // points that share a pass over the coefficients
-inline unsigned blocks(uint64_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 PolyTuning g_tune;
-float g_ms = 0;
-hipEvent_t g_ev[2] = {nullptr, nullptr};
+PhaseTimer g_tm{1};                    // one bracket: from before the first launch to the one wait of an entry point
 
 // ---------------------------------------------------------------------------------------------------- kernels
 // w: k factors of this level; point p0 + p reads fin + (p0 + p) in_stride (ABI_IN: every point reads abi) and writes
@@ -118,45 +113,20 @@ template <bool COUNT> __global__ void __launch_bounds__(RBLOCK) poly_reduce_kern
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-template <class P> Fp from_abi12(const uint64_t* v12) { return fp_from_abi<P>(reinterpret_cast<const uint32_t*>(v12)); }
-
 int two_adicity(gh_field_t f) { return f == GH_MNT4753_FR ? GH_P6_TWO_ADICITY : GH_P4_TWO_ADICITY; }
-int field_ok(gh_field_t f) {
-    if (f == GH_MNT4753_FR || f == GH_MNT6753_FR) return GH_OK;
-    g_err = "unknown field id";
-    return GH_E_BAD_ARG;
-}
-int null_arg() { g_err = "null argument"; return GH_E_BAD_ARG; }
-int rows_ok(size_t n) {
-    if (n > (SIZE_MAX >> 9)) { g_err = "input too large"; return GH_E_BAD_ARG; }
-    return GH_OK;
-}
+int rows_ok(size_t n) { return n > (SIZE_MAX >> 9) ? too_large() : GH_OK; }
 int domain_ok(gh_field_t f, uint32_t log_n) {
     if ((int)log_n >= two_adicity(f)) { g_err = "domain exceeds the field's 2-adicity"; return GH_E_UNSUPPORTED; }
     return GH_OK;
 }
-#define POLY_DISPATCH(field, fn, ...) ((field) == GH_MNT4753_FR ? fn<P6>(__VA_ARGS__) : fn<P4>(__VA_ARGS__))
 
-// the two events of gh_poly_last_timing: begin before the first launch, end before the one wait of an entry point
-int tm_begin() {
-    if (!g_ev[0]) {
-        HIPCHK(hipEventCreate(&g_ev[0]));
-        HIPCHK(hipEventCreate(&g_ev[1]));
-        g.at_shutdown.push_back([] {
-            for (hipEvent_t& e : g_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-        });
-    }
-    HIPCHK(hipEventRecord(g_ev[0], g.stream));
-    return GH_OK;
-}
-int tm_end() {
+// the end of a timed entry point: the second mark, the one wait, the record of gh_poly_last_timing
+int wait_timed() {
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(g_ev[1], g.stream));
+    if (int rc = g_tm.mark()) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
-    HIPCHK(hipEventElapsedTime(&g_ms, g_ev[0], g_ev[1]));
-    return GH_OK;
+    return g_tm.single(0);
 }
-template <class T> int pool(const char* name, size_t count, T** out) { return gh_rt::pool_get(name, count * sizeof(T), (void**)out); }
 
 // ---- evaluate.  hw must outlive the caller's wait: its upload is asynchronous.
 template <class P> int evaluate_issue(const uint32_t* d_c, size_t n, const uint64_t* points12, size_t k, uint32_t* d_res, std::vector<Fp>& hw) {
@@ -174,9 +144,9 @@ template <class P> int evaluate_issue(const uint32_t* d_c, size_t n, const uint6
     size_t total = 0;
     for (int l = 0; l + 1 < nl; l++) total += (size_t)lv[l].G * k;
     Fp *d_w, *d_lvl = nullptr;
-    if (int rc = pool("poly_w", hw.size(), &d_w)) return rc;
+    if (int rc = dbuf("poly_w", hw.size(), &d_w, 0)) return rc;
     if (total)
-        if (int rc = pool("poly_lvl", total, &d_lvl)) return rc;
+        if (int rc = dbuf("poly_lvl", total, &d_lvl, 0)) return rc;
     HIPCHK(hipMemcpyAsync(d_w, hw.data(), hw.size() * sizeof(Fp), hipMemcpyHostToDevice, g.stream));
     const Fp* in = nullptr;
     Fp* out = d_lvl;
@@ -199,13 +169,13 @@ template <class P> int evaluate_issue(const uint32_t* d_c, size_t n, const uint6
 }
 template <class P> int evaluate_run(const void* d_c, size_t n, const uint64_t* points12, size_t k, uint64_t* out12) {
     uint32_t* d_res;
-    if (int rc = pool("poly_res", k * 24, &d_res)) return rc;
+    if (int rc = dbuf("poly_res", k * 24, &d_res, 0)) return rc;
     std::vector<Fp> hw;
-    int rc = tm_begin();
+    int rc = g_tm.begin().mark();
     if (!rc) rc = evaluate_issue<P>((const uint32_t*)d_c, n, points12, k, d_res, hw);
     if (rc) { (void)hipStreamSynchronize(g.stream); return rc; }
     HIPCHK(hipMemcpyAsync(out12, d_res, k * 96, hipMemcpyDeviceToHost, g.stream));
-    return tm_end();
+    return wait_timed();
 }
 
 // ---- scan: T over the m rows of d_in with stride N; T_i goes to row i of lo where i < split, to row i - split of hi otherwise
@@ -218,7 +188,7 @@ int scan_issue(const uint32_t* d_in, uint64_t m, uint64_t N, uint32_t L, uint32_
     for (int l = 1; l < nl; l++) total += (size_t)lv[l].m;
     Fp* d_lvl = nullptr;
     if (total)
-        if (int rc = pool("poly_lvl", total, &d_lvl)) return rc;
+        if (int rc = dbuf("poly_lvl", total, &d_lvl, 0)) return rc;
     std::vector<Fp*> vec((size_t)nl, nullptr);
     std::vector<Fp> mu((size_t)nl, mu0);
     for (int l = 1; l < nl; l++) {
@@ -246,22 +216,22 @@ template <class P> int divide_linear_run(const void* d_in, size_t n, const uint6
         return GH_OK;
     }
     uint32_t* d_rem;
-    if (int rc = pool("poly_res", (size_t)24, &d_rem)) return rc;
-    int rc = tm_begin();
+    if (int rc = dbuf("poly_res", (size_t)24, &d_rem, 0)) return rc;
+    int rc = g_tm.begin().mark();
     if (!rc) rc = scan_issue<P, true>((const uint32_t*)d_in, n, 1, g_tune.run_len, g_tune.direct_max, from_abi12<P>(z12), 1, d_rem, (uint32_t*)d_q);
     if (rc) { (void)hipStreamSynchronize(g.stream); return rc; }
     HIPCHK(hipMemcpyAsync(rem12, d_rem, 96, hipMemcpyDeviceToHost, g.stream));
-    return tm_end();
+    return wait_timed();
 }
 
 template <class P> int divide_vanishing_run(const void* d_in, size_t n, uint32_t log_n, void* d_q, void* d_r) {
     const uint64_t N = (uint64_t)1 << log_n;
-    int rc = tm_begin();
+    int rc = g_tm.begin().mark();
     if (rc) return rc;
     if (n < N) HIPCHK(hipMemsetAsync((uint8_t*)d_r + n * 96, 0, (N - n) * 96, g.stream));      // r = p padded with zeros
     rc = scan_issue<P, false>((const uint32_t*)d_in, n, N, g_tune.seg_max, g_tune.seg_max, fp_zero(), N, (uint32_t*)d_r, (uint32_t*)d_q);
     if (rc) { (void)hipStreamSynchronize(g.stream); return rc; }
-    return tm_end();
+    return wait_timed();
 }
 
 // ---- reductions, each with its own wait: *result is the host's finish of the per-block results
@@ -270,7 +240,7 @@ template <bool COUNT> int reduce_rows(const uint32_t* d, size_t n, size_t* resul
     if (!n) return GH_OK;
     const size_t nb = blocks(n, RBLOCK * RITEMS);
     uint64_t* d_pb;
-    if (int rc = pool("poly_red", nb, &d_pb)) return rc;
+    if (int rc = dbuf("poly_red", nb, &d_pb, 0)) return rc;
     std::vector<uint64_t> pb(nb);
     GH_LAUNCH((poly_reduce_kernel<COUNT>), dim3((unsigned)nb), dim3(RBLOCK), 0, g.stream, d, (uint64_t)n, d_pb);
     HIPCHK(hipGetLastError());
@@ -295,26 +265,26 @@ template <class P> int axpy_run(int op, const void* d_a, size_t na, const void* 
     const size_t rows = std::max(na, nb);
     if (!rows) return GH_OK;
     const Fp f = f12 ? from_abi12<P>(f12) : fp_zero();
-    if (int rc = tm_begin()) return rc;
+    if (int rc = g_tm.begin().mark()) return rc;
     GH_LAUNCH((poly_axpy_kernel<P>), dim3(blocks(rows, EBLOCK)), dim3(EBLOCK), 0, g.stream, op, (const uint32_t*)d_a, (uint64_t)na, (const uint32_t*)d_b, (uint64_t)nb,
               f, (uint32_t*)d_out, (uint64_t)rows);
-    return tm_end();
+    return wait_timed();
 }
 
 template <class P> int mul_vanishing_run(const void* d_in, size_t n, uint32_t log_n, void* d_out) {
     const uint64_t N = (uint64_t)1 << log_n;
-    if (int rc = tm_begin()) return rc;
+    if (int rc = g_tm.begin().mark()) return rc;
     GH_LAUNCH((poly_mul_vanishing_kernel<P>), dim3(blocks(n + N, EBLOCK)), dim3(EBLOCK), 0, g.stream, (const uint32_t*)d_in, (uint64_t)n, N, (uint32_t*)d_out);
-    return tm_end();
+    return wait_timed();
 }
 
 template <class P> int elements_run(gh_field_t field, uint32_t log_n, void* d_out) {
     const Fp* tw;
     if (int rc = gh_rt::domain_table(field, log_n, &tw)) return rc;
     const uint64_t N = (uint64_t)1 << log_n;
-    if (int rc = tm_begin()) return rc;
+    if (int rc = g_tm.begin().mark()) return rc;
     GH_LAUNCH((poly_elements_kernel<P>), dim3(blocks(N, EBLOCK)), dim3(EBLOCK), 0, g.stream, tw, N, (uint32_t*)d_out);
-    return tm_end();
+    return wait_timed();
 }
 
 template <class P> int sparse_run(gh_field_t field, const uint64_t* exps, const uint64_t* coeffs12, size_t t, uint32_t log_n, void* d_out) {
@@ -331,15 +301,15 @@ template <class P> int sparse_run(gh_field_t field, const uint64_t* exps, const 
     Fp* d_c = nullptr;
     if (t) {
         int rc;
-        if ((rc = pool("poly_sp_e", t, &d_e)) || (rc = pool("poly_sp_c", t, &d_c))) return rc;
+        if ((rc = dbuf("poly_sp_e", t, &d_e, 0)) || (rc = dbuf("poly_sp_c", t, &d_c, 0))) return rc;
     }
-    if (int rc = tm_begin()) return rc;
+    if (int rc = g_tm.begin().mark()) return rc;
     if (t) {
         HIPCHK(hipMemcpyAsync(d_e, he.data(), t * 8, hipMemcpyHostToDevice, g.stream));
         HIPCHK(hipMemcpyAsync(d_c, hc.data(), t * sizeof(Fp), hipMemcpyHostToDevice, g.stream));
     }
     GH_LAUNCH((poly_sparse_kernel<P>), dim3(blocks(N, EBLOCK)), dim3(EBLOCK), 0, g.stream, log_n, tw, (const uint64_t*)d_e, (const Fp*)d_c, (uint64_t)t, (uint32_t*)d_out);
-    return tm_end();                                          // he, hc live until here
+    return wait_timed();                                          // he, hc live until here
 }
 
 // Mul (dense.rs:342-357).  The checks that need the trimmed lengths come first, as the reference returns zero before it asks
@@ -356,8 +326,8 @@ int mul_run(gh_field_t field, const void* d_a, size_t na, const void* d_b, size_
     const size_t N = (size_t)1 << log_n;
     if (out_cap < N) { g_err = "out_cap: the output holds fewer rows than the domain of n_a + n_b coefficients"; return GH_E_BAD_ARG; }
     uint8_t* d_pb;
-    if ((rc = pool("poly_mul_b", N * 96, &d_pb))) return rc;
-    if ((rc = tm_begin())) return rc;
+    if ((rc = dbuf("poly_mul_b", N * 96, &d_pb, 0))) return rc;
+    if ((rc = g_tm.begin().mark())) return rc;
     uint8_t* d_pa = (uint8_t*)d_out;
     HIPCHK(hipMemcpyAsync(d_pa, d_a, ta * 96, hipMemcpyDeviceToDevice, g.stream));             // rows from the trimmed length on are zero
     HIPCHK(hipMemsetAsync(d_pa + ta * 96, 0, (N - ta) * 96, g.stream));
@@ -366,7 +336,7 @@ int mul_run(gh_field_t field, const void* d_a, size_t na, const void* d_b, size_
     if ((rc = gh_rt::fft_run(field, d_pa, log_n, 0)) || (rc = gh_rt::fft_run(field, d_pb, log_n, 0)) || (rc = gh_rt::vec_op(field, 0, d_pa, d_pb, nullptr, N)) ||
         (rc = gh_rt::fft_run(field, d_pa, log_n, GH_FFT_INVERSE)))
         return rc;
-    if ((rc = tm_end())) return rc;
+    if ((rc = wait_timed())) return rc;
     return reduce_run<false>(d_pa, ta + tb - 1, n_out);      // the degrees add up: nothing above is non-zero
 }
 
@@ -377,10 +347,10 @@ int evals_div_run(gh_field_t field, void* d_a, const void* d_b, size_t n, size_t
     if (*zero_divisors) return GH_OK;
     uint8_t* d_inv;
     int rc;
-    if ((rc = pool("poly_div_b", n * 96, &d_inv)) || (rc = tm_begin())) return rc;
+    if ((rc = dbuf("poly_div_b", n * 96, &d_inv, 0)) || (rc = g_tm.begin().mark())) return rc;
     HIPCHK(hipMemcpyAsync(d_inv, d_b, n * 96, hipMemcpyDeviceToDevice, g.stream));
     if ((rc = gh_rt::batch_inverse(field, d_inv, n)) || (rc = gh_rt::vec_op(field, 0, d_a, d_inv, nullptr, n))) return rc;
-    return tm_end();
+    return wait_timed();
 }
 
 // host-buffer forms: a device copy of an input vector / the download of an output vector
@@ -415,7 +385,7 @@ int gh_poly_evaluate_dev(gh_field_t field, const void* d_coeffs, size_t n, const
     if (k == 0) { g_err = "k: at least one point"; return GH_E_BAD_ARG; }
     if (k > 65535) { g_err = "k: at most 65535 points in one call"; return GH_E_BAD_ARG; }      // a point (or a group of them) per grid.y
     if (int rc = ensure_init()) return rc;
-    return POLY_DISPATCH(field, evaluate_run, d_coeffs, n, points12, k, out12);
+    return GH_FIELD_DISPATCH(field, evaluate_run, d_coeffs, n, points12, k, out12);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_poly_evaluate(gh_field_t field, const uint64_t* coeffs, size_t n, const uint64_t* points12, size_t k, uint64_t* out12) try {
@@ -426,7 +396,7 @@ int gh_poly_evaluate(gh_field_t field, const uint64_t* coeffs, size_t n, const u
     if (int rc = ensure_init()) return rc;
     DevMem d;
     if (int rc = up(d, coeffs, n)) return rc;
-    return POLY_DISPATCH(field, evaluate_run, d.get(), n, points12, k, out12);
+    return GH_FIELD_DISPATCH(field, evaluate_run, d.get(), n, points12, k, out12);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_poly_resize_dev(gh_field_t field, const void* d_in, size_t n, void* d_out, size_t n_out) try {
@@ -435,10 +405,10 @@ int gh_poly_resize_dev(gh_field_t field, const void* d_in, size_t n, void* d_out
     if (!n_out) return GH_OK;
     if (int rc = ensure_init()) return rc;
     const size_t keep = std::min(n, n_out);
-    if (int rc = tm_begin()) return rc;
+    if (int rc = g_tm.begin().mark()) return rc;
     if (keep) HIPCHK(hipMemcpyAsync(d_out, d_in, keep * 96, hipMemcpyDeviceToDevice, g.stream));
     if (n_out > keep) HIPCHK(hipMemsetAsync((uint8_t*)d_out + keep * 96, 0, (n_out - keep) * 96, g.stream));
-    return tm_end();
+    return wait_timed();
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_poly_trimmed_len_dev(gh_field_t field, const void* d, size_t n, size_t* len) try {
@@ -453,7 +423,7 @@ static int axpy_api(gh_field_t field, int op, const void* d_a, size_t n_a, const
     const bool given = (d_a || !n_a) && (d_b || !n_b) && (d_out || !(n_a | n_b)) && (op != POLY_ADD_SCALED || f12);
     if (int rc = prologue(field, given, n_a | n_b)) return rc;
     if (int rc = ensure_init()) return rc;
-    return POLY_DISPATCH(field, axpy_run, op, d_a, n_a, d_b, n_b, f12, d_out);
+    return GH_FIELD_DISPATCH(field, axpy_run, op, d_a, n_a, d_b, n_b, f12, d_out);
 }
 int gh_poly_add_dev(gh_field_t field, const void* d_a, size_t n_a, const void* d_b, size_t n_b, void* d_out) try {
     return axpy_api(field, POLY_ADD, d_a, n_a, d_b, n_b, nullptr, d_out);
@@ -473,7 +443,7 @@ int gh_poly_mul_by_vanishing_dev(gh_field_t field, const void* d_in, size_t n, u
     if (int rc = prologue(field, (d_in || !n) && d_out, n)) return rc;
     if (int rc = domain_ok(field, log_n)) return rc;
     if (int rc = ensure_init()) return rc;
-    return POLY_DISPATCH(field, mul_vanishing_run, d_in, n, log_n, d_out);
+    return GH_FIELD_DISPATCH(field, mul_vanishing_run, d_in, n, log_n, d_out);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_poly_divide_by_vanishing_dev(gh_field_t field, const void* d_in, size_t n, uint32_t log_n, void* d_q, void* d_r) try {
@@ -482,7 +452,7 @@ int gh_poly_divide_by_vanishing_dev(gh_field_t field, const void* d_in, size_t n
     if (int rc = prologue(field, (d_in || !n) && d_r && (d_q || !has_q), n)) return rc;
     if (int rc = domain_ok(field, log_n)) return rc;
     if (int rc = ensure_init()) return rc;
-    return POLY_DISPATCH(field, divide_vanishing_run, d_in, n, log_n, d_q, d_r);
+    return GH_FIELD_DISPATCH(field, divide_vanishing_run, d_in, n, log_n, d_q, d_r);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_poly_divide_by_vanishing(gh_field_t field, const uint64_t* in, size_t n, uint32_t log_n, uint64_t* q, uint64_t* r) try {
@@ -495,7 +465,7 @@ int gh_poly_divide_by_vanishing(gh_field_t field, const uint64_t* in, size_t n, 
     DevMem d_in, d_q, d_r;
     int rc;
     if ((rc = up(d_in, in, n)) || (rc = d_q.alloc(std::max(nq, (size_t)1) * 96)) || (rc = d_r.alloc(N * 96))) return rc;
-    if ((rc = POLY_DISPATCH(field, divide_vanishing_run, d_in.get(), n, log_n, d_q.get(), d_r.get()))) return rc;
+    if ((rc = GH_FIELD_DISPATCH(field, divide_vanishing_run, d_in.get(), n, log_n, d_q.get(), d_r.get()))) return rc;
     if ((rc = down(q, d_q, nq))) return rc;
     return down(r, d_r, N);
 } catch (...) { return gh_rt::api_exception(); }
@@ -504,7 +474,7 @@ int gh_poly_divide_by_linear_dev(gh_field_t field, const void* d_in, size_t n, c
     std::lock_guard<std::mutex> lk(api_mutex());
     if (int rc = prologue(field, (d_in || !n) && z12 && rem12 && (d_q || n < 2), n)) return rc;
     if (int rc = ensure_init()) return rc;
-    return POLY_DISPATCH(field, divide_linear_run, d_in, n, z12, d_q, rem12);
+    return GH_FIELD_DISPATCH(field, divide_linear_run, d_in, n, z12, d_q, rem12);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_poly_divide_by_linear(gh_field_t field, const uint64_t* in, size_t n, const uint64_t* z12, uint64_t* q, uint64_t* rem12) try {
@@ -515,7 +485,7 @@ int gh_poly_divide_by_linear(gh_field_t field, const uint64_t* in, size_t n, con
     DevMem d_in, d_q;
     int rc;
     if ((rc = up(d_in, in, n)) || (rc = d_q.alloc(std::max(nq, (size_t)1) * 96))) return rc;
-    if ((rc = POLY_DISPATCH(field, divide_linear_run, d_in.get(), n, z12, d_q.get(), rem12))) return rc;
+    if ((rc = GH_FIELD_DISPATCH(field, divide_linear_run, d_in.get(), n, z12, d_q.get(), rem12))) return rc;
     return down(q, d_q, nq);
 } catch (...) { return gh_rt::api_exception(); }
 
@@ -549,7 +519,7 @@ int gh_domain_elements_dev(gh_field_t field, uint32_t log_n, void* d_out) try {
     if (int rc = prologue(field, d_out != nullptr, 0)) return rc;
     if (int rc = domain_ok(field, log_n)) return rc;
     if (int rc = ensure_init()) return rc;
-    return POLY_DISPATCH(field, elements_run, field, log_n, d_out);
+    return GH_FIELD_DISPATCH(field, elements_run, field, log_n, d_out);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_poly_sparse_evaluate_over_domain_dev(gh_field_t field, const uint64_t* exps, const uint64_t* coeffs12, size_t t, uint32_t log_n, void* d_out) try {
@@ -557,7 +527,7 @@ int gh_poly_sparse_evaluate_over_domain_dev(gh_field_t field, const uint64_t* ex
     if (int rc = prologue(field, ((exps && coeffs12) || !t) && d_out, t)) return rc;
     if (int rc = domain_ok(field, log_n)) return rc;
     if (int rc = ensure_init()) return rc;
-    return POLY_DISPATCH(field, sparse_run, field, exps, coeffs12, t, log_n, d_out);
+    return GH_FIELD_DISPATCH(field, sparse_run, field, exps, coeffs12, t, log_n, d_out);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_poly_set_tuning(uint32_t run_len, uint32_t direct_max, uint32_t seg_max) try {
@@ -571,7 +541,7 @@ int gh_poly_set_tuning(uint32_t run_len, uint32_t direct_max, uint32_t seg_max) 
 
 int gh_poly_last_timing(float* ms) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if (ms) *ms = g_ms;
+    if (ms) *ms = g_tm.ms[0];
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
 

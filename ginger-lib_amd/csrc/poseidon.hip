@@ -13,13 +13,9 @@
 #include <chrono>
 #include <thread>
 #include <vector>
-#include "runtime.h"
+#include "unit_host.h"
 #include "poseidon_perm.h"
 #include "../../include/ginger_hip_poseidon.h"
-
-using namespace gh;
-using gh_rt::g;
-using gh_rt::g_err;
 
 struct gh_poseidon {
     uint32_t magic = 0x706f7364u;
@@ -43,6 +39,7 @@ int g_k = 0;                          // states per lane, 0 = auto
 size_t g_tail = TAIL_DEFAULT;
 std::vector<float> g_level_ms;
 float g_total_ms = 0;
+PhaseTimer g_level_tm;                // the bracket around one device level of a tree
 
 constexpr int BLOCK = 64;
 
@@ -197,16 +194,6 @@ void host_hash2(const gh_poseidon* h, const uint64_t* a, const uint64_t* b, uint
     else host_hash2_t<P4>(h, a, b, out);
 }
 
-template <class P> bool below_modulus(const uint64_t* x) {
-    static const uint64_t p4[12] = GH_P4_P_64, p6[12] = GH_P6_P_64;
-    const uint64_t* p = std::is_same<P, P6>::value ? p6 : p4;
-    for (int i = 11; i >= 0; i--)
-        if (x[i] != p[i]) return x[i] < p[i];
-    return false;
-}
-
-template <class P> Fp to_internal(const uint64_t* x) { return fp_from_abi<P>((const uint32_t*)x); }
-
 // device constants and evaluate([1]), once per handle; API lock held
 int prepare(gh_poseidon* h) {
     if (int rc = gh_rt::ensure_init()) return rc;
@@ -229,8 +216,6 @@ int prepare(gh_poseidon* h) {
     }
     return GH_OK;
 }
-
-bool mul_overflows(size_t a, size_t b, size_t* r) { return __builtin_mul_overflow(a, b, r); }
 
 }  // namespace
 
@@ -256,9 +241,9 @@ extern "C" {
 int gh_poseidon_create(gh_field_t field, uint32_t r_f, uint32_t r_p, const uint64_t* round_cst, size_t n_round_cst,
                        const uint64_t* mds9, const uint64_t* c2, const uint64_t* after_zero_perm3, gh_poseidon_t* out) try {
     std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
-    if (!round_cst || !mds9 || !c2 || !after_zero_perm3 || !out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!round_cst || !mds9 || !c2 || !after_zero_perm3 || !out) return null_arg();
     *out = nullptr;
-    if (field != GH_MNT4753_FR && field != GH_MNT6753_FR) { g_err = "unknown field"; return GH_E_BAD_ARG; }
+    if (field != GH_MNT4753_FR && field != GH_MNT6753_FR) { g_err = "unknown field"; return GH_E_BAD_ARG; }   // its own wording, kept
     if (r_f == 0 || r_f > 1024 || r_p > 1u << 20) { g_err = "r_f must be >= 1 (and the round counts sane)"; return GH_E_BAD_ARG; }
     const size_t nrc = 3 * (2 * (size_t)r_f + r_p);
     if (n_round_cst < nrc) { g_err = "too few round constants"; return GH_E_BAD_ARG; }
@@ -267,14 +252,13 @@ int gh_poseidon_create(gh_field_t field, uint32_t r_f, uint32_t r_p, const uint6
     for (int i = 0; i < 9; i++) all.push_back(mds9 + 12 * i);
     all.push_back(c2);
     for (int i = 0; i < 3; i++) all.push_back(after_zero_perm3 + 12 * i);
-    const bool p6 = field == GH_MNT4753_FR;
     for (const uint64_t* x : all)
-        if (!(p6 ? below_modulus<P6>(x) : below_modulus<P4>(x))) { g_err = "a Poseidon constant is not below the modulus"; return GH_E_BAD_ARG; }
+        if (!GH_FIELD_DISPATCH(field, below, x)) { g_err = "a Poseidon constant is not below the modulus"; return GH_E_BAD_ARG; }
     auto* h = new gh_poseidon();
     h->field = field;
     h->r_f = (int)r_f;
     h->r_p = (int)r_p;
-    for (const uint64_t* x : all) h->host.push_back(p6 ? to_internal<P6>(x) : to_internal<P4>(x));
+    for (const uint64_t* x : all) h->host.push_back(GH_FIELD_DISPATCH(field, from_abi12, x));
     *out = h;
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
@@ -293,7 +277,7 @@ int gh_poseidon_hash_dev(gh_poseidon_t h, const void* d_in, size_t n, size_t len
     std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
     SlabTrim trim_;
     if (!valid(h)) { g_err = "not a Poseidon handle"; return GH_E_BAD_HANDLE; }
-    if (n && (!d_out || (len && !d_in))) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!d_out || (len && !d_in))) return null_arg();
     if (n == 0) return GH_OK;
     if (int rc = prepare(h)) return rc;
     if (int rc = launch(h, d_in, n, len, d_out, 0)) return rc;
@@ -305,9 +289,9 @@ int gh_poseidon_hash(gh_poseidon_t h, const uint64_t* in, size_t n, size_t len, 
     std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
     SlabTrim trim_;
     if (!valid(h)) { g_err = "not a Poseidon handle"; return GH_E_BAD_HANDLE; }
-    if (n && (!out || (len && !in))) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!out || (len && !in))) return null_arg();
     size_t nin = 0, bin = 0;
-    if (mul_overflows(n, len, &nin) || mul_overflows(nin, 96, &bin)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, len, &nin) || mul_overflows(nin, 96, &bin)) return too_large();
     if (n == 0) return GH_OK;
     if (int rc = prepare(h)) return rc;
     void *d_in = nullptr, *d_out = nullptr;
@@ -323,9 +307,9 @@ int gh_poseidon_permute(gh_poseidon_t h, uint64_t* states, size_t n) try {
     std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
     SlabTrim trim_;
     if (!valid(h)) { g_err = "not a Poseidon handle"; return GH_E_BAD_HANDLE; }
-    if (n && !states) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && !states) return null_arg();
     size_t bytes = 0;
-    if (mul_overflows(n, 3 * 96, &bytes)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, 3 * 96, &bytes)) return too_large();
     if (n == 0) return GH_OK;
     if (int rc = prepare(h)) return rc;
     void* d = nullptr;
@@ -341,7 +325,7 @@ int gh_poseidon_merkle_tree(gh_poseidon_t h, const uint64_t* leaves, size_t n_le
     std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
     SlabTrim trim_;
     if (!valid(h)) { g_err = "not a Poseidon handle"; return GH_E_BAD_HANDLE; }
-    if (!out_root || (n_leaves && !leaves)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!out_root || (n_leaves && !leaves)) return null_arg();
     if (n_leaves > ((size_t)1 << 40)) { g_err = "too many leaves"; return GH_E_BAD_ARG; }
     size_t L = 1;
     uint32_t th = 1;                                   // tree_height = log2(L) + 1
@@ -362,12 +346,11 @@ int gh_poseidon_merkle_tree(gh_poseidon_t h, const uint64_t* leaves, size_t n_le
     // device levels: m nodes at m - 1 from the 2m children at 2m - 1 (contiguous pairs: a hash batch of len 2)
     size_t m = L / 2;
     for (; m >= 1 && m > g_tail; m /= 2) {
-        HIPCHK(hipEventRecord(g.ev[0], g.stream));
-        if (int rc = launch(h, d_tree + (2 * m - 1) * 12, m, 2, d_tree + (m - 1) * 12, 0)) return rc;
-        HIPCHK(hipEventRecord(g.ev[1], g.stream));
-        HIPCHK(hipEventSynchronize(g.ev[1]));
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, g.ev[0], g.ev[1]));
+        int rc;
+        if ((rc = g_level_tm.begin().mark()) || (rc = launch(h, d_tree + (2 * m - 1) * 12, m, 2, d_tree + (m - 1) * 12, 0)) ||
+            (rc = g_level_tm.mark()) || (rc = g_level_tm.wait()) || (rc = g_level_tm.bracket(&ms)))
+            return rc;
         g_level_ms.push_back(ms);
     }
     // host levels: the top 2 (2m) - 1 nodes, from the device's level of 2m nodes
@@ -425,14 +408,12 @@ int gh_poseidon_merkle_verify(gh_poseidon_t h, const uint64_t* leaves, const uin
     std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
     SlabTrim trim_;
     if (!valid(h)) { g_err = "not a Poseidon handle"; return GH_E_BAD_HANDLE; }
-    if (n && (!leaves || !siblings || !directions || !root || !out_ok)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!leaves || !siblings || !directions || !root || !out_ok)) return null_arg();
     if (height < 2) { g_err = "a path needs height >= 2 (the reference rejects an empty path)"; return GH_E_BAD_ARG; }
     const uint32_t steps = height - 1;
     size_t nsib = 0, bsib = 0, bpairs = 0;
-    if (mul_overflows(n, steps, &nsib) || mul_overflows(nsib, 96, &bsib) || mul_overflows(n, 192, &bpairs)) {
-        g_err = "input too large";
-        return GH_E_BAD_ARG;
-    }
+    if (mul_overflows(n, steps, &nsib) || mul_overflows(nsib, 96, &bsib) || mul_overflows(n, 192, &bpairs))
+        return too_large();
     if (n == 0) return GH_OK;
     if (int rc = prepare(h)) return rc;
     uint64_t *d_cur = nullptr, *d_sib = nullptr, *d_pairs = nullptr;
@@ -467,7 +448,7 @@ int gh_poseidon_set_tuning(int states_per_lane, size_t host_tail_nodes) try {
 
 int gh_poseidon_last_timing(float* level_ms, int max_levels, float* total_ms) try {
     std::lock_guard<std::mutex> lk(gh_rt::api_mutex());
-    if ((!level_ms && max_levels > 0) || max_levels < 0) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if ((!level_ms && max_levels > 0) || max_levels < 0) return null_arg();
     const int cnt = std::min<int>(max_levels, (int)g_level_ms.size());
     for (int i = 0; i < cnt; i++) level_ms[i] = g_level_ms[i];
     if (total_ms) *total_ms = g_total_ms;

@@ -11,20 +11,16 @@
 // builder; the vectors' lengths are the handle's.
 #include <algorithm>
 #include <memory>
-#include "runtime.h"
+#include "unit_host.h"
 #include "r1cs_plan.h"
 #include "sap_rows.h"
 #include "../../include/ginger_hip_sap.h"
 
 namespace {
 
-using namespace gh;
 using gh_rt::DevMem;
-using gh_rt::g;
-using gh_rt::g_err;
 
 constexpr int BLOCK = 128;
-inline unsigned blocks(size_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 // ---------------------------------------------------------------------------------------------------- kernels
 // xs[i] = x[i] in internal form; scalars (nullable): row i - 1 = the integer x[i] itself (into_repr), i >= 1; aux (nullable):
@@ -167,52 +163,8 @@ gh_r1cs* checked(gh_r1cs_t h) {
     return h;
 }
 
-// ---- timing: one event after every launch, told apart by phase once the stream has been waited for
-struct Timing {
-    std::vector<hipEvent_t> ev;                    // grown on demand, destroyed by gh_shutdown
-    std::vector<int> phase;                        // phase of the interval that ENDS at event k (k >= 1)
-    std::vector<float> ms;
-    float total_ms = 0;
-    size_t used = 0;
-    bool registered = false;
-} g_tm;
-
-int tm_begin() {
-    g_tm.used = 0;
-    g_tm.phase.clear();
-    return GH_OK;
-}
-int tm_mark(int phase) {
-    if (g_tm.used == g_tm.ev.size()) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        g_tm.ev.push_back(e);
-        if (!g_tm.registered) {
-            g_tm.registered = true;
-            g.at_shutdown.push_back([] {
-                for (hipEvent_t e : g_tm.ev) (void)hipEventDestroy(e);
-                g_tm.ev.clear();
-                g_tm.used = 0;
-                g_tm.registered = false;
-            });
-        }
-    }
-    HIPCHK(hipEventRecord(g_tm.ev[g_tm.used++], g.stream));
-    g_tm.phase.push_back(phase);
-    return GH_OK;
-}
-// after the stream has been waited for
-int tm_finish(int n_phases) {
-    g_tm.ms.assign((size_t)n_phases, 0.f);
-    g_tm.total_ms = 0;
-    for (size_t k = 1; k < g_tm.used; k++) {
-        float d = 0;
-        HIPCHK(hipEventElapsedTime(&d, g_tm.ev[k - 1], g_tm.ev[k]));
-        g_tm.ms[(size_t)g_tm.phase[k]] += d;
-        g_tm.total_ms += d;
-    }
-    return GH_OK;
-}
+// one event after every launch, told apart by phase once the stream has been waited for (unit_host.h: labelled intervals)
+PhaseTimer g_tm;
 
 // ---- upload
 int upload_plan(const R1csPlan& p, DevPlan& d, size_t& bytes) {
@@ -249,7 +201,7 @@ template <class P> const char* check_values(size_t ni, size_t nc, const gh_r1cs_
         if (m[k].num_coeffs && !m[k].coeff_values) return "null coeff_values";
         if (m[k].num_coeffs >> 29) return "a dictionary holds 2^29 entries or more";
         for (size_t i = 0; i < m[k].num_coeffs; i++)
-            if (!r1cs_below<P>(m[k].coeff_values + 12 * i)) return "a dictionary value is not below the modulus";
+            if (!below<P>(m[k].coeff_values + 12 * i)) return "a dictionary value is not below the modulus";
     }
     *domain_ok = r1cs_domain<P>((uint64_t)nc + ni, log_n);
     return nullptr;
@@ -298,10 +250,10 @@ int get_scratch(const gh_r1cs* h, Scratch& s, size_t xs_rows = 0) {
 }
 
 template <class P> int convert(const void* d_x, size_t n, const Scratch& s, void* d_scalars, void* d_aux = nullptr, size_t aux_first = 0) {
-    if (!n) return tm_mark(0);
-    GH_LAUNCH((r1cs_convert_kernel<P>), dim3(blocks(n)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_x, n, s.xs, (uint32_t*)d_scalars,
+    if (!n) return g_tm.mark(0);
+    GH_LAUNCH((r1cs_convert_kernel<P>), dim3(blocks(n, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_x, n, s.xs, (uint32_t*)d_scalars,
               (uint32_t*)d_aux, aux_first);
-    return tm_mark(0);
+    return g_tm.mark(0);
 }
 
 // y = M x over the converted vector in s.xs
@@ -313,14 +265,14 @@ template <class P> int product(const gh_r1cs* h, int which, int tr, const Scratc
         if (lv.n_segs) {
             Fp* out = s.part + lv.partial_off;
             if (l == 0)
-                GH_LAUNCH((r1cs_level_kernel<P, true>), dim3(blocks(lv.n_segs)), dim3(BLOCK), 0, g.stream, lv.segs.as<R1csSeg>(), lv.n_segs,
+                GH_LAUNCH((r1cs_level_kernel<P, true>), dim3(blocks(lv.n_segs, BLOCK)), dim3(BLOCK), 0, g.stream, lv.segs.as<R1csSeg>(), lv.n_segs,
                           p.src.as<uint32_t>(), p.code.as<uint32_t>(), (const Fp*)s.xs, dict, out, (uint32_t*)d_y);
             else
-                GH_LAUNCH((r1cs_level_kernel<P, false>), dim3(blocks(lv.n_segs)), dim3(BLOCK), 0, g.stream, lv.segs.as<R1csSeg>(), lv.n_segs,
+                GH_LAUNCH((r1cs_level_kernel<P, false>), dim3(blocks(lv.n_segs, BLOCK)), dim3(BLOCK), 0, g.stream, lv.segs.as<R1csSeg>(), lv.n_segs,
                           (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const Fp*)(s.part + p.levels[l - 1].partial_off), dict, out,
                           (uint32_t*)d_y);
         }
-        if (int rc = tm_mark(1 + (int)l)) return rc;
+        if (int rc = g_tm.mark(1 + (int)l)) return rc;
     }
     HIPCHK(hipGetLastError());
     return GH_OK;
@@ -328,13 +280,13 @@ template <class P> int product(const gh_r1cs* h, int which, int tr, const Scratc
 
 int finish(const gh_r1cs* h) {
     HIPCHK(hipStreamSynchronize(g.stream));
-    return tm_finish(h->max_levels + 2);
+    return g_tm.finish(h->max_levels + 2);
 }
 
 template <class P> int matvec(const gh_r1cs* h, int which, int tr, const void* d_x, void* d_y) {
     Scratch s;
     int rc;
-    if ((rc = get_scratch(h, s)) || (rc = tm_begin()) || (rc = tm_mark(0))) return rc;
+    if ((rc = get_scratch(h, s)) || (rc = g_tm.begin().mark(0))) return rc;
     if ((rc = convert<P>(d_x, h->plan[which][tr].n_src, s, nullptr)) || (rc = product<P>(h, which, tr, s, d_y))) return rc;
     return finish(h);
 }
@@ -343,29 +295,29 @@ template <class P> int matvec(const gh_r1cs* h, int which, int tr, const void* d
 template <class P> int evaluate_launch(const gh_r1cs* h, const void* d_z, void* d_a, void* d_b, void* d_c, void* d_scalars) {
     Scratch s;
     int rc;
-    if ((rc = get_scratch(h, s)) || (rc = tm_begin()) || (rc = tm_mark(0))) return rc;
+    if ((rc = get_scratch(h, s)) || (rc = g_tm.begin().mark(0))) return rc;
     if ((rc = convert<P>(d_z, h->ni + h->na, s, d_scalars))) return rc;
     void* out[3] = {d_a, d_b, d_c};
     for (int k = 0; k < 3; k++)
         if ((rc = product<P>(h, k, 0, s, out[k]))) return rc;
     const size_t N = (size_t)1 << h->log_n;
-    GH_LAUNCH((r1cs_tail_kernel<P>), dim3(blocks((N - h->nc) * 3)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_z, h->nc, h->ni, N, (uint32_t*)d_a,
+    GH_LAUNCH((r1cs_tail_kernel<P>), dim3(blocks((N - h->nc) * 3, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_z, h->nc, h->ni, N, (uint32_t*)d_a,
               (uint32_t*)d_b, (uint32_t*)d_c);
     HIPCHK(hipGetLastError());
-    return tm_mark(h->max_levels + 1);
+    return g_tm.mark(h->max_levels + 1);
 }
 
 template <class P> int instance_map_launch(const gh_r1cs* h, const void* d_u, void* d_a, void* d_b, void* d_c) {
     Scratch s;
     int rc;
-    if ((rc = get_scratch(h, s)) || (rc = tm_begin()) || (rc = tm_mark(0))) return rc;
+    if ((rc = get_scratch(h, s)) || (rc = g_tm.begin().mark(0))) return rc;
     if ((rc = convert<P>(d_u, h->nc, s, nullptr))) return rc;
     void* out[3] = {d_a, d_b, d_c};
     for (int k = 0; k < 3; k++)
         if ((rc = product<P>(h, k, 1, s, out[k]))) return rc;
-    GH_LAUNCH((r1cs_add_inputs_kernel<P>), dim3(blocks(h->ni)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_u, h->nc, h->ni, (uint32_t*)d_a);
+    GH_LAUNCH((r1cs_add_inputs_kernel<P>), dim3(blocks(h->ni, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_u, h->nc, h->ni, (uint32_t*)d_a);
     HIPCHK(hipGetLastError());
-    return tm_mark(h->max_levels + 1);
+    return g_tm.mark(h->max_levels + 1);
 }
 
 // ---- GM17's R1CS -> SAP maps: the same conversion, products and marks, then one SAP kernel
@@ -397,14 +349,14 @@ int sap_rows_launch(const gh_r1cs* h, const SapShape& sh, const void* d_z, void*
     Scratch s;
     uint32_t* prod[3];
     int rc;
-    if ((rc = get_scratch(h, s)) || (rc = get_sap_products(h, prod)) || (rc = tm_begin()) || (rc = tm_mark(0))) return rc;
+    if ((rc = get_scratch(h, s)) || (rc = get_sap_products(h, prod)) || (rc = g_tm.begin().mark(0))) return rc;
     if ((rc = convert<P>(d_z, sh.nv, s, d_scalars, d_aux, sh.ni))) return rc;
     for (int k = 0; k < 3; k++)
         if ((rc = product<P>(h, k, 0, s, prod[k]))) return rc;
-    GH_LAUNCH((sap_rows_kernel<P>), dim3(blocks(sh.rows_lanes())), dim3(BLOCK), 0, g.stream, sh, (const uint32_t*)prod[0], (const uint32_t*)prod[1],
+    GH_LAUNCH((sap_rows_kernel<P>), dim3(blocks(sh.rows_lanes(), BLOCK)), dim3(BLOCK), 0, g.stream, sh, (const uint32_t*)prod[0], (const uint32_t*)prod[1],
               (const uint32_t*)prod[2], (const uint32_t*)d_z, (uint32_t*)d_a, (uint32_t*)d_c, (uint32_t*)d_scalars, (uint32_t*)d_aux, (uint32_t*)d_full);
     HIPCHK(hipGetLastError());
-    return tm_mark(h->max_levels + 1);
+    return g_tm.mark(h->max_levels + 1);
 }
 
 // r1cs_to_sap.rs:37-94, no wait: p, m, q side by side in the conversion scratch, one transposed product over each
@@ -412,38 +364,22 @@ template <class P> int sap_instance_launch(const gh_r1cs* h, const SapShape& sh,
     Scratch s;
     uint32_t* prod[3];
     int rc;
-    if ((rc = get_scratch(h, s, 3 * sh.nc)) || (rc = get_sap_products(h, prod)) || (rc = tm_begin()) || (rc = tm_mark(0))) return rc;
-    if (sh.nc) GH_LAUNCH((sap_split_kernel<P>), dim3(blocks(sh.nc)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_u, sh.nc, s.xs);
-    if ((rc = tm_mark(0))) return rc;
+    if ((rc = get_scratch(h, s, 3 * sh.nc)) || (rc = get_sap_products(h, prod)) || (rc = g_tm.begin().mark(0))) return rc;
+    if (sh.nc) GH_LAUNCH((sap_split_kernel<P>), dim3(blocks(sh.nc, BLOCK)), dim3(BLOCK), 0, g.stream, (const uint32_t*)d_u, sh.nc, s.xs);
+    if ((rc = g_tm.mark(0))) return rc;
     for (int k = 0; k < 3; k++) {
         Scratch sk = s;
         sk.xs = s.xs + (size_t)k * sh.nc;
         if ((rc = product<P>(h, k, 1, sk, prod[k]))) return rc;
     }
-    GH_LAUNCH((sap_instance_finish_kernel<P>), dim3(blocks(sh.full_rows())), dim3(BLOCK), 0, g.stream, sh, (const uint32_t*)prod[0],
+    GH_LAUNCH((sap_instance_finish_kernel<P>), dim3(blocks(sh.full_rows(), BLOCK)), dim3(BLOCK), 0, g.stream, sh, (const uint32_t*)prod[0],
               (const uint32_t*)prod[1], (const uint32_t*)prod[2], (const uint32_t*)d_u, (uint32_t*)d_a, (uint32_t*)d_c);
     HIPCHK(hipGetLastError());
-    return tm_mark(h->max_levels + 1);
+    return g_tm.mark(h->max_levels + 1);
 }
 
-int last_timing(float* phase_ms, int max_phases, float* total_ms) {
-    if ((!phase_ms && max_phases > 0) || max_phases < 0) { g_err = "null argument"; return GH_E_BAD_ARG; }
-    const int cnt = std::min(max_phases, (int)g_tm.ms.size());
-    for (int i = 0; i < cnt; i++) phase_ms[i] = g_tm.ms[(size_t)i];
-    if (total_ms) *total_ms = g_tm.total_ms;
-    return cnt;
-}
-
-#define R1CS_FIELD_DISPATCH(field, fn, ...) ((field) == GH_MNT4753_FR ? fn<P6>(__VA_ARGS__) : fn<P4>(__VA_ARGS__))
-
-int to_device(void* d, const void* hsrc, size_t bytes) {
-    if (bytes) HIPCHK(hipMemcpyAsync(d, hsrc, bytes, hipMemcpyHostToDevice, g.stream));
-    return GH_OK;
-}
-int to_host(void* hdst, const void* d, size_t bytes) {
-    if (bytes) HIPCHK(hipMemcpyAsync(hdst, d, bytes, hipMemcpyDeviceToHost, g.stream));
-    return GH_OK;
-}
+int to_device(void* d, const void* hsrc, size_t bytes) { return up((uint8_t*)d, (const uint8_t*)hsrc, bytes); }
+int to_host(void* hdst, const void* d, size_t bytes) { return down((uint8_t*)hdst, (const uint8_t*)d, bytes); }
 
 }  // namespace
 
@@ -455,9 +391,9 @@ extern "C" {
 int gh_r1cs_upload(gh_field_t field, size_t num_inputs, size_t num_aux, size_t num_constraints, const gh_r1cs_matrix_t* m,
                    uint32_t segment_terms, gh_r1cs_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if (!m || !out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!m || !out) return null_arg();
     *out = nullptr;
-    if (field != GH_MNT4753_FR && field != GH_MNT6753_FR) { g_err = "unknown field id"; return GH_E_BAD_ARG; }
+    if (int rc = field_ok(field)) return rc;
     if (num_inputs == 0) { g_err = "num_inputs is 0: variable 0 is the constant one"; return GH_E_BAD_ARG; }
     if (segment_terms == 1) { g_err = "segment_terms must be 0 or at least 2"; return GH_E_BAD_ARG; }
     size_t nv;
@@ -472,7 +408,7 @@ int gh_r1cs_upload(gh_field_t field, size_t num_inputs, size_t num_aux, size_t n
         }
     uint32_t log_n = 0;
     bool domain_ok = false;
-    if (const char* why = R1CS_FIELD_DISPATCH(field, check_values, num_inputs, num_constraints, m, &log_n, &domain_ok)) {
+    if (const char* why = GH_FIELD_DISPATCH(field, check_values, num_inputs, num_constraints, m, &log_n, &domain_ok)) {
         g_err = why;
         return GH_E_BAD_ARG;
     }
@@ -485,7 +421,7 @@ int gh_r1cs_upload(gh_field_t field, size_t num_inputs, size_t num_aux, size_t n
     h->nc = num_constraints;
     h->log_n = log_n;
     h->segment = segment_terms ? segment_terms : R1CS_DEFAULT_SEGMENT;
-    if (int rc = R1CS_FIELD_DISPATCH(field, build, h.get(), m)) return rc;
+    if (int rc = GH_FIELD_DISPATCH(field, build, h.get(), m)) return rc;
     *out = h.release();
     return GH_OK;
 } catch (...) { return gh_rt::api_exception(); }
@@ -504,7 +440,7 @@ int gh_r1cs_info(gh_r1cs_t handle, gh_r1cs_info_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!out) return null_arg();
     memset(out, 0, sizeof *out);
     out->num_inputs = h->ni;
     out->num_aux = h->na;
@@ -528,18 +464,18 @@ int gh_r1cs_matvec_dev(gh_r1cs_t handle, int which, int transpose, const void* d
     if (!h) return GH_E_BAD_HANDLE;
     if (which < 0 || which > 2) { g_err = "which must be 0 (A), 1 (B) or 2 (C)"; return GH_E_BAD_ARG; }
     const DevPlan& p = h->plan[which][transpose ? 1 : 0];
-    if ((p.n_src && !d_x) || (p.rows && !d_y)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if ((p.n_src && !d_x) || (p.rows && !d_y)) return null_arg();
     if (int rc = ensure_init()) return rc;
-    return R1CS_FIELD_DISPATCH(h->field, matvec, h, which, transpose ? 1 : 0, d_x, d_y);
+    return GH_FIELD_DISPATCH(h->field, matvec, h, which, transpose ? 1 : 0, d_x, d_y);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_r1cs_evaluate_dev(gh_r1cs_t handle, const void* d_assignment, void* d_a, void* d_b, void* d_c) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!d_assignment || !d_a || !d_b || !d_c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!d_assignment || !d_a || !d_b || !d_c) return null_arg();
     if (int rc = ensure_init()) return rc;
-    if (int rc = R1CS_FIELD_DISPATCH(h->field, evaluate_launch, h, d_assignment, d_a, d_b, d_c, nullptr)) return rc;
+    if (int rc = GH_FIELD_DISPATCH(h->field, evaluate_launch, h, d_assignment, d_a, d_b, d_c, nullptr)) return rc;
     return finish(h);
 } catch (...) { return gh_rt::api_exception(); }
 
@@ -547,13 +483,13 @@ int gh_r1cs_evaluate(gh_r1cs_t handle, const uint64_t* assignment, uint64_t* a, 
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!assignment || !a || !b || !c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!assignment || !a || !b || !c) return null_arg();
     if (int rc = ensure_init()) return rc;
     const size_t zb = (h->ni + h->na) * 96, ob = ((size_t)1 << h->log_n) * 96;
     DevMem dz, da, db, dc;
     int rc;
     if ((rc = dz.alloc(zb)) || (rc = da.alloc(ob)) || (rc = db.alloc(ob)) || (rc = dc.alloc(ob)) || (rc = to_device(dz.get(), assignment, zb))) return rc;
-    if ((rc = R1CS_FIELD_DISPATCH(h->field, evaluate_launch, h, dz.get(), da.get(), db.get(), dc.get(), nullptr))) return rc;
+    if ((rc = GH_FIELD_DISPATCH(h->field, evaluate_launch, h, dz.get(), da.get(), db.get(), dc.get(), nullptr))) return rc;
     if ((rc = to_host(a, da.get(), ob)) || (rc = to_host(b, db.get(), ob)) || (rc = to_host(c, dc.get(), ob))) return rc;
     return finish(h);
 } catch (...) { return gh_rt::api_exception(); }
@@ -563,24 +499,24 @@ int gh_r1cs_witness_map_dev(gh_r1cs_t handle, const void* d_assignment, const ui
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!d_assignment || !d1 || !d2 || !d3 || !d_h) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!d_assignment || !d1 || !d2 || !d3 || !d_h) return null_arg();
     if (int rc = ensure_init()) return rc;
     const size_t ob = ((size_t)1 << h->log_n) * 96;
     void *da, *db, *dc;
     int rc;
     if ((rc = pool_get("r1cs_a", ob, &da)) || (rc = pool_get("r1cs_b", ob, &db)) || (rc = pool_get("r1cs_c", ob, &dc))) return rc;
-    if ((rc = R1CS_FIELD_DISPATCH(h->field, evaluate_launch, h, d_assignment, da, db, dc, d_scalars))) return rc;
+    if ((rc = GH_FIELD_DISPATCH(h->field, evaluate_launch, h, d_assignment, da, db, dc, d_scalars))) return rc;
     if ((rc = witness_map(h->field, da, db, dc, h->log_n, d1, d2, d3, d_h))) return rc;      // waits for the stream at its end
-    return tm_finish(h->max_levels + 2);
+    return g_tm.finish(h->max_levels + 2);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_r1cs_instance_map_dev(gh_r1cs_t handle, const void* d_u, void* d_a, void* d_b, void* d_c) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!d_u || !d_a || !d_b || !d_c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!d_u || !d_a || !d_b || !d_c) return null_arg();
     if (int rc = ensure_init()) return rc;
-    if (int rc = R1CS_FIELD_DISPATCH(h->field, instance_map_launch, h, d_u, d_a, d_b, d_c)) return rc;
+    if (int rc = GH_FIELD_DISPATCH(h->field, instance_map_launch, h, d_u, d_a, d_b, d_c)) return rc;
     return finish(h);
 } catch (...) { return gh_rt::api_exception(); }
 
@@ -588,20 +524,20 @@ int gh_r1cs_instance_map(gh_r1cs_t handle, const uint64_t* u, uint64_t* a, uint6
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!u || !a || !b || !c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!u || !a || !b || !c) return null_arg();
     if (int rc = ensure_init()) return rc;
     const size_t ub = ((size_t)1 << h->log_n) * 96, ob = (h->ni + h->na) * 96;
     DevMem du, da, db, dc;
     int rc;
     if ((rc = du.alloc(ub)) || (rc = da.alloc(ob)) || (rc = db.alloc(ob)) || (rc = dc.alloc(ob)) || (rc = to_device(du.get(), u, ub))) return rc;
-    if ((rc = R1CS_FIELD_DISPATCH(h->field, instance_map_launch, h, du.get(), da.get(), db.get(), dc.get()))) return rc;
+    if ((rc = GH_FIELD_DISPATCH(h->field, instance_map_launch, h, du.get(), da.get(), db.get(), dc.get()))) return rc;
     if ((rc = to_host(a, da.get(), ob)) || (rc = to_host(b, db.get(), ob)) || (rc = to_host(c, dc.get(), ob))) return rc;
     return finish(h);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_r1cs_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    return last_timing(phase_ms, max_phases, total_ms);
+    return g_tm.copy_out(phase_ms, max_phases, total_ms);
 } catch (...) { return gh_rt::api_exception(); }
 
 // ---- include/ginger_hip_sap.h
@@ -609,7 +545,7 @@ int gh_sap_info(gh_r1cs_t handle, gh_sap_info_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!out) return null_arg();
     SapShape sh;
     uint32_t log_n;
     if (int rc = sap_shape(h, &sh, &log_n)) return rc;
@@ -626,12 +562,12 @@ int gh_sap_rows_dev(gh_r1cs_t handle, const void* d_assignment, void* d_a, void*
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!d_assignment || !d_a || !d_c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!d_assignment || !d_a || !d_c) return null_arg();
     SapShape sh;
     uint32_t log_n;
     if (int rc = sap_shape(h, &sh, &log_n)) return rc;
     if (int rc = ensure_init()) return rc;
-    if (int rc = R1CS_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, d_assignment, d_a, d_c, d_scalars, d_aux_scalars, nullptr)) return rc;
+    if (int rc = GH_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, d_assignment, d_a, d_c, d_scalars, d_aux_scalars, nullptr)) return rc;
     return finish(h);
 } catch (...) { return gh_rt::api_exception(); }
 
@@ -639,7 +575,7 @@ int gh_sap_rows(gh_r1cs_t handle, const uint64_t* assignment, uint64_t* a, uint6
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!assignment || !a || !c || !full) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!assignment || !a || !c || !full) return null_arg();
     SapShape sh;
     uint32_t log_n;
     if (int rc = sap_shape(h, &sh, &log_n)) return rc;
@@ -649,7 +585,7 @@ int gh_sap_rows(gh_r1cs_t handle, const uint64_t* assignment, uint64_t* a, uint6
     int rc;
     if ((rc = dz.alloc(zb)) || (rc = da.alloc(ob)) || (rc = dc.alloc(ob)) || (rc = df.alloc(fb))) return rc;
     if ((rc = to_device(dz.get(), assignment, zb)) || (rc = to_device(df.get(), assignment, zb))) return rc;      // full = z || e || f
-    if ((rc = R1CS_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, dz.get(), da.get(), dc.get(), nullptr, nullptr, df.get()))) return rc;
+    if ((rc = GH_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, dz.get(), da.get(), dc.get(), nullptr, nullptr, df.get()))) return rc;
     if ((rc = to_host(a, da.get(), ob)) || (rc = to_host(c, dc.get(), ob)) || (rc = to_host(full, df.get(), fb))) return rc;
     return finish(h);
 } catch (...) { return gh_rt::api_exception(); }
@@ -659,7 +595,7 @@ int gh_sap_r1cs_witness_map_dev(gh_r1cs_t handle, const void* d_assignment, cons
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!d_assignment || !d1 || !d2 || !d_h) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!d_assignment || !d1 || !d2 || !d_h) return null_arg();
     SapShape sh;
     uint32_t log_n;
     if (int rc = sap_shape(h, &sh, &log_n)) return rc;
@@ -667,21 +603,21 @@ int gh_sap_r1cs_witness_map_dev(gh_r1cs_t handle, const void* d_assignment, cons
     void *da, *dc;
     int rc;
     if ((rc = pool_get("sap_a", sh.N * 96, &da)) || (rc = pool_get("sap_c", sh.N * 96, &dc))) return rc;
-    if ((rc = R1CS_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, d_assignment, da, dc, d_scalars, d_aux_scalars, nullptr))) return rc;
+    if ((rc = GH_FIELD_DISPATCH(h->field, sap_rows_launch, h, sh, d_assignment, da, dc, d_scalars, d_aux_scalars, nullptr))) return rc;
     if ((rc = sap_witness_map(h->field, da, dc, log_n, d1, d2, d_h))) return rc;                  // waits for the stream at its end
-    return tm_finish(h->max_levels + 2);
+    return g_tm.finish(h->max_levels + 2);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_sap_instance_map_dev(gh_r1cs_t handle, const void* d_u, void* d_a, void* d_c) try {
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!d_u || !d_a || !d_c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!d_u || !d_a || !d_c) return null_arg();
     SapShape sh;
     uint32_t log_n;
     if (int rc = sap_shape(h, &sh, &log_n)) return rc;
     if (int rc = ensure_init()) return rc;
-    if (int rc = R1CS_FIELD_DISPATCH(h->field, sap_instance_launch, h, sh, d_u, d_a, d_c)) return rc;
+    if (int rc = GH_FIELD_DISPATCH(h->field, sap_instance_launch, h, sh, d_u, d_a, d_c)) return rc;
     return finish(h);
 } catch (...) { return gh_rt::api_exception(); }
 
@@ -689,7 +625,7 @@ int gh_sap_instance_map(gh_r1cs_t handle, const uint64_t* u, uint64_t* a, uint64
     std::lock_guard<std::mutex> lk(api_mutex());
     const gh_r1cs* h = checked(handle);
     if (!h) return GH_E_BAD_HANDLE;
-    if (!u || !a || !c) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!u || !a || !c) return null_arg();
     SapShape sh;
     uint32_t log_n;
     if (int rc = sap_shape(h, &sh, &log_n)) return rc;
@@ -698,14 +634,14 @@ int gh_sap_instance_map(gh_r1cs_t handle, const uint64_t* u, uint64_t* a, uint64
     DevMem du, da, dc;
     int rc;
     if ((rc = du.alloc(ub)) || (rc = da.alloc(ob)) || (rc = dc.alloc(ob)) || (rc = to_device(du.get(), u, ub))) return rc;
-    if ((rc = R1CS_FIELD_DISPATCH(h->field, sap_instance_launch, h, sh, du.get(), da.get(), dc.get()))) return rc;
+    if ((rc = GH_FIELD_DISPATCH(h->field, sap_instance_launch, h, sh, du.get(), da.get(), dc.get()))) return rc;
     if ((rc = to_host(a, da.get(), ob)) || (rc = to_host(c, dc.get(), ob))) return rc;
     return finish(h);
 } catch (...) { return gh_rt::api_exception(); }
 
 int gh_sap_last_timing(float* phase_ms, int max_phases, float* total_ms) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    return last_timing(phase_ms, max_phases, total_ms);
+    return g_tm.copy_out(phase_ms, max_phases, total_ms);
 } catch (...) { return gh_rt::api_exception(); }
 
 }  // extern "C"

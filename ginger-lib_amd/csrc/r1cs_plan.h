@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <vector>
 #include "fp29.h"
+#include "modulus.h"
 
 namespace gh {
 
@@ -70,16 +71,9 @@ inline const char* r1cs_check_csr(uint64_t num_rows, uint64_t num_cols, const ui
     return nullptr;
 }
 
-template <class P> inline const uint64_t* r1cs_modulus() {
-    static const uint64_t p4[12] = GH_P4_P_64, p6[12] = GH_P6_P_64;
-    return std::is_same<P, P6>::value ? p6 : p4;
-}
-template <class P> inline bool r1cs_below(const uint64_t* x) {
-    const uint64_t* p = r1cs_modulus<P>();
-    for (int i = 11; i >= 0; i--)
-        if (x[i] != p[i]) return x[i] < p[i];
-    return false;
-}
+// modulus.h under the names the host checks of this header use
+template <class P> inline const uint64_t* r1cs_modulus() { return modulus64<P>(); }
+template <class P> inline bool r1cs_below(const uint64_t* x) { return below<P>(x); }
 
 // log2 of the QAP domain of EvaluationDomain::new(num_coeffs) (domain.rs:65-72); false where it would be None
 template <class P> inline bool r1cs_domain(uint64_t num_coeffs, uint32_t* log_n) {

@@ -55,7 +55,6 @@ struct Ctx {
     hipStream_t stream_acc2 = nullptr;  // second half of a split affine round (msm_impl.h issue_round): same priority as stream_acc
     hipStream_t stream_acc_alt = nullptr;   // the accumulations of the odd jobs of a G1 batch (msm_impl.h msm_batch); null under GH_ACC_ALT=0
     hipEvent_t tev[2] = {nullptr, nullptr};   // fork / join of a split round
-    hipEvent_t ev[10];
     hipEvent_t pev[4][8];               // MSM stage events, one set per job in flight (job k of a batch uses set k & 3)
     std::map<int, Domain> domains[2];
     std::map<std::string, DevBuf> pool;
@@ -169,6 +168,8 @@ template <> struct CurveId<gh::Mnt6G2> { static constexpr gh_curve_t id = GH_MNT
 inline int unknown_curve() { g_err = "unknown curve id"; return GH_E_BAD_ARG; }
 // fn<C>(args) for the curve policy C of a curve id: the two G1 curves (Schnorr, EC-VRF: the caller has checked is_g1), or all four
 #define GH_G1_DISPATCH(curve, fn, ...) ((curve) == GH_MNT6753_G1 ? fn<gh::Mnt6G1>(__VA_ARGS__) : fn<gh::Mnt4G1>(__VA_ARGS__))
+// fn<P>(args) for the field policy P of a field id; the caller has checked the id (unit_host.h field_ok)
+#define GH_FIELD_DISPATCH(field, fn, ...) ((field) == GH_MNT4753_FR ? fn<gh::P6>(__VA_ARGS__) : fn<gh::P4>(__VA_ARGS__))
 #define GH_CURVE_DISPATCH(curve, fn, ...)                          \
     ((curve) == GH_MNT4753_G1   ? fn<gh::Mnt4G1>(__VA_ARGS__)       \
      : (curve) == GH_MNT4753_G2 ? fn<gh::Mnt4G2>(__VA_ARGS__)       \
@@ -251,9 +252,8 @@ int poseidon_field(const gh_poseidon* h, gh_field_t* out);                      
 int poseidon_hash_dev_locked(gh_poseidon* h, const void* d_in, size_t n, size_t len, void* d_out);   // on g.stream, no sync
 void poseidon_trim_slab();                         // the release of a large slab every Poseidon entry point does on return
 // points.hip, on g.stream, no sync: d_code[i * stride] = the GH_POINT_* code of point i (membership: 0, 3 or 4; decompression: 0 .. 4,
-// d_xy / d_inf the points, failed rows zero).  points_validate_mark(0 / 1) brackets such launches with the two events
-// no Phases uses for a mark-to-mark time (g.ev[8], g.ev[9]); points_validate_finish(), after the caller's stream synchronise and before
-// anything else records an event, makes their distance the validate phase of gh_points_last_timing.
+// d_xy / d_inf the points, failed rows zero).  points_validate_mark(0 / 1) brackets such launches on the points unit's own timer;
+// points_validate_finish(), after the caller's stream synchronise, makes their distance the validate phase of gh_points_last_timing.
 int points_member_dev(gh_curve_t curve, const void* d_xy, const uint8_t* d_inf, size_t n, uint8_t* d_code, size_t stride);
 int points_decompress_dev(gh_curve_t curve, const void* d_x, const uint8_t* d_flags, size_t n, void* d_xy, uint8_t* d_inf, uint8_t* d_code, size_t stride);
 int points_validate_mark(int end);

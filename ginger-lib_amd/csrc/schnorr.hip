@@ -16,7 +16,7 @@ struct gh_schnorr {
 namespace {
 
 constexpr int VB_W_DEFAULT = 4;                       // the fastest of the sweep w = 4, 5, 6
-Timing g_tm{6};                                       // upload, fixed base, variable base, normalise, hash, finish
+PhaseTimer g_tm{6};                                   // upload, fixed base, variable base, normalise, hash, finish
 
 // hash rows m_0 .. m_(len-1) | R.x | R.y | pk.x: the message and pk.x (0 for the point at infinity); R comes from normalize_kernel
 __global__ void __launch_bounds__(256) rows_kernel(const uint64_t* __restrict__ msg, const uint64_t* __restrict__ pk_xy,
@@ -79,7 +79,7 @@ template <class C> int run_sign(gh_schnorr* h, const uint64_t* sk, const uint64_
     if (!rc) rc = dbuf("vb_xy", n * 24, &d_sig);
     if (!rc) rc = dbuf("vb_st", n, &d_st);
     if (rc) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_sk, sk, n * 12)) || (rc = up(d_nonce, nonce, n * 12)) || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_pkinf, pk_inf, n)) ||
         (rc = up(d_msg, msg, n * len * 12)) || (rc = ph.mark()))
@@ -125,7 +125,7 @@ template <class C> int run_verify(gh_schnorr* h, const uint64_t* pk_xy, const ui
     if (!rc) rc = dbuf("vb_h", n * 12, &d_e);
     if (!rc) rc = dbuf("vb_st", n, &d_st);
     if (rc) return rc;
-    Phases ph{g_tm};
+    PhaseTimer& ph = g_tm.begin();
     if ((rc = ph.mark())) return rc;
     if ((rc = up(d_sig, sig, n * 24)) || (rc = up(d_pk, pk_xy, n * 24)) || (rc = up(d_pkinf, pk_inf, n)) || (rc = up(d_msg, msg, n * len * 12)) ||
         (rc = ph.mark()))
@@ -158,14 +158,12 @@ template <class C> int run_batch_mul(const uint64_t* xy, const uint8_t* inf, con
     if (!rc) rc = dbuf("vb_rows", n * 36, &d_out);
     if (!rc && inf) rc = dbuf("vb_pkinf", n, &d_inf);
     if (rc || (rc = up(d_xy, xy, n * 24)) || (rc = up((uint64_t*)d_k, scalars, n * 12)) || (inf && (rc = up(d_inf, inf, n)))) return rc;
-    HIPCHK(hipEventRecord(g.ev[0], g.stream));
-    if ((rc = vb_launch<C>(d_xy, d_inf, d_k, n, 0, d_p))) return rc;
-    HIPCHK(hipEventRecord(g.ev[1], g.stream));
+    if ((rc = g_tm.begin().mark()) || (rc = vb_launch<C>(d_xy, d_inf, d_k, n, 0, d_p)) || (rc = g_tm.mark())) return rc;
     GH_LAUNCH((proj_to_abi_kernel<C>), dim3(blocks(n, 256)), dim3(256), 0, g.stream, (const Proj<C>*)d_p, n, (uint32_t*)d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_xyz, d_out, n * 288, hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
-    return g_tm.single(2, g.ev[0], g.ev[1]);                         // the variable-base phase: the two kernels
+    return g_tm.single(2);                                             // the variable-base phase: the two kernels
 }
 
 int checked_handle(gh_schnorr* h) {
@@ -182,7 +180,7 @@ extern "C" {
 
 int gh_schnorr_create(gh_curve_t curve, gh_poseidon_t hash, int window, gh_schnorr_t* out) try {
     std::lock_guard<std::mutex> lk(api_mutex());
-    if (!hash || !out) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (!hash || !out) return null_arg();
     *out = nullptr;
     if (int rc = check_create("Schnorr", curve, hash, window)) return rc;
     auto* h = new gh_schnorr();
@@ -215,7 +213,7 @@ int gh_schnorr_sign(gh_schnorr_t h, const uint64_t* sk, const uint64_t* pk_xy, c
     std::lock_guard<std::mutex> lk(api_mutex());
     Trim trim_;
     if (int rc = checked_handle(h)) return rc;
-    if (n && (!sk || !pk_xy || !pk_inf || (len && !msg) || !nonce || !out_sig || !out_status)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!sk || !pk_xy || !pk_inf || (len && !msg) || !nonce || !out_sig || !out_status)) return null_arg();
     if (int rc = GH_G1_DISPATCH(h->curve, check_rows, pk_xy, len ? msg : nullptr, n, len)) return rc;
     if (!GH_G1_DISPATCH(h->curve, scalar_below, sk, n) || !GH_G1_DISPATCH(h->curve, scalar_below, nonce, n)) {
         g_err = "a secret key or nonce is not below the modulus";
@@ -231,7 +229,7 @@ int gh_schnorr_verify(gh_schnorr_t h, const uint64_t* pk_xy, const uint8_t* pk_i
     std::lock_guard<std::mutex> lk(api_mutex());
     Trim trim_;
     if (int rc = checked_handle(h)) return rc;
-    if (n && (!pk_xy || !pk_inf || (len && !msg) || !sig || !out_status)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!pk_xy || !pk_inf || (len && !msg) || !sig || !out_status)) return null_arg();
     if (int rc = GH_G1_DISPATCH(h->curve, check_rows, pk_xy, len ? msg : nullptr, n, len)) return rc;
     if (!GH_G1_DISPATCH(h->curve, data_below, sig, 2 * n)) { g_err = "a signature element is not below the modulus"; return GH_E_BAD_ARG; }
     if (n == 0) return GH_OK;

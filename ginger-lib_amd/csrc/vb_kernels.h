@@ -1,6 +1,6 @@
-// vb_kernels.h -- the per-row variable-base kernels, the pipeline kernels and the host steps that schnorr.hip and ecvrf.hip
-// share (DESIGN.md sections 12 and 13).  Everything sits in an anonymous namespace: every unit that includes this header
-// gets its own instances of the kernels.
+// vb_kernels.h -- the per-row variable-base kernels and their launches, the pipeline kernels and the pipeline steps that
+// schnorr.hip and ecvrf.hip share (DESIGN.md sections 12 and 13), on the host layer of unit_host.h.  Everything sits in an
+// anonymous namespace: every unit that includes this header gets its own instances of the kernels.
 //
 // Variable base, one lane per row (out[i] = k_i P_i, a different P_i per row):
 //   vb_table_kernel   the odd multiples (2 j + 1) P_i, j < 2^(W-1), by one doubling and 2^(W-1) - 1 projective additions, then
@@ -11,18 +11,11 @@
 //                     for every row, digits read straight from the scalar's bits, one final correction for an even scalar.
 //                     Only the exceptional cases inside the mixed addition (P = +-Q, an accumulator at infinity) diverge.
 #pragma once
-#include <string.h>
-#include <algorithm>
-#include <chrono>
-#include "runtime.h"
+#include "unit_host.h"
 #include "msm_kernels.h"
 #include "schnorr_recode.h"
 
 namespace {
-
-using namespace gh;
-using gh_rt::g;
-using gh_rt::g_err;
 
 constexpr int BLOCK = 64;
 
@@ -259,51 +252,6 @@ __global__ void __launch_bounds__(256) on_curve_kernel(const uint32_t* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-inline unsigned blocks(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
-template <class P> bool below(const uint64_t* x) {
-    static const uint64_t p4[12] = GH_P4_P_64, p6[12] = GH_P6_P_64;
-    const uint64_t* p = std::is_same<P, P6>::value ? p6 : p4;
-    for (int i = 11; i >= 0; i--)
-        if (x[i] != p[i]) return x[i] < p[i];
-    return false;
-}
-template <class P> bool all_below(const uint64_t* x, size_t count) {
-    for (size_t i = 0; i < count; i++)
-        if (!below<P>(x + 12 * i)) return false;
-    return true;
-}
-bool mul_overflows(size_t a, size_t b, size_t* r) { return __builtin_mul_overflow(a, b, r); }
-
-// the curve's types: C the group, PF its base (= data) field, PS its scalar field; field: the hash's field id
-template <class C> struct Scheme;
-template <> struct Scheme<Mnt6G1> { typedef P6 PF; typedef P4 PS; static constexpr gh_field_t field = GH_MNT4753_FR; };
-template <> struct Scheme<Mnt4G1> { typedef P4 PF; typedef P6 PS; static constexpr gh_field_t field = GH_MNT6753_FR; };
-inline bool is_g1(gh_curve_t c) { return c == GH_MNT6753_G1 || c == GH_MNT4753_G1; }
-template <class C> bool data_below(const uint64_t* x, size_t count) { return all_below<typename Scheme<C>::PF>(x, count); }
-template <class C> bool scalar_below(const uint64_t* x, size_t count) { return all_below<typename Scheme<C>::PS>(x, count); }
-
-template <class C> Fp curve_b() {
-    static const uint64_t b4[12] = GH_MNT4753_G1_B0_M_64, b6[12] = GH_MNT6753_G1_B0_M_64;
-    return fp_from_abi<typename Scheme<C>::PF>((const uint32_t*)(std::is_same<C, Mnt6G1>::value ? b6 : b4));
-}
-// y^2 == x^3 + a x + b on the host (the generators of gh_bh_create and gh_pedersen_create)
-template <class C> bool on_curve_host(const uint64_t* xy) {
-    typedef typename Scheme<C>::PF PF;
-    typedef F1<PF, true> F;
-    const Fp x = fp_from_abi<PF>((const uint32_t*)xy), y = fp_from_abi<PF>((const uint32_t*)(xy + 12));
-    const Fp rhs = F::add(F::add(F::mul(F::sqr(x), x), C::mul_by_a(x)), curve_b<C>());
-    return F::eq(F::sqr(y), rhs);
-}
-template <class C> void generator_xyz(uint64_t* g_xyz) {
-    const bool m6 = std::is_same<C, Mnt6G1>::value;
-    static const uint64_t gx4[12] = GH_MNT4753_G1_GX0_M_64, gy4[12] = GH_MNT4753_G1_GY0_M_64, one4[12] = GH_P4_R_64;
-    static const uint64_t gx6[12] = GH_MNT6753_G1_GX0_M_64, gy6[12] = GH_MNT6753_G1_GY0_M_64, one6[12] = GH_P6_R_64;
-    memcpy(g_xyz, m6 ? gx6 : gx4, 96);
-    memcpy(g_xyz + 12, m6 ? gy6 : gy4, 96);
-    memcpy(g_xyz + 24, m6 ? one6 : one4, 96);
-}
-
 // The generator's fixed-base table of a handle: the caller's window, or (window 0) gh_fixed_base_window(n), rebuilt when a
 // later call's n asks for a larger window than the table has -- a handle first used on a few rows does not keep a tiny table
 // for large batches.  The window grows with log n, so a handle rebuilds at most a few times.
@@ -329,62 +277,6 @@ struct GeneratorTable {
         gh_rt::fixed_table_destroy(table);
         table = nullptr;
         table_window = 0;
-    }
-};
-
-// A unit's timing record, what its *_last_timing reports.  Each unit has its own instance: the two report separately.
-struct Timing {
-    static constexpr int MAX_PHASES = 9;  // g.ev holds 10 events
-    int nph;
-    float ms[MAX_PHASES] = {};
-    float total_ms = 0;
-    // a call that times one phase only, between two recorded and completed events
-    int single(int phase, hipEvent_t ev0, hipEvent_t ev1) {
-        for (int i = 0; i < nph; i++) ms[i] = 0;
-        HIPCHK(hipEventElapsedTime(&ms[phase], ev0, ev1));
-        total_ms = ms[phase];
-        return GH_OK;
-    }
-    // the body of a *_last_timing: the count of phases written, or an error
-    int copy_out(float* phase_ms, int max_phases, float* total) const {
-        if ((!phase_ms && max_phases > 0) || max_phases < 0) { g_err = "null argument"; return GH_E_BAD_ARG; }
-        const int cnt = std::min(max_phases, nph);
-        for (int i = 0; i < cnt; i++) phase_ms[i] = ms[i];
-        if (total) *total = total_ms;
-        return cnt;
-    }
-};
-// the phases of an entry point on g.stream: ev[0] start, ev[k] end of phase k; finish() writes the unit's timing record
-struct Phases {
-    Timing& tm;
-    int k = 0;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    int mark() {
-        HIPCHK(hipEventRecord(g.ev[k], g.stream));
-        k++;
-        return GH_OK;
-    }
-    int finish() {
-        HIPCHK(hipEventSynchronize(g.ev[k - 1]));
-        for (int i = 0; i < tm.nph; i++) tm.ms[i] = 0;
-        for (int i = 1; i < k && i <= tm.nph; i++) HIPCHK(hipEventElapsedTime(&tm.ms[i - 1], g.ev[i - 1], g.ev[i]));
-        tm.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return GH_OK;
-    }
-};
-
-// Pooled device buffers and uploads on g.stream.  Both units draw from the one "vb_" namespace of the pool: every entry
-// point holds api_mutex() and synchronises before it returns, so the two never hold a buffer at once.  An entry point keeps a
-// Trim: when it returns, every "vb_" buffer above SLAB_KEEP_BYTES is released, and Poseidon's slab by the same rule.
-template <class T> int dbuf(const char* name, size_t count, T** out) { return gh_rt::pool_get(name, std::max<size_t>(count * sizeof(T), 64), (void**)out); }
-template <class T> int up(T* d, const T* h, size_t count) {
-    if (count) HIPCHK(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, g.stream));
-    return GH_OK;
-}
-struct Trim {
-    ~Trim() {
-        gh_rt::pool_trim("vb_", gh_rt::SLAB_KEEP_BYTES);
-        gh_rt::poseidon_trim_slab();
     }
 };
 
@@ -460,9 +352,9 @@ template <class C> int run_public_keys(GeneratorTable& gt, gh_curve_t curve, con
 }
 // the body of gh_*_public_keys after the handle check
 inline int public_keys_api(GeneratorTable& gt, gh_curve_t curve, const uint64_t* sk, size_t n, uint64_t* out_xy, uint8_t* out_inf) {
-    if (n && (!sk || !out_xy || !out_inf)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!sk || !out_xy || !out_inf)) return null_arg();
     size_t b;
-    if (mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, 1024, &b)) return too_large();
     if (!GH_G1_DISPATCH(curve, scalar_below, sk, n)) { g_err = "a secret key is not below the modulus"; return GH_E_BAD_ARG; }
     if (n == 0) return GH_OK;
     if (int rc = gh_rt::ensure_init()) return rc;
@@ -488,14 +380,14 @@ template <class C> int run_keyverify(const uint64_t* pk_xy, const uint8_t* pk_in
 // sizes and the moduli of pk and the message (msg null: none), shared by sign / verify / prove / proof_to_hash / keyverify
 template <class C> int check_rows(const uint64_t* pk_xy, const uint64_t* msg, size_t n, size_t len) {
     size_t nm = 0, b = 0;
-    if (mul_overflows(n, len, &nm) || mul_overflows(nm, 96 * 4, &b) || mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, len, &nm) || mul_overflows(nm, 96 * 4, &b) || mul_overflows(n, 1024, &b)) return too_large();
     if (!data_below<C>(pk_xy, 2 * n)) { g_err = "a public-key coordinate is not below the modulus"; return GH_E_BAD_ARG; }
     if (msg && !data_below<C>(msg, nm)) { g_err = "a message element is not below the modulus"; return GH_E_BAD_ARG; }
     return GH_OK;
 }
 // the body of gh_*_keyverify after the handle check
 inline int keyverify_api(gh_curve_t curve, const uint64_t* pk_xy, const uint8_t* pk_inf, size_t n, uint8_t* out_ok) {
-    if (n && (!pk_xy || !pk_inf || !out_ok)) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && (!pk_xy || !pk_inf || !out_ok)) return null_arg();
     if (int rc = GH_G1_DISPATCH(curve, check_rows, pk_xy, nullptr, n, 0)) return rc;
     if (n == 0) return GH_OK;
     if (int rc = gh_rt::ensure_init()) return rc;
@@ -515,9 +407,9 @@ inline int check_create(const char* scheme, gh_curve_t curve, gh_poseidon* hash,
 inline int check_batch(const char* fn, gh_curve_t curve, size_t n, bool non_null) {
     if (curve == GH_MNT4753_G2 || curve == GH_MNT6753_G2) { g_err = std::string(fn) + ": G1 curves only"; return GH_E_UNSUPPORTED; }
     if (!is_g1(curve)) { g_err = "unknown curve id"; return GH_E_BAD_ARG; }
-    if (n && !non_null) { g_err = "null argument"; return GH_E_BAD_ARG; }
+    if (n && !non_null) return null_arg();
     size_t b;
-    if (mul_overflows(n, 1024, &b)) { g_err = "input too large"; return GH_E_BAD_ARG; }
+    if (mul_overflows(n, 1024, &b)) return too_large();
     return GH_OK;
 }
 inline bool below_2_753(const uint64_t* k, size_t n) {
