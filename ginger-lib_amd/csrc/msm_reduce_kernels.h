@@ -30,7 +30,10 @@
 // coefficient of a P3 per lane of a pair / triple) says how a lane reaches its point.  The Fq3 build of
 // msm_wave_reduce_split_kernel runs it.  msm_wave_reduce_kernel (G1, a whole Proj<C> per lane) and the Fq2 build of the split
 // kernel keep the loop WRITTEN OUT, because their register allocation does not survive a shared piece: the notes above the two
-// kernels have the figures.  A change to the program has to be repeated in both.
+// kernels have the figures.  A change to the program has to be repeated in both.  tests/test_msm_host.py sees msm_schedule.h
+// only; the three copies themselves are compared on the card, build by build, with sums written down by definition
+// (tests/test_gpu_msm_reduce.py over tests/device_shim/msm_reduce.hip: every step kind and tree offset with equal operands,
+// both salts, infinite operands, all shapes of count, valid, stride and run_if).
 #pragma once
 #include "msm_kernels.h"
 
