@@ -1,6 +1,7 @@
 // A stand-alone program over ginger-lib_amd/csrc/gm17_sum.h: the GH_HD group additions of the GM17 verifier on their degenerate
-// cases, for G1 and G2 of both engines, with the group laws as the check.  Meant to be built with the host sanitizers and run
-// once on its own (no GPU, nothing loaded into another process):
+// cases, for G1 and G2 of both engines, with the group laws as the check.  Built with the host sanitizers and run once on its
+// own (no GPU, nothing loaded into another process) by tests/test_gm17_verify_host.py test_sanitized_standalone_check, through
+// tests/shim_build.py sanitized_check:
 //     g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all tests/host_shim/gm17_sum_check.cpp -o gm17_sum_check
 // Exit status 0 and "ok" on success.  Test infrastructure.
 #include <stdint.h>

@@ -1,7 +1,8 @@
 // A stand-alone program over ginger-lib_amd/csrc/unit_host.h: the argument checks and their messages, the modulus comparison at
 // its edges, the generator checks of the hash handles and PhaseTimer::copy_out.  It calls no HIP API and needs no device: the
-// paths it drives are the ones that return before a unit touches the card.  Meant to be built with the host sanitizers and run
-// once on its own (nothing loaded into another process):
+// paths it drives are the ones that return before a unit touches the card.  Built with the host sanitizers and run once on its
+// own (nothing loaded into another process) by tests/test_shim_build.py test_unit_host_check_runs_clean_under_the_sanitizers,
+// through tests/shim_build.py sanitized_check:
 //     hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         tests/host_shim/unit_host_check.cpp -o unit_host_check
 // Exit status 0 and "ok" on success.  Test infrastructure.

@@ -5,28 +5,18 @@ textbook affine sums (pyref).  Covers what the reference's bucket loop covers th
 P + (-P), sums passing through infinity, plus the list shapes of the rounds (odd sizes, empty buckets, one huge
 bucket, tails shorter than a wave, more lanes than work)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import pyref
+import shim_build
 import support as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "build", "libaff_shim.so")
-SRC = os.path.join(ROOT, "tests", "host_shim", "aff_shim.hip")
 
 
 @pytest.fixture(scope="module")
 def shim():
-    deps = [SRC] + [os.path.join(ROOT, "ginger-lib_amd", "csrc", f) for f in ("aff_kernels.h", "ec29.h", "fp29.h")]
-    if not os.path.exists(SHIM) or any(os.path.getmtime(d) > os.path.getmtime(SHIM) for d in deps):
-        os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-        subprocess.check_call(["hipcc", "-O2", "-std=c++17", "--offload-host-only", "-shared", "-fPIC", "-Wno-unused-result",
-                               "-o", SHIM, SRC])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("aff")
     vp, sz, ci, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
     lib.aff_tree_host.argtypes = [ci, vp, sz, vp, sz, vp, vp, u32, ci, u32, u32, vp, vp]
     return lib

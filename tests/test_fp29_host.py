@@ -2,25 +2,18 @@
 g++ (tests/host_shim/fp29_shim.cpp) and checked against Python integers: the exact code the HIP
 kernels run (29-bit reduced radix, Montgomery 2^754), including the ABI conversions."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
 import pyref
+import shim_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "build", "libfp29_shim.so")
 U = ctypes.c_uint32
 
 
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "fp29_shim.cpp")
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(src), os.path.getmtime(os.path.join(ROOT, "ginger-lib_amd", "csrc", "fp29.h")), os.path.getmtime(os.path.join(ROOT, "ginger-lib_amd", "csrc", "ec29.h"))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    return ctypes.CDLL(SHIM)
+    return shim_build.host_shim("fp29")
 
 
 def words(x, n=24):

@@ -9,7 +9,6 @@ fp_is_zero_or_p, xyzz_madd_lazy with its init and exit conversions) compiled for
 import ctypes
 import os
 import random
-import subprocess
 import sys
 
 import numpy as np
@@ -19,30 +18,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ginger-lib_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pyref                                                      # noqa: E402
+import shim_build                                                 # noqa: E402
 import test_asmgen_acc_persist as TP                              # noqa: E402
 import test_asmgen_lazy as TL                                     # noqa: E402  (its operand sets and simulator harness)
 from asmgen import g1_xyzz                                        # noqa: E402
 from asmgen.field import LB, LM, NL, limbs, runv, unlimbs         # noqa: E402
 
-SRC = os.path.join(ROOT, "tests", "host_shim", "fp29_lazy_shim.cpp")
-HDRS = [os.path.join(ROOT, "ginger-lib_amd", "csrc", f) for f in ("fp29.h", "ec29.h", "constants_gen.h")]
-SHIM = os.path.join(ROOT, "build", "libfp29_lazy_shim.so")
 SAN = os.path.join(ROOT, "build", "fp29_lazy_san")
 U = ctypes.c_uint32
 R, RD, EPS = TL.R, TL.RD, TL.EPS
 FIELDS = [(4, "p4", "mnt4753_g1"), (6, "p6", "mnt6753_g1")]
 
 
-def _stale(out):
-    return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in [SRC] + HDRS)
-
-
 @pytest.fixture(scope="module")
 def shim():
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if _stale(SHIM):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, SRC])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("fp29_lazy")
     lib.t_lazy_split.restype = ctypes.c_uint64
     return lib
 
@@ -142,10 +132,6 @@ def test_lazy_update_against_the_group_law_and_the_generated_kernel(shim, fid, t
 def test_the_same_source_runs_clean_under_the_sanitizers():
     """a stand-alone program (its own main) built with -fsanitize=address,undefined: operands at the kernel's bounds and a chain of
     60 updates per prime against the fully reduced xyzz_madd"""
-    os.makedirs(os.path.dirname(SAN), exist_ok=True)
-    if _stale(SAN):
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-DFP29_LAZY_MAIN", "-o", SAN, SRC])
-    out = subprocess.run([SAN], capture_output=True, text=True, timeout=120)
+    out = shim_build.sanitized_check("fp29_lazy_shim.cpp", SAN, defines=("FP29_LAZY_MAIN",))
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.split() == ["mnt4753:", "ok", "mnt6753:", "ok"] and "runtime error" not in out.stderr

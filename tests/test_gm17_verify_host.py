@@ -15,9 +15,9 @@ import pytest
 import gm17_verify_ref as R
 import pairing_ref
 import pyref
+import shim_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "build", "libgm17_shim.so")
 GH_E_BAD_ARG, GH_E_NO_DEVICE = -1, -3
 V = ctypes.c_void_p
 
@@ -36,13 +36,7 @@ def edge(pr):
 
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "gm17_shim.cpp")
-    deps = [src] + [os.path.join(ROOT, "ginger-lib_amd", "csrc", f)
-                    for f in ("fp29.h", "ec29.h", "pairing29.h", "pairing29_mnt6.h", "gm17_sum.h", "pairing_constants_gen.h", "constants_gen.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("gm17")
     I = ctypes.c_int
     lib.t_gm17_sum_g1.argtypes = lib.t_gm17_sum_g2.argtypes = [I, V, I, V, I, V, V]
     lib.t_gm17_row.argtypes = [I, V, V, V, V, V, V, I, V, I, V, I, V, I, ctypes.POINTER(I)]
@@ -110,6 +104,12 @@ def test_shim_verdict_equals_the_closed_form(shim, pr, edge):
         bits.append((bool(t.value & 1), bool(t.value & 2)))
     assert got == edge["expected"]
     assert bits == edge["tests"]                                     # which of the two tests fails, row by row
+
+
+def test_sanitized_standalone_check(tmp_path):
+    """the same additions on their degenerate cases as a program of its own under the host sanitizers (gm17_sum_check.cpp)"""
+    out = shim_build.sanitized_check("gm17_sum_check.cpp", str(tmp_path / "gm17_sum_check"))
+    assert out.returncode == 0 and (out.stdout + out.stderr).strip().endswith("ok"), (out.stdout + out.stderr)[-2000:]
 
 
 # ---- 3. the C ABI without a device

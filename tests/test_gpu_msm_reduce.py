@@ -31,8 +31,7 @@ import ctypes
 import functools
 import os
 import random
-import subprocess
-import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
@@ -40,12 +39,8 @@ import pytest
 import asm_card
 import msm_reduce_ref as R
 import pyref
-from __graft_entry__ import HIPCC_FLAGS
+import shim_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ginger-lib_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "device_shim", "msm_reduce.hip")
-HOST_SHIM = os.path.join(ROOT, "build", "libmsm_host_shim.so")
 vp, u32, u64, cint = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
 FILL = R.FILL
 ITEM, WACC, TREE_WACC, SCAN, TREE_RUN = R.ITEM, R.WACC, R.TREE_WACC, R.SCAN, R.TREE_RUN
@@ -61,7 +56,7 @@ BASE_T = 0x5EED5EED5EED5EED5EED5EED7          # the base point of every set but 
 
 
 def so_path(cid):
-    return os.path.join(ROOT, "build", "libmsm_reduce_%d.so" % cid)
+    return os.path.join(shim_build.BUILD, "libmsm_reduce_%d.so" % cid)
 
 
 def counts_of(tpw, L):
@@ -71,12 +66,7 @@ def counts_of(tpw, L):
 # ------------------------------------------------------------------ the host shim (msm_schedule.h, msm_fold.h with g++)
 @functools.lru_cache(maxsize=None)
 def host_shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "msm_host_shim.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("msm_plan.h", "msm_fold.h", "msm_schedule.h", "host_math.h", "ec29.h", "fp29.h")]
-    os.makedirs(os.path.dirname(HOST_SHIM), exist_ok=True)
-    if not os.path.exists(HOST_SHIM) or os.path.getmtime(HOST_SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", HOST_SHIM, src])
-    lib = ctypes.CDLL(HOST_SHIM)
+    lib = shim_build.host_shim("msm_host")
     lib.t_wave_step.argtypes = [u32] + [cint] * 3 + [ctypes.POINTER(cint)]
     lib.t_wave_step_active.argtypes = [cint] * 5
     lib.t_fold.argtypes = [cint, cint, ctypes.POINTER(u64)] + [cint] * 6 + [ctypes.POINTER(u64)]
@@ -412,18 +402,9 @@ def set_case(s, tpw, rnd):
 def build_shim():
     """build/libmsm_reduce_<k>.so, k = 0 .. 3, from the shipped headers with the product's compiler flags, side by side; rebuilt
     when a source is newer.  -> {curve name: seconds} of what was compiled"""
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("msm_kernels.h", "msm_reduce_kernels.h", "msm_plan.h", "msm_schedule.h",
-                                                    "aff_kernels.h", "ec29.h", "fp29.h")]
-    newest = max(os.path.getmtime(d) for d in deps)
-    todo = [k for k in range(4) if not os.path.exists(so_path(k)) or os.path.getmtime(so_path(k)) < newest]
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    t0 = time.time()
-    procs = [(k, subprocess.Popen(["hipcc"] + HIPCC_FLAGS + ["-DRD_CURVE=%d" % k, "-shared", SRC, "-o", so_path(k)])) for k in todo]
-    took = {}
-    for k, p in procs:
-        assert p.wait() == 0, "hipcc failed on curve %d" % k
-        took[R.CURVE_NAMES[k]] = time.time() - t0
-    return took
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        took = list(ex.map(lambda k: shim_build.device_shim("msm_reduce.hip", so_path(k), ["-DRD_CURVE=%d" % k]), range(4)))
+    return {R.CURVE_NAMES[k]: t for k, t in enumerate(took) if t}
 
 
 LAUNCHERS = {
@@ -584,7 +565,7 @@ def test_shim_cross_compiles_for_gfx950():
         for s in kernels + names[k] + tuple(LAUNCHERS) + ("rd_sizeof",):
             assert s.encode() in blob, (k, s)
     # the lane-group fields the shim names are the ones msm_impl.h chooses, and the launch shapes are the ones it uses
-    impl = open(os.path.join(CSRC, "msm_impl.h")).read()
+    impl = open(os.path.join(shim_build.CSRC, "msm_impl.h")).read()
     assert "typename std::conditional<C::F::DEG == 2, F2S<P4, 13>, F3S<P6, 11>>::type" in impl
     assert "msm_wave_reduce_split_kernel<C, FS, FS::LANES, DEG == 2 ? 32 : 16>), dim3(grid), dim3(64), 64 * sizeof(P3)" in impl
     assert "msm_wave_reduce_kernel<C, 1>), dim3(grid), dim3(64), 64 * sizeof(Proj<C>)" in impl

@@ -13,10 +13,7 @@ the group, the weighted bucket sums of every layout and window size must give su
 hold the rows they exist for."""
 import ctypes
 import functools
-import os
 import random
-import subprocess
-import time
 
 import numpy as np
 import pytest
@@ -24,13 +21,9 @@ import pytest
 import asm_card
 import msm_sort_ref as R
 import pyref
-from __graft_entry__ import HIPCC_FLAGS
+import shim_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ginger-lib_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "device_shim", "msm_stages.hip")
-SO = os.path.join(ROOT, "build", "libmsm_stages.so")
-HOST_SHIM = os.path.join(ROOT, "build", "libmsm_host_shim.so")
+SO = shim_build.BUILD + "/libmsm_stages.so"
 KERNELS = ("msm_digits_kernel", "msm_scatter_kernel", "msm_part_hist_kernel", "msm_part_scatter_kernel", "msm_bin_sort_kernel",
            "msm_size_hist_kernel", "msm_size_scatter_kernel", "msm_heavy_plan_kernel", "msm_acc_tasks_kernel", "msm_base_hash_kernel",
            "msm_dup_verify_kernel", "msm_merge_scalars_kernel", "msm_merge_groups_kernel", "scan_partials_kernel",
@@ -67,12 +60,7 @@ MERGE_GROUPS = (1, 2, 255, 256, 257, 4096, 4097, 8193)
 # ------------------------------------------------------------------ the plans (msm_plan.h through the host shim)
 @functools.lru_cache(maxsize=None)
 def host_shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "msm_host_shim.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("msm_plan.h", "msm_fold.h", "msm_schedule.h", "host_math.h", "ec29.h", "fp29.h")]
-    os.makedirs(os.path.dirname(HOST_SHIM), exist_ok=True)
-    if not os.path.exists(HOST_SHIM) or os.path.getmtime(HOST_SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", HOST_SHIM, src])
-    lib = ctypes.CDLL(HOST_SHIM)
+    lib = shim_build.host_shim("msm_host")
     lib.t_plan_msm.argtypes = [u64] + [cint] * 8 + [ctypes.POINTER(ctypes.c_int64)]
     lib.t_plan_sort.argtypes = [u64, u64, u64, ctypes.POINTER(u32)]
     return lib
@@ -203,14 +191,7 @@ def merge_case(r, seed=41):
 def build_shim():
     """build/libmsm_stages.so from the shipped headers with the product's compiler flags; rebuilt when a source is newer.
     -> seconds spent compiling (0.0: up to date)"""
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("msm_kernels.h", "scan_kernels.h", "msm_plan.h", "msm_schedule.h", "aff_kernels.h",
-                                                    "ec29.h", "fp29.h")]
-    if os.path.exists(SO) and all(os.path.getmtime(d) <= os.path.getmtime(SO) for d in deps):
-        return 0.0
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    t0 = time.time()
-    subprocess.check_call(["hipcc"] + HIPCC_FLAGS + ["-shared", SRC, "-o", SO])
-    return time.time() - t0
+    return shim_build.device_shim("msm_stages.hip", SO)
 
 
 class Bufs:

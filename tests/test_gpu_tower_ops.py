@@ -16,21 +16,16 @@ fully reduced or a limb above 29 bits fails as well.
 The CPU part (no marker) checks these identities, the operand sets and the cross-compile of the code object for gfx950."""
 import functools
 import itertools
-import os
-import subprocess
-import time
 
 import numpy as np
 import pytest
 
 import asm_card
 import pyref
+import shim_build
 import support as S
-from __graft_entry__ import HIPCC_FLAGS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "device_shim", "tower_ops.hip")
-CO = os.path.join(ROOT, "build", "tower_ops.co")
+CO = shim_build.BUILD + "/tower_ops.co"
 KERNELS = ("tower_ops_f2s", "tower_ops_f3s", "tower_ops_f1s_p4", "tower_ops_f1s_p6", "dev_inv_p4", "dev_inv_p6", "dev_inv_fq2", "dev_inv_fq3")
 
 NL, LB = 26, 29
@@ -226,13 +221,7 @@ def place(T, elems, nrows):
 def build_code_object():
     """build/tower_ops.co from the shipped headers, with the product's compiler flags; rebuilt when a source is newer.
     -> seconds spent compiling (0.0: up to date)"""
-    deps = [SRC] + [os.path.join(ROOT, "ginger-lib_amd", "csrc", f) for f in ("msm_kernels.h", "ec29.h", "fp29.h", "aff_kernels.h")]
-    if os.path.exists(CO) and all(os.path.getmtime(d) <= os.path.getmtime(CO) for d in deps):
-        return 0.0
-    os.makedirs(os.path.dirname(CO), exist_ok=True)
-    t0 = time.time()
-    subprocess.check_call(["hipcc"] + HIPCC_FLAGS + ["--genco", SRC, "-o", CO])
-    return time.time() - t0
+    return shim_build.device_shim("tower_ops.hip", CO, genco=True)
 
 
 class Device:

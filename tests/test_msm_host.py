@@ -5,28 +5,19 @@ the bucket accumulation's task decode (msm_schedule.h) against an enumeration, a
 (msm_schedule.h) run over integers against the sums the wave program promises.
 Nothing here is a recording of the code's own output."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
 import pyref
+import shim_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ginger-lib_amd", "csrc")
-SHIM = os.path.join(ROOT, "build", "libmsm_host_shim.so")
 U64 = ctypes.c_uint64
 CURVE_NAMES = ("mnt4753_g1", "mnt4753_g2", "mnt6753_g1", "mnt6753_g2")
 
 
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "msm_host_shim.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("msm_plan.h", "msm_fold.h", "msm_schedule.h", "host_math.h", "ec29.h", "fp29.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("msm_host")
     for f in (lib.t_auto_window, lib.t_precompute_window):
         f.argtypes = [U64, ctypes.c_int, ctypes.c_int]
     lib.t_plan_msm.argtypes = [U64] + [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_int64)]

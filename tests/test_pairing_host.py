@@ -18,9 +18,9 @@ import pytest
 
 import pairing_ref
 import pyref
+import shim_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "build", "libpairing_shim.so")
 GH_E_BAD_ARG, GH_E_NO_DEVICE = -1, -3
 V = ctypes.c_void_p
 # the shim's tower operations (tests/host_shim/pairing_shim.cpp)
@@ -32,13 +32,7 @@ M4, M6 = pairing_ref.engine("mnt4753"), pairing_ref.engine("mnt6753")
 
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "pairing_shim.cpp")
-    deps = [src] + [os.path.join(ROOT, "ginger-lib_amd", "csrc", f)
-                    for f in ("fp29.h", "ec29.h", "pairing29.h", "pairing29_mnt6.h", "pairing_constants_gen.h", "constants_gen.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("pairing")
     I = ctypes.c_int
     lib.t_pairing_product.argtypes = [I, V, V, V, V, I, V]
     lib.t_pairing_prepared.argtypes = [I, V, V, V]

@@ -4,17 +4,16 @@ restatement's bits, and the argument checks / exports of include/ginger_hip_pede
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import pedersen_ref
 import pyref
+import shim_build
 from schnorr_ref import mul
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "build", "libpedersen_shim.so")
 GH_E_BAD_ARG, GH_E_UNSUPPORTED, GH_E_NO_DEVICE = -1, -2, -3
 MNT4_G1, MNT4_G2, MNT6_G1, MNT6_G2 = 0, 1, 2, 3
 CURVE_ID = {"mnt4753_g1": MNT4_G1, "mnt6753_g1": MNT6_G1}
@@ -53,12 +52,7 @@ def test_restatement_closed_form_with_recipe_generators(cname, wn):
 # ---- 2. the digit header against the restatement
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "pedersen_shim.cpp")
-    deps = [src, os.path.join(ROOT, "ginger-lib_amd", "csrc", "pedersen_digits.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("pedersen")
     u64, ci, vp = ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p
     lib.t_ped_positions.argtypes, lib.t_ped_positions.restype = [u64, ci], u64
     lib.t_ped_row_positions.argtypes, lib.t_ped_row_positions.restype = [u64, ci], u64

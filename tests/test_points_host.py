@@ -15,10 +15,10 @@ import pytest
 
 import points_ref as pr
 import pyref
+import shim_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ginger-lib_amd", "csrc")
-SHIM = os.path.join(ROOT, "build", "libpoints_shim.so")
 KATS = json.load(open(os.path.join(ROOT, "tests", "golden", "compression_kats.json")))
 GH_E_BAD_ARG, GH_E_NO_DEVICE = -1, -3
 V = ctypes.c_void_p
@@ -29,12 +29,7 @@ FIELDS = {0: pyref.Ext(pyref.P4, 1, 0), 1: pyref.Ext(pyref.P6, 1, 0), 2: pyref.C
 
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "points_shim.cpp")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("fp29.h", "ec29.h", "sqrt29.h", "sqrt_constants_gen.h", "constants_gen.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("points")
     lib.pts_sqrt.argtypes = [ctypes.c_int, V, V]
     lib.pts_decompress.argtypes = [ctypes.c_int, V, ctypes.c_uint8, V, V]
     lib.pts_compress.argtypes = [ctypes.c_int, V, ctypes.c_uint8, V]
@@ -239,11 +234,8 @@ def test_bit_vectors_round_trip():
 
 # ---- 4. the stand-alone check under the host sanitizers: a program of its own, nothing sanitised is loaded into python
 def test_sanitized_standalone_check(tmp_path):
-    exe = str(tmp_path / "points_check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "host_shim", "points_check.cpp"), "-o", exe])
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:]
+    out = shim_build.sanitized_check("points_check.cpp", str(tmp_path / "points_check"))
+    assert out.returncode == 0 and (out.stdout + out.stderr).strip().endswith("ok"), (out.stdout + out.stderr)[-2000:]
 
 
 # ---- 5. the C ABI without a device

@@ -6,16 +6,14 @@ import ctypes
 import importlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import poly_ref as ref
+import shim_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ginger-lib_amd", "csrc")
-SHIM = os.path.join(ROOT, "build", "libpoly_shim.so")
 GH_E_BAD_ARG, GH_E_UNSUPPORTED = -1, -2
 V, U64, U32, I = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
 FIELD_ID = {"mnt4753_fr": 0, "mnt6753_fr": 1}
@@ -30,12 +28,7 @@ def poly(gl):
 
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "poly_shim.cpp")
-    deps = [src, os.path.join(ROOT, "tests", "host_shim", "poly_host.h")] + [os.path.join(CSRC, f) for f in ("fp29.h", "poly_plan.h", "poly_kernels.h", "constants_gen.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("poly")
     lib.poly_shim_evaluate.argtypes = [I, V, U64, V, U64, U32, U32, V]
     lib.poly_shim_divide_linear.argtypes = [I, V, U64, V, U32, U32, V, V]
     lib.poly_shim_divide_vanishing.argtypes = [I, V, U64, U32, U32, V, V]
@@ -256,8 +249,5 @@ def test_package_module_has_no_test_dependency():
 
 # ---- 5. the stand-alone check under the host sanitizers: a program of its own, nothing sanitised is loaded into python
 def test_sanitized_standalone_check(tmp_path):
-    exe = str(tmp_path / "poly_check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "host_shim", "poly_check.cpp"), "-o", exe])
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:]
+    out = shim_build.sanitized_check("poly_check.cpp", str(tmp_path / "poly_check"))
+    assert out.returncode == 0 and (out.stdout + out.stderr).strip().endswith("ok"), (out.stdout + out.stderr)[-2000:]

@@ -12,9 +12,9 @@ import pytest
 
 import poseidon_ref
 import pyref
+import shim_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "build", "libposeidon_shim.so")
 TAGS = ["mnt4753", "mnt6753"]
 U = ctypes.c_uint32
 GH_E_BAD_ARG, GH_E_NO_DEVICE = -1, -3
@@ -22,12 +22,7 @@ GH_E_BAD_ARG, GH_E_NO_DEVICE = -1, -3
 
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "poseidon_shim.cpp")
-    deps = [src] + [os.path.join(ROOT, "ginger-lib_amd", "csrc", f) for f in ("fp29.h", "poseidon_perm.h", "constants_gen.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("poseidon")
     lib.t_poseidon_perm.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     return lib
 

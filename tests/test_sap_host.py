@@ -16,10 +16,9 @@ import pytest
 import pyref
 import r1cs_ref
 import sap_ref as ref
+import shim_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ginger-lib_amd", "csrc")
-SHIM = os.path.join(ROOT, "build", "libsap_shim.so")
 GH_E_BAD_ARG, GH_E_UNSUPPORTED, GH_E_NO_DEVICE, GH_E_BAD_HANDLE = -1, -2, -3, -6
 V = ctypes.c_void_p
 U64, U32 = ctypes.c_uint64, ctypes.c_uint32
@@ -45,13 +44,7 @@ def mods(gl):
 
 @pytest.fixture(scope="module")
 def shim(r1cs):
-    src = os.path.join(ROOT, "tests", "host_shim", "sap_shim.cpp")
-    deps = [src, os.path.join(ROOT, "tests", "host_shim", "sap_host.h"), os.path.join(ROOT, "include", "ginger_hip_r1cs.h")]
-    deps += [os.path.join(CSRC, f) for f in ("fp29.h", "r1cs_plan.h", "sap_rows.h", "constants_gen.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("sap")
     M = ctypes.POINTER(r1cs.Matrix)
     lib.sap_shim_info.argtypes = [ctypes.c_int, U64, U64, U64, ctypes.POINTER(U32), ctypes.POINTER(U64), ctypes.POINTER(U64)]
     lib.sap_shim_rows.argtypes = [ctypes.c_int, U64, U64, U64, M, U32, V, V, V, V, V, V]
@@ -257,11 +250,8 @@ def test_package_module_has_no_test_dependency():
 
 # ---- 4. the stand-alone check under the host sanitizers: a program of its own, nothing sanitised is loaded into python
 def test_sanitized_standalone_check(tmp_path):
-    exe = str(tmp_path / "sap_check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "host_shim", "sap_check.cpp"), "-o", exe])
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:]
+    out = shim_build.sanitized_check("sap_check.cpp", str(tmp_path / "sap_check"))
+    assert out.returncode == 0 and (out.stdout + out.stderr).strip().endswith("ok"), (out.stdout + out.stderr)[-2000:]
 
 
 # ---- 5. the Rust side (delivered as files: no Rust toolchain checks them here)

@@ -13,9 +13,9 @@ import pytest
 
 import pyref
 import schnorr_ref
+import shim_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "build", "libschnorr_shim.so")
 SCHEMES = list(schnorr_ref.SCHEMES)
 GH_E_BAD_ARG, GH_E_UNSUPPORTED, GH_E_NO_DEVICE = -1, -2, -3
 MNT4_G1, MNT4_G2, MNT6_G1 = 0, 1, 2
@@ -69,12 +69,7 @@ def test_restatement_scalar_multiplication(refs, scheme):
 # ---- the recoding the kernel runs
 @pytest.fixture(scope="module")
 def shim():
-    src = os.path.join(ROOT, "tests", "host_shim", "schnorr_shim.cpp")
-    deps = [src] + [os.path.join(ROOT, "ginger-lib_amd", "csrc", f) for f in ("fp29.h", "schnorr_recode.h", "constants_gen.h")]
-    os.makedirs(os.path.dirname(SHIM), exist_ok=True)
-    if not os.path.exists(SHIM) or os.path.getmtime(SHIM) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SHIM, src])
-    lib = ctypes.CDLL(SHIM)
+    lib = shim_build.host_shim("schnorr")
     lib.t_vb_recode.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     return lib
 
